@@ -29,6 +29,13 @@ N=8 takes 1.37 ms against a 1.5 ms forward (profiles/h2d_bandwidth.txt): the ran
 PCIe link, not xGMI, would bound the node, which is why it is not the default. Data
 is synthetic (random uint8 images) and the weights are random-init of the exact
 architecture (no network for checkpoints).
+
+A plain run does what the throughput figure needs and no more: set up, settle, warm up, time
+``--steps`` steps, print one JSON line (``value`` images/s, ``ms_per_step``). ``--full`` adds the
+unloaded per-batch latency (``p50_latency_ms`` / ``p99_latency_ms``, 20 batches one at a time after
+the timed steps). ``--dump-outputs DIR`` writes the logits the last timed step delivered to the host
+as ``DIR/logits.npy``; the inputs are seeded and do not depend on how long the settle took, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -120,8 +128,18 @@ def main(argv=None) -> int:
                     help="permit more ranks than visible GPUs (ranks share GPUs; the JSON says gpus_shared)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launcher / rank wiring: gloo group, no GPU, one JSON line")
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps right before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the unloaded per-batch latency "
+                         "(p50_latency_ms / p99_latency_ms, one batch in flight, after the timed steps). A plain "
+                         "run sets up, settles, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step delivered to the host, the fp32 "
+                         "logits [global batch, classes] on rank 0, to DIR/logits.npy (float32; with --egress "
+                         "local on several ranks every rank writes DIR/logits_rank<r>.npy). The synthetic inputs "
+                         "are seeded and the last timed step always reads the same one of them, so the same "
+                         "arguments give the same inputs in every run")
     ap.add_argument("--settle", type=float, default=0.5,
                     help="minimum seconds of untimed pipelined steps before the warmup steps (GPU clock ramp)")
     ap.add_argument("--settle-max", type=float, default=3.0,
@@ -451,6 +469,12 @@ def main(argv=None) -> int:
             more = bool(t.item())
         if not more:
             break
+    # step i uses input slot i % NS: a few more untimed steps bring the warmup to slot 0 however many
+    # chunks the settle took, so the last timed step reads the same synthetic batch in every run
+    # (--dump-outputs compares builds output for output)
+    while nxt % NS:
+        step(nxt)
+        nxt += 1
     settle_s = time.perf_counter() - t_start
     if rank == 0:   # settle trajectory of the untimed pipelined steps (fresh-lease diagnosis, stderr only)
         print("settle chunks (10 pipelined steps, ms): " + " ".join(f"{c:.2f}" for c in chunk_ms), file=sys.stderr)
@@ -485,9 +509,19 @@ def main(argv=None) -> int:
         t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
-    # unloaded per-batch latency (same path, one batch in flight at a time), outside the timed region
+    if a.dump_outputs:
+        # what the last timed step delivered: its slot's pinned host logits (every copy has completed)
+        j_last = (nxt + total - 1) % NS
+        writes = rank == 0 if gather or not dist_on else True
+        if a.steps > 0 and writes:
+            name = "logits" if rank == 0 else f"logits_rank{rank}"
+            rows = n_global if gather or not dist_on else B
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, name + ".npy"),
+                    out_host[j_last][:rows].numpy().astype(np.float32))
+    # --full: unloaded per-batch latency (same path, one batch in flight at a time), outside the timed region
     lat = []
-    for k in range(min(20, total)):
+    for k in range(min(20, total) if a.full else 0):
         if dist_on:
             dist.barrier()
         torch.cuda.synchronize()
@@ -496,7 +530,7 @@ def main(argv=None) -> int:
         collect(k, timed=True)
         torch.cuda.synchronize()
         lat.append(t_in[k].elapsed_time(t_out[k]))
-    if dist_on:
+    if dist_on and lat:
         t = torch.tensor(lat, device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         lat = t.tolist()
@@ -519,11 +553,13 @@ def main(argv=None) -> int:
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(ms_step, 4),
-            "p50_latency_ms": round(statistics.median(lat), 4),
-            "p99_latency_ms": round(sorted(lat)[min(len(lat) - 1, int(0.99 * len(lat)))], 4),
+            **({"p50_latency_ms": round(statistics.median(lat), 4),
+                "p99_latency_ms": round(sorted(lat)[min(len(lat) - 1, int(0.99 * len(lat)))], 4),
+                "latency_note": "p50/p99: one batch in flight (H2D start -> logits on host), measured "
+                                "after the timed loop; the timed loop overlaps batch i+1's H2D with batch i"}
+               if lat else {}),
             "settle_s": round(settle_s, 3),
-            "latency_note": "p50/p99: one batch in flight (H2D start -> logits on host), measured "
-                            "after the timed loop; the timed loop overlaps batch i+1's H2D with batch i",
+            "full": a.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": (None if BASELINE_IMG_S is None or a.model != "xception"

@@ -40,6 +40,18 @@ def test_self_launch_starts_every_rank(n):
     assert len({s[4] for s in seen}) == 1                 # one rendezvous port
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    # --full (the measurements beside the headline figure) and --dump-outputs DIR exist; the CPU
+    # rehearsal computes nothing, so it writes nothing
+    out = tmp_path / "out"
+    r = _run(["--gpus", "1", "--dry-run", "--full", "--dump-outputs", str(out), "--steps", "3", "--warmup", "1"],
+             _env(), timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert res["steps"] == 3 and res["dry_run"] is True
+    assert not out.exists()
+
+
 def test_more_ranks_than_visible_gpus_is_refused():
     # refused in the launcher parent, before any rank (or any GPU call) starts
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], _env(HIP_VISIBLE_DEVICES="0"), timeout=120)
