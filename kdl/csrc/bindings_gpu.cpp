@@ -199,6 +199,17 @@ ResizeArgs resize_args(const py::dict& d) {
   return a;
 }
 
+JpegArgs jpeg_args(const py::dict& d) {
+  JpegArgs a{};
+  a.desc = P<const JpegDesc>(d, "desc"); a.h_desc = P<const JpegDesc>(d, "h_desc");
+  a.coef = P<const int16_t>(d, "coef"); a.qt = P<const uint16_t>(d, "qt");
+  a.planes = P<uint8_t>(d, "planes"); a.out = P<uint8_t>(d, "out");
+  a.coef_cap = d["coef_cap"].cast<uint64_t>(); a.plane_cap = d["plane_cap"].cast<uint64_t>();
+  a.qt_cap = I(d, "qt_cap"); a.n = I(d, "n"); a.n_wg = I(d, "n_wg"); a.out_rows = I(d, "out_rows");
+  a.OH = I(d, "OH"); a.OW = I(d, "OW");
+  return a;
+}
+
 DwArgs dw_args(const py::dict& d) {
   DwArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.w = P<const float>(d, "w"); a.y = P<uint16_t>(d, "y");
@@ -333,6 +344,17 @@ PYBIND11_MODULE(_C, m) {
     const auto a = resize_args(d);
     py::gil_scoped_release nogil;
     chk(resize_nearest_u8(a, S(s)), "resize_nearest_u8");
+  });
+  // baseline JPEG (kernels/jpeg.hip): d = the JpegArgs fields; h_desc is a HOST address
+  m.def("jpeg_idct_u8", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_idct_u8(a, S(s)), "jpeg_idct_u8");
+  });
+  m.def("jpeg_sample_rgb_u8", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_sample_rgb_u8(a, S(s)), "jpeg_sample_rgb_u8");
   });
   m.def("u8_to_bf16_norm", [](uintptr_t x, uintptr_t y, long npix, int ldy, uintptr_t s) {
     py::gil_scoped_release nogil;

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 
@@ -18,6 +19,7 @@
 #include "runtime/grpc_front.h"
 #include "runtime/grpc_load.h"
 #include "runtime/h2.h"
+#include "runtime/jpeg.h"
 #include "runtime/sstable.h"
 #include "runtime/tfproto.h"
 
@@ -432,6 +434,80 @@ PYBIND11_MODULE(_rt, m) {
   m.attr("DP_BATCH") = int(DP_BATCH);
   m.attr("DP_RELOAD") = int(DP_RELOAD);
   m.attr("DP_PING") = int(DP_PING);
+
+  // ---- baseline JPEG (runtime/jpeg.h): host entropy decode + the CPU pixel path of serving_bytes
+  py::class_<JpegHeader>(m, "JpegHeader")
+      .def_readonly("W", &JpegHeader::W)
+      .def_readonly("H", &JpegHeader::H)
+      .def_readonly("ncomp", &JpegHeader::ncomp)
+      .def_readonly("hmax", &JpegHeader::hmax)
+      .def_readonly("vmax", &JpegHeader::vmax)
+      .def_readonly("ncoef", &JpegHeader::ncoef)
+      .def_readonly("restart", &JpegHeader::restart)
+      .def_property_readonly("why", [](const JpegHeader& h) { return std::string(h.why); })
+      // per component: (id, h, v, tq, bw, bh, dw, dh, coef_off)
+      .def_property_readonly("comps", [](const JpegHeader& h) {
+        py::list out;
+        for (int c = 0; c < h.ncomp; ++c) {
+          const JpegComp& k = h.comp[c];
+          out.append(py::make_tuple(k.id, k.h, k.v, k.tq, k.bw, k.bh, k.dw, k.dh, k.coef_off));
+        }
+        return out;
+      })
+      .def_property_readonly("qt", [](const JpegHeader& h) {     // uint16 [4][64], natural order
+        py::array_t<uint16_t> a({4, 64});
+        std::memcpy(a.mutable_data(), h.qt, sizeof(h.qt));
+        return a;
+      });
+  m.def("jpeg_probe", [](py::bytes data, uint64_t max_pixels) {
+    std::string_view sv = data;
+    JpegHeader h;
+    int st;
+    {
+      py::gil_scoped_release nogil;
+      st = jpeg_probe(reinterpret_cast<const uint8_t*>(sv.data()), sv.size(), max_pixels, &h);
+    }
+    return py::make_tuple(st, h);
+  }, py::arg("data"), py::arg("max_pixels") = uint64_t(64) << 20);
+  // `coef`: a writable buffer of at least header.ncoef int16 (pinned staging on GPU servers)
+  m.def("jpeg_parse", [](py::bytes data, py::buffer coef, uint64_t max_pixels) {
+    std::string_view sv = data;
+    py::buffer_info ci = coef.request(true);
+    if (reinterpret_cast<uintptr_t>(ci.ptr) % alignof(int16_t)) throw std::invalid_argument("jpeg_parse: unaligned buffer");
+    const uint64_t cap = uint64_t(ci.size) * uint64_t(ci.itemsize) / sizeof(int16_t);
+    JpegHeader h;
+    int st;
+    {
+      py::gil_scoped_release nogil;
+      st = jpeg_parse(reinterpret_cast<const uint8_t*>(sv.data()), sv.size(), max_pixels,
+                      static_cast<int16_t*>(ci.ptr), cap, &h);
+    }
+    return py::make_tuple(st, h);
+  }, py::arg("data"), py::arg("coef"), py::arg("max_pixels") = uint64_t(64) << 20);
+  m.def("jpeg_pixels_cpu", [](const JpegHeader& h, py::buffer coef) {
+    py::buffer_info ci = coef.request();
+    if (uint64_t(ci.size) * uint64_t(ci.itemsize) / sizeof(int16_t) < h.ncoef || h.ncomp < 1)
+      throw std::invalid_argument("jpeg_pixels_cpu: coefficient buffer smaller than the header's planes");
+    py::array_t<uint8_t> out({h.H, h.W, 3});
+    uint8_t* o = out.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      jpeg_pixels_cpu(h, static_cast<const int16_t*>(ci.ptr), o);
+    }
+    return out;
+  });
+  // one image's descriptor of a GPU decode call -> (raw JpegDesc bytes, next free workgroup)
+  m.def("jpeg_desc", [](const JpegHeader& h, uint64_t coef_base, uint64_t plane_base, int32_t qt_base, int32_t wg,
+                        int32_t out_row, uint64_t ytab, uint64_t xtab) {
+    JpegDesc d;
+    jpeg_fill_desc(h, coef_base, plane_base, qt_base, &wg, out_row, ytab, xtab, &d);
+    return py::make_tuple(py::bytes(reinterpret_cast<const char*>(&d), sizeof(d)), wg);
+  }, py::arg("header"), py::arg("coef_base"), py::arg("plane_base"), py::arg("qt_base"), py::arg("wg"),
+     py::arg("out_row"), py::arg("ytab"), py::arg("xtab"));
+  m.attr("JPEG_DESC_BYTES") = int(sizeof(JpegDesc));
+  m.attr("JPEG_OK") = int(JPEG_OK);
+  m.attr("JPEG_UNSUPPORTED") = int(JPEG_UNSUPPORTED);
+  m.attr("JPEG_MALFORMED") = int(JPEG_MALFORMED);
 
   m.attr("ST_OK") = int(ST_OK);
   m.attr("ST_DEADLINE") = int(ST_DEADLINE);

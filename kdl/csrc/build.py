@@ -50,7 +50,7 @@ GPU_SOURCES = sorted((HERE / "kernels").glob("*.hip")) + [HERE / "runtime" / "en
                                                          HERE / "runtime" / "dp_hiploop.cpp",
                                                          HERE / "bindings_gpu.cpp"]
 RT_SOURCES = [HERE / "runtime" / n for n in ("batcher.cpp", "executor.cpp", "tfproto.cpp", "sstable.cpp", "dp_loop.cpp",
-                                                "h2.cpp", "grpc_front.cpp", "grpc_load.cpp")] + [
+                                                "h2.cpp", "grpc_front.cpp", "grpc_load.cpp", "jpeg.cpp")] + [
     HERE / "bindings_rt.cpp"]
 HEADERS = sorted(HERE.rglob("*.h"))
 

@@ -318,6 +318,24 @@ struct ResizeArgs {
 };
 hipError_t resize_nearest_u8(const ResizeArgs& a, hipStream_t s);
 
+// Baseline JPEG pixel work (kernels/jpeg.hip): the host has entropy-decoded n images into
+// coefficient planes (runtime/jpeg.h); jpeg_idct_u8 makes uint8 sample planes of all of them,
+// jpeg_sample_rgb_u8 gathers each image's resized RGB into row desc.out_row of out. Both
+// launchers check every descriptor (the host copy) against the capacities given here.
+struct JpegDesc;
+struct JpegArgs {
+  const JpegDesc* desc;     // [n] in device memory
+  const JpegDesc* h_desc;   // the same [n] in host memory (checked, never dereferenced on the device)
+  const int16_t* coef;      // coefficients, coef_cap int16
+  const uint16_t* qt;       // quantisation tables, natural order, qt_cap uint16
+  uint8_t* planes;          // sample-plane scratch, plane_cap bytes
+  uint8_t* out;             // [out_rows][OH][OW][3]
+  uint64_t coef_cap, plane_cap;
+  int qt_cap, n, n_wg, out_rows, OH, OW;
+};
+hipError_t jpeg_idct_u8(const JpegArgs& a, hipStream_t s);
+hipError_t jpeg_sample_rgb_u8(const JpegArgs& a, hipStream_t s);
+
 // Elementwise: uint8 HWC image -> Xception-normalised bf16 NHWC padded to ldy
 // (x/127.5 - 1), used by the non-folded path and by tests.
 hipError_t u8_to_bf16_norm(const uint8_t* x, uint16_t* y, long npix, int ldy, hipStream_t s);

@@ -1,0 +1,455 @@
+// Baseline JPEG: marker walk + Huffman decode on the host, and the CPU pixel path (jpeg.h).
+// The input is untrusted: every read is bounded by the buffer and every index by its table.
+#include "runtime/jpeg.h"
+
+#include <cstring>
+#include <vector>
+
+namespace kdl {
+namespace {
+
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+constexpr int kFast = 9;
+
+struct Huff {
+  bool defined = false;
+  int nvals = 0;
+  uint16_t fast[1 << kFast];   // (length << 8) | symbol for codes of <= kFast bits, 0 = longer
+  // AC shortcut: code and magnitude bits both inside the kFast-bit window:
+  // (value << 8) | (run << 4) | (code length + magnitude bits), 0 = take the long way
+  int16_t fast_ac[1 << kFast];
+  int32_t maxcode[17];         // last code of each length (next free code - 1)
+  int32_t valoff[17];          // vals index = valoff[len] + code
+  uint8_t vals[256];
+};
+
+// canonical code from the 16 counts; false when the counts do not form a prefix code
+bool build_huff(const uint8_t* counts, const uint8_t* vals, int nvals, Huff* t) {
+  std::memset(t->fast, 0, sizeof(t->fast));
+  std::memcpy(t->vals, vals, (size_t)nvals);
+  t->nvals = nvals;
+  int32_t code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    t->valoff[len] = k - code;
+    for (int i = 0; i < counts[len - 1]; ++i, ++k, ++code) {
+      if (code >= (1 << len)) return false;
+      if (len <= kFast) {
+        const int lo = code << (kFast - len);
+        for (int j = 0; j < (1 << (kFast - len)); ++j) t->fast[lo + j] = (uint16_t)((len << 8) | vals[k]);
+      }
+    }
+    t->maxcode[len] = code - 1;
+    code <<= 1;
+  }
+  for (int i = 0; i < (1 << kFast); ++i) {
+    t->fast_ac[i] = 0;
+    const uint16_t f = t->fast[i];
+    const int len = f >> 8, run = (f >> 4) & 15, mag = f & 15;
+    if (!f || !mag || len + mag > kFast) continue;
+    int v = ((i << len) & ((1 << kFast) - 1)) >> (kFast - mag);
+    if (v < (1 << (mag - 1))) v += 1 - (1 << mag);
+    if (v >= -128 && v <= 127) t->fast_ac[i] = (int16_t)(v * 256 + run * 16 + len + mag);
+  }
+  t->defined = true;
+  return true;
+}
+
+// MSB-first bit reader over entropy-coded data: removes FF00 stuffing and fill bytes, stops at a
+// marker (or the end of the buffer) and feeds zero bits from there on; a decoder that consumed
+// any of those zero bits ran past the data (overrun())
+struct Bits {
+  const uint8_t* p;
+  const uint8_t* end;
+  uint64_t buf = 0;
+  int cnt = 0;       // valid bits in buf (from the top)
+  int npad = 0;      // zero bytes fed since the last reset
+  bool stopped = false;
+
+  // afterwards at least 32 bits are valid: one Huffman code (<= 16) and its magnitude bits (<= 15)
+  void fill() {
+    if (cnt > 32) return;
+    if (!stopped && end - p >= 4) {      // four bytes without an FF: no stuffing, no marker
+      const uint32_t w = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+      const uint32_t x = ~w;
+      if (((x - 0x01010101u) & ~x & 0x80808080u) == 0) {
+        buf |= (uint64_t)w << (32 - cnt);
+        cnt += 32;
+        p += 4;
+        return;
+      }
+    }
+    while (cnt <= 56) {
+      uint32_t b = 0;
+      if (!stopped) {
+        if (p >= end) {
+          stopped = true;
+        } else if (*p != 0xFF) {
+          b = *p++;
+        } else if (p + 1 >= end) {
+          stopped = true;
+        } else if (p[1] == 0x00) {
+          b = 0xFF;
+          p += 2;
+        } else if (p[1] == 0xFF) {   // fill byte
+          ++p;
+          continue;
+        } else {
+          stopped = true;            // a marker: p stays on its FF
+        }
+      }
+      if (stopped) ++npad;
+      buf |= (uint64_t)b << (56 - cnt);
+      cnt += 8;
+    }
+  }
+  uint32_t peek16() const { return (uint32_t)(buf >> 48); }
+  void skip(int n) { buf <<= n; cnt -= n; }
+  uint32_t get(int n) {               // 1 <= n <= 16
+    const uint32_t v = (uint32_t)(buf >> (64 - n));
+    skip(n);
+    return v;
+  }
+  bool overrun() const { return cnt < npad * 8; }
+  void reset() { buf = 0; cnt = 0; npad = 0; stopped = false; }
+};
+
+// one Huffman symbol, or -1 for a bit string that is no code; needs >= 16 bits in the buffer
+inline int decode(Bits& b, const Huff& t) {
+  const uint32_t pk = b.peek16();
+  const uint16_t f = t.fast[pk >> (16 - kFast)];
+  if (f) {
+    b.skip(f >> 8);
+    return f & 255;
+  }
+  for (int len = kFast + 1; len <= 16; ++len) {
+    const int32_t code = (int32_t)(pk >> (16 - len));
+    if (code <= t.maxcode[len]) {
+      const int32_t idx = t.valoff[len] + code;
+      if (idx < 0 || idx >= t.nvals) return -1;
+      b.skip(len);
+      return t.vals[idx];
+    }
+  }
+  return -1;
+}
+
+inline int extend(uint32_t v, int s) { return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
+
+inline uint32_t be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
+
+JpegStatus fail(JpegHeader* h, JpegStatus st, const char* why) {
+  h->why = why;
+  return st;
+}
+
+struct Parser {
+  const uint8_t* data;
+  size_t n;
+  uint64_t max_pixels;
+  JpegHeader* h;
+  Huff dc[4], ac[4];
+  bool have_qt[4] = {false, false, false, false};
+  bool have_sof = false, jfif = false, adobe = false;
+  int adobe_transform = 0;
+
+  JpegStatus sof0(const uint8_t* s, size_t sl) {
+    if (have_sof) return fail(h, JPEG_MALFORMED, "two frame headers");
+    if (sl < 6) return fail(h, JPEG_MALFORMED, "short SOF0");
+    const int prec = s[0], nc = s[5];
+    if (prec != 8) return fail(h, JPEG_UNSUPPORTED, "sample precision is not 8 bits");
+    if (nc != 1 && nc != 3) return fail(h, JPEG_UNSUPPORTED, "not 1 or 3 components");
+    if (sl != (size_t)(6 + 3 * nc)) return fail(h, JPEG_MALFORMED, "SOF0 length does not match its components");
+    h->H = (int)be16(s + 1);
+    h->W = (int)be16(s + 3);
+    if (h->W == 0 || h->H == 0) return fail(h, JPEG_MALFORMED, "zero image dimension");
+    if ((uint64_t)h->W * (uint64_t)h->H > max_pixels) return fail(h, JPEG_MALFORMED, "image exceeds the pixel limit");
+    h->ncomp = nc;
+    for (int c = 0; c < nc; ++c) {
+      JpegComp& k = h->comp[c];
+      k.id = s[6 + 3 * c];
+      k.h = s[7 + 3 * c] >> 4;
+      k.v = s[7 + 3 * c] & 15;
+      k.tq = s[8 + 3 * c];
+      if (k.h < 1 || k.h > 4 || k.v < 1 || k.v > 4) return fail(h, JPEG_MALFORMED, "sampling factor out of range");
+      if (k.tq > 3) return fail(h, JPEG_MALFORMED, "quantisation table id out of range");
+    }
+    if (nc == 1) {      // a single-component scan is never interleaved: its factors mean nothing
+      h->comp[0].h = h->comp[0].v = 1;
+    } else {
+      const JpegComp& y = h->comp[0];
+      const bool luma = (y.h == 1 && y.v == 1) || (y.h == 2 && y.v == 1) || (y.h == 2 && y.v == 2);
+      if (!luma || h->comp[1].h != 1 || h->comp[1].v != 1 || h->comp[2].h != 1 || h->comp[2].v != 1)
+        return fail(h, JPEG_UNSUPPORTED, "sampling other than 4:4:4, 4:2:2, 4:2:0");
+    }
+    h->hmax = h->comp[0].h;
+    h->vmax = h->comp[0].v;
+    const int mx = (h->W + 8 * h->hmax - 1) / (8 * h->hmax), my = (h->H + 8 * h->vmax - 1) / (8 * h->vmax);
+    uint64_t off = 0;
+    for (int c = 0; c < nc; ++c) {
+      JpegComp& k = h->comp[c];
+      k.bw = mx * k.h;
+      k.bh = my * k.v;
+      k.dw = (h->W * k.h + h->hmax - 1) / h->hmax;
+      k.dh = (h->H * k.v + h->vmax - 1) / h->vmax;
+      k.coef_off = off;
+      off += (uint64_t)k.bw * (uint64_t)k.bh * 64;
+    }
+    h->ncoef = off;
+    have_sof = true;
+    return JPEG_OK;
+  }
+
+  JpegStatus dqt(const uint8_t* s, size_t sl) {
+    size_t i = 0;
+    while (i < sl) {
+      const int pq = s[i] >> 4, tq = s[i] & 15;
+      if (tq > 3) return fail(h, JPEG_MALFORMED, "quantisation table id out of range");
+      if (pq == 1) return fail(h, JPEG_UNSUPPORTED, "16-bit quantisation table");
+      if (pq != 0) return fail(h, JPEG_MALFORMED, "bad quantisation table precision");
+      if (sl - i < 65) return fail(h, JPEG_MALFORMED, "short DQT");
+      for (int k = 0; k < 64; ++k) h->qt[tq][kZigzag[k]] = s[i + 1 + k];
+      have_qt[tq] = true;
+      i += 65;
+    }
+    return JPEG_OK;
+  }
+
+  JpegStatus dht(const uint8_t* s, size_t sl) {
+    size_t i = 0;
+    while (i < sl) {
+      const int tc = s[i] >> 4, th = s[i] & 15;
+      if (tc > 1 || th > 3) return fail(h, JPEG_MALFORMED, "Huffman table id out of range");
+      if (sl - i < 17) return fail(h, JPEG_MALFORMED, "short DHT");
+      int total = 0;
+      for (int k = 0; k < 16; ++k) total += s[i + 1 + k];
+      if (total > 256 || sl - i - 17 < (size_t)total) return fail(h, JPEG_MALFORMED, "DHT symbols past its segment");
+      if (!build_huff(s + i + 1, s + i + 17, total, tc ? &ac[th] : &dc[th]))
+        return fail(h, JPEG_MALFORMED, "DHT counts are not a prefix code");
+      i += 17 + (size_t)total;
+    }
+    return JPEG_OK;
+  }
+
+  JpegStatus scan(const uint8_t* s, size_t sl, size_t pos, int16_t* coef, uint64_t cap) {
+    if (!have_sof) return fail(h, JPEG_MALFORMED, "scan before the frame header");
+    if (sl < 1) return fail(h, JPEG_MALFORMED, "short SOS");
+    const int ns = s[0];
+    if (ns < 1 || ns > 4 || sl != (size_t)(4 + 2 * ns)) return fail(h, JPEG_MALFORMED, "SOS length does not match");
+    if (ns != h->ncomp) return fail(h, JPEG_UNSUPPORTED, "more than one scan");
+    const Huff* tdc[3];
+    const Huff* tac[3];
+    for (int c = 0; c < ns; ++c) {
+      if (s[1 + 2 * c] != h->comp[c].id) return fail(h, JPEG_UNSUPPORTED, "scan components not in frame order");
+      const int td = s[2 + 2 * c] >> 4, ta = s[2 + 2 * c] & 15;
+      if (td > 3 || ta > 3) return fail(h, JPEG_MALFORMED, "Huffman table id out of range");
+      if (!dc[td].defined || !ac[ta].defined) return fail(h, JPEG_MALFORMED, "scan uses a missing Huffman table");
+      if (!have_qt[h->comp[c].tq]) return fail(h, JPEG_MALFORMED, "component uses a missing quantisation table");
+      tdc[c] = &dc[td];
+      tac[c] = &ac[ta];
+    }
+    if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0)
+      return fail(h, JPEG_UNSUPPORTED, "spectral selection / approximation in a sequential scan");
+    if (ns == 3) {   // colour rule: YCbCr with JFIF, with Adobe transform 1, or with ids 1,2,3
+      if (adobe && adobe_transform != 1) return fail(h, JPEG_UNSUPPORTED, "Adobe colour transform is not YCbCr");
+      const bool ids = h->comp[0].id == 1 && h->comp[1].id == 2 && h->comp[2].id == 3;
+      if (!jfif && !adobe && !ids) return fail(h, JPEG_UNSUPPORTED, "colour space is not known to be YCbCr");
+    }
+    if (cap < h->ncoef || coef == nullptr) return fail(h, JPEG_MALFORMED, "coefficient buffer too small");
+
+    Bits b{data + pos, data + n};
+    const int mx = h->comp[0].bw / h->comp[0].h, my = h->comp[0].bh / h->comp[0].v;
+    int pred[3] = {0, 0, 0};
+    int left = h->restart, next_rst = 0;
+    for (int y = 0; y < my; ++y) {
+      for (int x = 0; x < mx; ++x) {
+        if (h->restart && left == 0) {
+          // the interval's data ends at a marker: drop the padding bits, expect RSTn
+          if (!b.stopped) b.fill();
+          const uint8_t* q = b.p;
+          if (!b.stopped) {          // unread entropy bytes in front of the marker: skip to it
+            while (q + 1 < b.end && !(q[0] == 0xFF && q[1] != 0x00 && q[1] != 0xFF)) ++q;
+          }
+          while (q + 1 < b.end && q[0] == 0xFF && q[1] == 0xFF) ++q;
+          if (q + 1 >= b.end || q[0] != 0xFF || q[1] != 0xD0 + next_rst)
+            return fail(h, JPEG_MALFORMED, "restart marker missing");
+          b.p = q + 2;
+          b.reset();
+          next_rst = (next_rst + 1) & 7;
+          left = h->restart;
+          pred[0] = pred[1] = pred[2] = 0;
+        }
+        for (int c = 0; c < ns; ++c) {
+          const JpegComp& k = h->comp[c];
+          for (int v = 0; v < k.v; ++v) {
+            for (int u = 0; u < k.h; ++u) {
+              const uint64_t blk = (uint64_t)(y * k.v + v) * (uint64_t)k.bw + (uint64_t)(x * k.h + u);
+              int16_t* out = coef + k.coef_off + blk * 64;
+              std::memset(out, 0, 128);
+              b.fill();
+              int s_ = decode(b, *tdc[c]);
+              if (s_ < 0) return fail(h, JPEG_MALFORMED, "bad Huffman code");
+              if (s_ > 11) return fail(h, JPEG_MALFORMED, "DC category out of range");
+              if (s_) {
+                b.fill();
+                pred[c] = (int16_t)(pred[c] + extend(b.get(s_), s_));
+              }
+              out[0] = (int16_t)pred[c];
+              for (int i = 1; i < 64;) {
+                b.fill();
+                const int16_t fa = tac[c]->fast_ac[b.buf >> (64 - kFast)];
+                if (fa) {
+                  i += (fa >> 4) & 15;
+                  if (i > 63) return fail(h, JPEG_MALFORMED, "coefficient index past 63");
+                  out[kZigzag[i++]] = (int16_t)(fa >> 8);
+                  b.skip(fa & 15);
+                  continue;
+                }
+                const int rs = decode(b, *tac[c]);
+                if (rs < 0) return fail(h, JPEG_MALFORMED, "bad Huffman code");
+                const int r = rs >> 4, sz = rs & 15;
+                if (sz == 0) {
+                  if (r != 15) break;     // end of block
+                  i += 16;
+                  continue;
+                }
+                i += r;
+                if (i > 63) return fail(h, JPEG_MALFORMED, "coefficient index past 63");
+                out[kZigzag[i]] = (int16_t)extend(b.get(sz), sz);
+                ++i;
+              }
+              if (b.overrun()) return fail(h, JPEG_MALFORMED, "entropy-coded data is truncated");
+            }
+          }
+        }
+        if (h->restart) --left;
+      }
+    }
+    return JPEG_OK;
+  }
+
+  JpegStatus run(int16_t* coef, uint64_t cap, bool probe) {
+    if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return fail(h, JPEG_UNSUPPORTED, "not a JPEG");
+    size_t pos = 2;
+    for (;;) {
+      if (pos >= n) return fail(h, JPEG_MALFORMED, "file ends before the scan");
+      if (data[pos] != 0xFF) return fail(h, JPEG_MALFORMED, "bytes between segments");
+      while (pos < n && data[pos] == 0xFF) ++pos;
+      if (pos >= n) return fail(h, JPEG_MALFORMED, "file ends before the scan");
+      const int m = data[pos++];
+      if (m == 0x00 || m == 0xD8 || m == 0xD9) return fail(h, JPEG_MALFORMED, "unexpected marker before the scan");
+      if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // stand-alone markers
+      if (n - pos < 2) return fail(h, JPEG_MALFORMED, "segment length past the end");
+      const size_t len = be16(data + pos);
+      if (len < 2 || len > n - pos) return fail(h, JPEG_MALFORMED, "segment length past the end");
+      const uint8_t* s = data + pos + 2;
+      const size_t sl = len - 2;
+      pos += len;
+      JpegStatus st = JPEG_OK;
+      switch (m) {
+        case 0xC0:
+          st = sof0(s, sl);
+          if (st == JPEG_OK && probe) return st;
+          break;
+        case 0xC1: case 0xC2: case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC8: case 0xC9: case 0xCA: case 0xCB:
+        case 0xCC: case 0xCD: case 0xCE: case 0xCF:
+          return fail(h, JPEG_UNSUPPORTED, "not baseline sequential Huffman (SOF0)");
+        case 0xC4:
+          if (!probe) st = dht(s, sl);
+          break;
+        case 0xDB:
+          st = dqt(s, sl);
+          break;
+        case 0xDD:
+          if (sl != 2) return fail(h, JPEG_MALFORMED, "bad DRI length");
+          h->restart = (int)be16(s);
+          break;
+        case 0xE0:
+          if (sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) jfif = true;
+          break;
+        case 0xEE:
+          if (sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+            adobe = true;
+            adobe_transform = s[11];
+          }
+          break;
+        case 0xDA:
+          if (probe) return fail(h, JPEG_MALFORMED, "scan before the frame header");
+          return scan(s, sl, pos, coef, cap);
+        default:      // APPn, COM and anything else with a length: skipped
+          break;
+      }
+      if (st != JPEG_OK) return st;
+    }
+  }
+};
+
+void idct_block(const int16_t* c, const uint16_t* q, uint8_t* out, size_t stride) {
+  uint32_t ws[64], in[8], o[8];
+  for (int col = 0; col < 8; ++col) {
+    for (int r = 0; r < 8; ++r) in[r] = (uint32_t)(int32_t)c[r * 8 + col] * (uint32_t)q[r * 8 + col];
+    jpeg_idct_1d(in, o);
+    for (int r = 0; r < 8; ++r) ws[r * 8 + col] = (uint32_t)jpeg_descale(o[r], 11);
+  }
+  for (int r = 0; r < 8; ++r) {
+    jpeg_idct_1d(ws + r * 8, o);
+    for (int col = 0; col < 8; ++col) out[r * stride + col] = jpeg_clamp(jpeg_descale(o[col], 18) + 128);
+  }
+}
+
+}  // namespace
+
+JpegStatus jpeg_probe(const uint8_t* data, size_t n, uint64_t max_pixels, JpegHeader* h) {
+  *h = JpegHeader{};
+  std::vector<Parser> p(1);       // the Huffman tables are too large for a handler thread's stack
+  p[0].data = data; p[0].n = n; p[0].max_pixels = max_pixels; p[0].h = h;
+  return p[0].run(nullptr, 0, true);
+}
+
+JpegStatus jpeg_parse(const uint8_t* data, size_t n, uint64_t max_pixels, int16_t* coef, uint64_t cap,
+                      JpegHeader* h) {
+  *h = JpegHeader{};
+  std::vector<Parser> p(1);
+  p[0].data = data; p[0].n = n; p[0].max_pixels = max_pixels; p[0].h = h;
+  return p[0].run(coef, cap, false);
+}
+
+void jpeg_fill_desc(const JpegHeader& h, uint64_t coef_base, uint64_t plane_base, int32_t qt_base, int32_t* wg,
+                    int32_t out_row, uint64_t ytab, uint64_t xtab, JpegDesc* d) {
+  std::memset(d, 0, sizeof(*d));
+  for (int c = 0; c < 3; ++c) {
+    const JpegComp& k = h.comp[c < h.ncomp ? c : 0];
+    d->coef_off[c] = coef_base + k.coef_off;
+    d->plane_off[c] = plane_base + k.coef_off;     // one byte per coefficient
+    d->bw[c] = k.bw; d->bh[c] = k.bh; d->dw[c] = k.dw; d->dh[c] = k.dh;
+    d->qoff[c] = qt_base + k.tq * 64;
+    d->wg_start[c] = *wg;
+    if (c < h.ncomp) *wg += (int32_t)(((uint64_t)k.bw * k.bh + kJpegBlocksPerWg - 1) / kJpegBlocksPerWg);
+  }
+  d->wg_start[3] = *wg;
+  d->ncomp = h.ncomp; d->hs = h.hmax; d->vs = h.vmax;
+  d->W = h.W; d->H = h.H; d->out_row = out_row;
+  d->ytab = ytab; d->xtab = xtab;
+}
+
+void jpeg_pixels_cpu(const JpegHeader& h, const int16_t* coef, uint8_t* rgb) {
+  std::vector<uint8_t> planes(h.ncoef);
+  for (int c = 0; c < h.ncomp; ++c) {
+    const JpegComp& k = h.comp[c];
+    const size_t stride = (size_t)k.bw * 8;
+    for (int by = 0; by < k.bh; ++by)
+      for (int bx = 0; bx < k.bw; ++bx)
+        idct_block(coef + k.coef_off + ((size_t)by * k.bw + bx) * 64, h.qt[k.tq],
+                   planes.data() + k.coef_off + (size_t)by * 8 * stride + (size_t)bx * 8, stride);
+  }
+  JpegDesc d;
+  int32_t wg = 0;
+  jpeg_fill_desc(h, 0, 0, 0, &wg, 0, 0, 0, &d);
+  for (int y = 0; y < h.H; ++y)
+    for (int x = 0; x < h.W; ++x) jpeg_pixel(d, planes.data(), y, x, rgb + ((size_t)y * h.W + x) * 3);
+}
+
+}  // namespace kdl

@@ -9,8 +9,9 @@ the reference lacks (§8.1): JSON errors (400 bad body, 502 fetch/backend errors
 mode that ships uint8 pixels to the ``serving_uint8`` signature (4x fewer bytes).
 
 Env: TF_SERVING_HOST, MODEL_NAME, SIGNATURE, INPUT_KEY, OUTPUT_KEY, LABELS,
-GATEWAY_MODE=compat|uint8|raw (raw: decoded pixels at their own size to ``serving_image``,
-resized on the model server's GPU -- no resize here), PREDICT_TIMEOUT, GATEWAY_CHANNELS (gRPC connections to open:
+GATEWAY_MODE=compat|uint8|raw|bytes (raw: decoded pixels at their own size to ``serving_image``,
+resized on the model server's GPU -- no resize here; bytes: the fetched file as it is to
+``serving_bytes``, decoded and resized on the model server -- no PIL here), PREDICT_TIMEOUT, GATEWAY_CHANNELS (gRPC connections to open:
 each gets its own subchannel, so a node running one model-server process per GPU on a
 shared SO_REUSEPORT port -- ``--procs`` -- sees the gateway's requests spread over all
 of them instead of pinned to whichever process accepted a single connection).
@@ -37,11 +38,11 @@ class GatewayConfig:
         self.server = env.get("TF_SERVING_HOST", "localhost:8500")
         self.model_name = env.get("MODEL_NAME", "clothing-model")
         self.mode = env.get("GATEWAY_MODE", "compat")
-        if self.mode not in ("compat", "uint8", "raw"):
-            raise ValueError(f"GATEWAY_MODE must be compat, uint8 or raw, got {self.mode!r}")
+        if self.mode not in ("compat", "uint8", "raw", "bytes"):
+            raise ValueError(f"GATEWAY_MODE must be compat, uint8, raw or bytes, got {self.mode!r}")
         self.signature = env.get("SIGNATURE", {"compat": "serving_default", "uint8": "serving_uint8",
-                                               "raw": "serving_image"}[self.mode])
-        self.input_key = env.get("INPUT_KEY", "input_8" if self.mode == "compat" else "images")
+                                               "raw": "serving_image", "bytes": "serving_bytes"}[self.mode])
+        self.input_key = env.get("INPUT_KEY", {"compat": "input_8", "bytes": "image_bytes"}.get(self.mode, "images"))
         self.output_key = env.get("OUTPUT_KEY", "dense_7")
         labels = env.get("LABELS", "")
         self.labels = [s for s in labels.split(",") if s] or list(DEFAULT_LABELS)
@@ -74,7 +75,7 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             return np.asarray(img, dtype=np.uint8)[None]
         return pp.image_to_tensor(img)
 
-    def run(X: np.ndarray):
+    def run(X):
         req = make_request(X, cfg.model_name, cfg.signature, cfg.input_key)
         return next_stub().Predict(req, timeout=cfg.timeout)
 
@@ -91,6 +92,8 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
 
     def load(url: str):
         try:
+            if cfg.mode == "bytes":        # a plain proxy: the model server decodes
+                return pp.fetch(url)
             return pp.load_image(pp.fetch(url))
         except (urllib.error.URLError, ValueError, OSError) as e:
             raise LookupError(f"could not fetch/decode image from {url!r}: {e}") from e
@@ -105,7 +108,7 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except LookupError as e:
             return fail(502, str(e))
         try:
-            pb_result = run(tensor_from_image(img))
+            pb_result = run([img] if cfg.mode == "bytes" else tensor_from_image(img))
         except grpc.RpcError as e:
             return grpc_fail(e)
         return jsonify(process_response(pb_result, cfg.labels, cfg.output_key))
@@ -117,10 +120,14 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         if not isinstance(urls, list) or not urls or not all(isinstance(u, str) for u in urls):
             return fail(400, 'request body must be JSON {"urls": ["<image url>", ...]}')
         try:
-            Xs = [tensor_from_image(load(u)) for u in urls]
+            Xs = [load(u) for u in urls]
+            if cfg.mode != "bytes":
+                Xs = [tensor_from_image(x) for x in Xs]
         except LookupError as e:
             return fail(502, str(e))
         try:
+            if cfg.mode == "bytes":        # all bodies in one request: the sizes may differ
+                return jsonify(process_batch_response(run(Xs), cfg.labels, cfg.output_key))
             if cfg.mode == "raw" and len({x.shape for x in Xs}) > 1:
                 # raw pixels of different sizes cannot share one dense tensor: one request each
                 return jsonify([process_response(run(x), cfg.labels, cfg.output_key) for x in Xs])

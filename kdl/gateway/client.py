@@ -31,11 +31,19 @@ class ModelStub:
             response_deserializer=P.GetModelStatusResponse.FromString)
 
 
-def np_to_protobuf(data: np.ndarray):
+def np_to_protobuf(data):
+    """A numeric array as ``tensor_content``; ``bytes`` or a list of them as a DT_STRING tensor
+    (scalar / shape [n], one ``string_val`` each), like ``tf.make_tensor_proto``."""
+    if isinstance(data, (bytes, bytearray)):
+        return P.TensorProto(dtype=P.DT_STRING, string_val=[bytes(data)])
+    if isinstance(data, (list, tuple)) and data and all(isinstance(b, (bytes, bytearray)) for b in data):
+        t = P.TensorProto(dtype=P.DT_STRING, string_val=[bytes(b) for b in data])
+        t.tensor_shape.dim.add(size=len(data))
+        return t
     return P.np_to_tensor_proto(data)
 
 
-def make_request(X: np.ndarray, model_name="clothing-model", signature="serving_default", input_key="input_8"):
+def make_request(X, model_name="clothing-model", signature="serving_default", input_key="input_8"):
     pb_request = P.PredictRequest()
     pb_request.model_spec.name = model_name
     pb_request.model_spec.signature_name = signature

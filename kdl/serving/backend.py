@@ -17,7 +17,8 @@ Backends:
 
 Families: ``xception`` (the reference's clothing model; SavedModel ingest,
 ``serving_default`` = f32 ``input_8`` like TF-Serving, plus ``serving_uint8`` and
-``serving_image`` = uint8 images of any size, resized on the GPU: resize.py),
+``serving_image`` = uint8 images of any size, resized on the GPU: resize.py, and
+``serving_bytes`` = encoded image files, decoded and resized on the GPU: jpeg.py),
 and ``resnet50`` / ``vit_b16`` / ``efficientnet_b7`` (BASELINE.json configs;
 torchvision-layout safetensors or synthetic weights, uint8 ``images`` input).
 """
@@ -39,6 +40,7 @@ from ..ops import _lib
 from . import protos as P
 from .config import ServerConfig
 from .metrics import BATCH_BUCKETS, METRICS
+from .jpeg import BYTES_SIGNATURE, BytesRunner, bytes_signature
 from .resize import IMAGE_SIGNATURE, ImageRunner
 
 log = logging.getLogger("kdl.serving")
@@ -90,6 +92,7 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
                                 output_shape=(-1, n)) for name in ("serving_default", NATIVE_SIGNATURE)}
     sigs[IMAGE_SIGNATURE] = SignatureInfo(IMAGE_SIGNATURE, NATIVE_INPUT_KEY, P.DT_UINT8, "logits",
                                           input_shape=(-1, -1, -1, 3), output_shape=(-1, n))
+    sigs[BYTES_SIGNATURE] = bytes_signature("logits", n)
     return ModelSource(params=params, head=None, signatures=sigs, origin=origin, family=family,
                        input_size=S, classes=n)
 
@@ -141,6 +144,8 @@ def load_version_dir(path: Path, synthetic: bool = False) -> ModelSource:
     # any-size uint8 images, resized on the GPU (serving/resize.py)
     sigs.setdefault(IMAGE_SIGNATURE, SignatureInfo(IMAGE_SIGNATURE, NATIVE_INPUT_KEY, P.DT_UINT8, out_key,
                                                    input_shape=(-1, -1, -1, 3), output_shape=(-1, head.classes)))
+    # encoded image files (DT_STRING), decoded and resized on the GPU (serving/jpeg.py)
+    sigs.setdefault(BYTES_SIGNATURE, bytes_signature(out_key, head.classes))
     return ModelSource(params=params, head=head, signatures=sigs, origin=origin, classes=head.classes)
 
 
@@ -308,6 +313,15 @@ class _Executor(threading.Thread):
         return handle
 
 
+# Executors set up on threads of their own, side by side. The device-wide synchronise that ends
+# one set-up fails in HIP ("operation not permitted when stream is capturing") when another
+# thread has a graph capture open meanwhile, and the failure invalidates that capture too (seen
+# with two executors per GPU: both failed to start). So the capture loop of a set-up and the
+# synchronise behind it run under this lock; engine construction, tuning and the native backend
+# stay parallel.
+_CAPTURE_LOCK = threading.Lock()
+
+
 class GPUExecutor(_Executor):
     def __init__(self, runner, device: int, engine_kwargs: dict, index: int = 0):
         super().__init__(runner, f"gpu{device}/{runner.sig.name}" + (f"#{index}" if index else ""))
@@ -401,15 +415,16 @@ class GPUExecutor(_Executor):
         self.h2d_done = [torch.cuda.Event() for _ in range(self.depth)]
         self.done = [torch.cuda.Event() for _ in range(self.depth)]
         self._rt = _lib.lib()
-        for slot in range(self.depth):        # warm-up + capture one hipGraph per (bucket, slot)
-            for bk in bs:
-                self.engine.program(bk, capture=cap, slot=slot)
-                self.engine.launch(bk, capture=cap, slot=slot)
-            for big in (self.lanes, self.pipe):
-                if big is not None:
-                    big.program(bs[-1], capture=cap, slot=slot)
-                    big.launch(bs[-1], capture=cap, slot=slot)
-        torch.cuda.synchronize(self.device)
+        with _CAPTURE_LOCK:
+            for slot in range(self.depth):    # warm-up + capture one hipGraph per (bucket, slot)
+                for bk in bs:
+                    self.engine.program(bk, capture=cap, slot=slot)
+                    self.engine.launch(bk, capture=cap, slot=slot)
+                for big in (self.lanes, self.pipe):
+                    if big is not None:
+                        big.program(bs[-1], capture=cap, slot=slot)
+                        big.launch(bs[-1], capture=cap, slot=slot)
+            torch.cuda.synchronize(self.device)
         if want_native:
             self._build_native(S * S * 3 * (1 if in_kind == "u8" else 4), src.classes)
 
@@ -718,6 +733,8 @@ class Servable:
                                        "in signature def")
                 if sig_name == IMAGE_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
                     r = ImageRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices)
+                elif sig_name == BYTES_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices)
                 else:
                     r = SignatureRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 self.runners[sig_name] = r
@@ -734,7 +751,9 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        used = [r for r in runners if r.batcher.stats()["submitted"] > 0]
+        # serving_image / serving_bytes feed the serving_uint8 runner's batcher and have none of
+        # their own: that runner is in the list already and speaks for them
+        used = [r for r in runners if hasattr(r, "batcher") and r.batcher.stats()["submitted"] > 0]
         return not used or any(r.healthy() for r in used)
 
     def close(self):

@@ -43,6 +43,8 @@ def _abort(context, err: ServingError):
 def _payload(raw: bytes, td: dict, sig) -> tuple[object, int]:
     """Return (buffer of n images in the signature's dtype, n) from a parsed input."""
     dims = list(td["dims"])
+    if sig.input_dtype == P.DT_STRING:      # serving_bytes: one encoded image file per element
+        return _bytes_payload(raw, td, sig, dims)
     IMG = sig.input_shape[1]
     if IMG == -1:           # serving_image: uint8 [n, H, W, 3] of any size
         return _image_payload(raw, td, sig, dims)
@@ -101,6 +103,24 @@ def _image_payload(raw: bytes, td: dict, sig, dims: list) -> tuple[np.ndarray, i
             raise ServingError("INVALID_ARGUMENT", f"input '{sig.input_key}' has {arr.size} values, but its "
                                f"shape {dims} needs {need}")
     return arr.reshape(n, H, W, 3), n
+
+
+def _bytes_payload(raw: bytes, td: dict, sig, dims: list) -> tuple[list, int]:
+    """DT_STRING [n] (or a scalar): the elements of ``string_val``, read through the Python
+    protobuf classes (these requests are ~50 KB; the native codec does not decode strings)."""
+    if td["dtype"] != P.DT_STRING:
+        raise ServingError("INVALID_ARGUMENT",
+                           f"Expects arg[0] to be {P.DTYPE_NAMES.get(sig.input_dtype)} but "
+                           f"{P.DTYPE_NAMES.get(td['dtype'], td['dtype'])} is provided")
+    try:
+        vals = list(P.PredictRequest.FromString(raw).inputs[td["key"]].string_val)
+    except (ValueError, KeyError, TypeError) as e:
+        raise ServingError("INVALID_ARGUMENT", f"cannot decode input '{sig.input_key}': {e}") from e
+    n = len(vals)
+    if len(dims) > 1 or n < 1 or (dims and dims[0] != n):
+        raise ServingError("INVALID_ARGUMENT", f"input '{sig.input_key}' must have shape [-1] with one encoded "
+                           f"image per element, got shape {dims} and {n} string values")
+    return vals, n
 
 
 def route_exact_u8(s, runner, buf, n: int):

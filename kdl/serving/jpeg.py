@@ -1,0 +1,278 @@
+"""``serving_bytes``: encoded image files in, decoded on the model server.
+
+TF-Serving models commonly take the image file itself as a ``DT_STRING`` tensor
+(``{"b64": ...}`` over REST); with it the gateway is a plain proxy (``GATEWAY_MODE=bytes``):
+about 50 KB per image cross the wire instead of 640 KB of pixels, and no gateway core decodes.
+
+Baseline JPEG -- what the web serves -- is split at its serial part. The host Huffman-decodes
+each file into quantised coefficient planes (``kdl._rt.jpeg_parse``, csrc/runtime/jpeg.cpp,
+GIL released, straight into pinned staging); everything per pixel is two HIP launches per
+request (csrc/kernels/jpeg.hip): ``jpeg_idct_u8`` for all blocks of all images, then
+``jpeg_sample_rgb_u8``, which reads only the source pixels that PIL's NEAREST resize would keep
+(the tables of ``resize_nearest_u8``), upsamples the chroma at those positions, converts to RGB
+and writes the image's row of the model batch. The full-size RGB image never exists and, with
+native executors, the batch never returns to the host. The arithmetic is libjpeg-turbo's
+default decode, so each row equals ``gateway.preprocess.to_uint8(load_image(data), (S, S))``
+bit for bit and the logits equal ``serving_image``'s for the PIL-decoded pixels.
+
+Files the decoder does not cover (progressive or arithmetic JPEG, CMYK, PNG, ...) are decoded by
+PIL on the host and resized by ``resize_nearest_u8`` into the same batch. Without a GPU the same
+arithmetic runs on the CPU (``jpeg_pixels_cpu``) followed by the numpy gather.
+"""
+from __future__ import annotations
+
+import concurrent.futures as cf
+import io
+import os
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+from ..gateway.preprocess import load_image
+from ..ops import _lib
+from . import protos as P
+from .metrics import METRICS
+from .resize import MAX_PIXELS, Resizer
+
+BYTES_SIGNATURE = "serving_bytes"
+BYTES_INPUT_KEY = "image_bytes"
+
+THREADS = int(os.environ.get("KDL_JPEG_THREADS", "4"))
+_POOL: cf.ThreadPoolExecutor | None = None
+
+
+def _pool() -> cf.ThreadPoolExecutor:
+    """Entropy-decode threads shared by all requests: the images of one request are spread over
+    them. A request of one image, and every request when KDL_JPEG_THREADS <= 1, decodes on its own
+    handler thread (the GIL is released either way, so handlers decode side by side)."""
+    global _POOL
+    if _POOL is None:
+        _POOL = cf.ThreadPoolExecutor(max_workers=THREADS, thread_name_prefix="jpeg")
+    return _POOL
+
+
+def _align(n: int, a: int) -> int:
+    return (n + a - 1) // a * a
+
+
+def _bad(msg: str):
+    from .backend import ServingError
+    return ServingError("INVALID_ARGUMENT", msg)
+
+
+class CallLayout:
+    """Where one GPU decode call keeps its inputs in the staging buffer (pinned on the host, mirrored
+    on the device): [descriptors | 4 quantisation tables per image | coefficient planes, each
+    128-byte aligned]. ``ncoefs``: the coefficient count of every image that may join the call."""
+
+    def __init__(self, ncoefs: list[int]):
+        self.desc_bytes = _lib.rt().JPEG_DESC_BYTES
+        n = len(ncoefs)
+        self.off_qt = _align(n * self.desc_bytes, 256)
+        self.off_coef = _align(self.off_qt + n * 512, 256)
+        self.coef_at, self.ncoef = [], 0            # int16 units from the coefficient base
+        for k in ncoefs:
+            self.coef_at.append(self.ncoef)
+            self.ncoef += _align(k, 64)
+        self.nbytes = self.off_coef + 2 * self.ncoef
+        self.n_desc = self.n_wg = 0
+
+    def coef(self, hin: np.ndarray, k: int, ncoef: int) -> np.ndarray:
+        """The int16 coefficient buffer of slot ``k`` inside the uint8 staging array ``hin``."""
+        o = self.off_coef + 2 * self.coef_at[k]
+        return hin[o:o + 2 * ncoef].view(np.int16)
+
+    def add(self, hin: np.ndarray, k: int, header, out_row: int, ys: torch.Tensor, xs: torch.Tensor) -> None:
+        """Stage the descriptor and tables of the parsed image in slot ``k``; it goes to ``out_row``
+        through the device tables ``ys`` / ``xs`` (PIL-NEAREST source rows / columns)."""
+        j, D = self.n_desc, self.desc_bytes
+        desc, self.n_wg = _lib.rt().jpeg_desc(header, self.coef_at[k], self.coef_at[k], j * 256, self.n_wg, out_row,
+                                              _lib.ptr(ys), _lib.ptr(xs))
+        hin[j * D:(j + 1) * D] = np.frombuffer(desc, np.uint8)
+        hin[self.off_qt + j * 512: self.off_qt + (j + 1) * 512].view(np.uint16)[:] = header.qt.reshape(-1)
+        self.n_desc = j + 1
+
+    def args(self, h_in: int, d_in: int, planes: int, plane_cap: int, out: int, out_rows: int, OH: int, OW: int) -> dict:
+        """The argument dict of kdl._C.jpeg_idct_u8 / jpeg_sample_rgb_u8 (addresses as ints)."""
+        return dict(desc=d_in, h_desc=h_in, qt=d_in + self.off_qt, coef=d_in + self.off_coef, planes=planes, out=out,
+                    coef_cap=self.ncoef, plane_cap=plane_cap, qt_cap=self.n_desc * 256, n=self.n_desc, n_wg=self.n_wg,
+                    out_rows=out_rows, OH=OH, OW=OW)
+
+
+class BytesRunner:
+    """The ``serving_bytes`` signature: decode + resize (GPU when the servable has one), then the
+    ``serving_uint8`` runner's batcher and executors."""
+
+    def __init__(self, sig, inner, devices: list[int]):
+        self.sig, self.inner = sig, inner
+        self.source = inner.source
+        self.S = inner.source.input_size
+        self.resizer = Resizer(self.S, devices or None)    # contexts, table cache, PIL-fallback resize
+        self.gpu = bool(devices)
+        self.device_path = self.gpu and inner.takes_device_items()
+
+    # ------------------------------------------------------------------ per image
+    def _probe(self, images) -> list:
+        """[file bytes, JPEG header | None (= a file for PIL)] per image, after the request's pixel
+        limit: nothing is allocated from a header before the sum of W x H has passed it."""
+        rt = _lib.rt()
+        plan, total = [], 0
+        for i, data in enumerate(images):
+            if not isinstance(data, (bytes, bytearray, memoryview)):
+                raise _bad(f"image {i}: expected the bytes of an image file")
+            data = bytes(data)
+            st, hd = rt.jpeg_probe(data, 1 << 62)
+            if st == rt.JPEG_MALFORMED:
+                raise _bad(f"image {i}: malformed JPEG ({hd.why})")
+            if st == rt.JPEG_OK:
+                plan.append([data, hd])
+                total += hd.W * hd.H
+            else:
+                try:
+                    w, h = Image.open(io.BytesIO(data)).size      # lazy: the header only
+                except Exception as e:  # noqa: BLE001 - PIL raises many types
+                    raise _bad(f"image {i}: not a decodable image file ({hd.why}; PIL: {e})") from e
+                plan.append([data, None])
+                total += w * h
+            if total > MAX_PIXELS:
+                raise _bad(f"the images of the request exceed the {MAX_PIXELS}-pixel request limit")
+        return plan
+
+    @staticmethod
+    def _pil(i: int, data: bytes) -> np.ndarray:
+        try:
+            px = np.array(load_image(data), dtype=np.uint8)      # a writable copy (torch.from_numpy)
+        except Exception as e:  # noqa: BLE001
+            raise _bad(f"image {i}: not a decodable image file (PIL: {e})") from e
+        METRICS.inc("kdl_jpeg_decoded_total", path="pil")
+        return px
+
+    def _parse_all(self, plan, buffers) -> None:
+        """Entropy-decode every JPEG of ``plan`` into its int16 buffer; a file that turns out to be
+        outside the decoder after its frame header (e.g. several scans) falls back to PIL."""
+        rt = _lib.rt()
+        jobs = [(i, p) for i, p in enumerate(plan) if p[1] is not None]
+        t0 = time.perf_counter()
+
+        def one(job):
+            i, p = job
+            return rt.jpeg_parse(p[0], buffers[i], MAX_PIXELS)
+        results = [one(j) for j in jobs] if len(jobs) < 2 or THREADS <= 1 else list(_pool().map(one, jobs))
+        for (i, p), (st, hd) in zip(jobs, results):
+            if st == rt.JPEG_MALFORMED:
+                raise _bad(f"image {i}: malformed JPEG ({hd.why})")
+            p[1] = hd if st == rt.JPEG_OK else None
+        if jobs:
+            METRICS.observe("kdl_stage_ms", (time.perf_counter() - t0) * 1e3, stage="jpeg_entropy")
+
+    # ------------------------------------------------------------------ CPU
+    def _decode_cpu(self, plan) -> np.ndarray:
+        rt = _lib.rt()
+        S = self.S
+        bufs = {i: np.empty(p[1].ncoef, np.int16) for i, p in enumerate(plan) if p[1] is not None}
+        self._parse_all(plan, bufs)
+        out = np.empty((len(plan), S, S, 3), np.uint8)
+        for i, (data, hd) in enumerate(plan):
+            if hd is not None:
+                px = rt.jpeg_pixels_cpu(hd, bufs[i])
+                METRICS.inc("kdl_jpeg_decoded_total", path="cpu")
+            else:
+                px = self._pil(i, data)
+            ys, xs = self.resizer._tables(px.shape[0], px.shape[1], None)
+            out[i] = px[ys][:, xs]
+        return out
+
+    # ------------------------------------------------------------------ GPU
+    def _decode_on(self, c, plan) -> int:
+        """Decode + resize the request into ``c.d_out`` ([n, S, S, 3]) on the context's stream;
+        returns the output's element count. The caller synchronises the stream."""
+        C = _lib.lib()
+        S, n = self.S, len(plan)
+        slot = {i: k for k, i in enumerate(i for i, p in enumerate(plan) if p[1] is not None)}
+        lay = CallLayout([plan[i][1].ncoef for i in slot])
+        n_in, n_out = lay.nbytes, n * S * S * 3
+        c.grow(max(n_in, 1), n_out)
+        c.grow_planes(max(lay.ncoef, 1))                # sample planes: one byte per coefficient
+        hin = c.h_in.numpy()
+        self._parse_all(plan, {i: lay.coef(hin, k, plan[i][1].ncoef) for i, k in slot.items()})
+        # every host step that can fail comes before the first launch: the stream never runs a
+        # request that was rejected half way
+        pil = {i: self._pil(i, p[0]) for i, p in enumerate(plan) if p[1] is None}
+        keep = []                                   # tables / fallback pixels in use by the stream
+        for i, k in slot.items():
+            hd = plan[i][1]
+            if hd is None:                          # fell back to PIL after its frame header
+                continue
+            ys, xs = self.resizer._tables(hd.H, hd.W, c.dev)
+            keep += [ys, xs]
+            lay.add(hin, k, hd, i, ys, xs)
+        stream = int(c.stream.cuda_stream)
+        with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
+            if lay.n_desc:
+                c.d_in[:n_in].copy_(c.h_in[:n_in], non_blocking=True)
+                args = lay.args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_planes), c.cap_planes,
+                                _lib.ptr(c.d_out), n, S, S)
+                C.jpeg_idct_u8(args, stream)
+                C.jpeg_sample_rgb_u8(args, stream)
+                METRICS.inc("kdl_jpeg_decoded_total", lay.n_desc, path="gpu")
+            for i, px in pil.items():               # what the decoder does not cover: PIL + the resize kernel
+                ys, xs = self.resizer._tables(px.shape[0], px.shape[1], c.dev)
+                src = torch.from_numpy(np.ascontiguousarray(px)).to(c.dev)
+                keep += [ys, xs, src]
+                C.resize_nearest_u8(dict(src=_lib.ptr(src), dst=_lib.ptr(c.d_out) + i * S * S * 3, ytab=_lib.ptr(ys),
+                                         xtab=_lib.ptr(xs), SH=px.shape[0], SW=px.shape[1], OH=S, OW=S, n=1), stream)
+        c.keep = keep
+        return n_out
+
+    def decode(self, images) -> np.ndarray:
+        """[n, S, S, 3] uint8 model inputs of the encoded ``images`` (host array)."""
+        plan = self._probe(images)
+        if not self.gpu:
+            return self._decode_cpu(plan)
+        c = self.resizer._free.get()
+        try:
+            n_out = self._decode_on(c, plan)
+            with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
+                c.h_out[:n_out].copy_(c.d_out[:n_out], non_blocking=True)
+            c.stream.synchronize()
+            return c.h_out[:n_out].numpy().reshape(len(plan), self.S, self.S, 3).copy()
+        finally:
+            self._release(c)
+
+    # ------------------------------------------------------------------ runner interface
+    def predict(self, images, n: int, deadline_us: int) -> np.ndarray:
+        if len(images) != n or n < 1:
+            raise _bad(f"expected {n} encoded images, got {len(images)}")
+        if not self.device_path:
+            return self.inner.predict(self.decode(images), n, deadline_us)
+        plan = self._probe(images)
+        c = self.resizer._free.get()
+        try:                           # decoded straight into device memory: no host round trip
+            self._decode_on(c, plan)
+            c.stream.synchronize()
+            return self.inner.predict_device(_lib.ptr(c.d_out), n, deadline_us)
+        finally:
+            self._release(c)
+
+    def _release(self, c) -> None:
+        """Hand the context back idle: the next request rewrites its pinned staging, which an
+        unfinished host-to-device copy of this one must not still be reading."""
+        try:
+            c.stream.synchronize()
+        finally:
+            c.keep = None
+            self.resizer._free.put(c)
+
+    def healthy(self) -> bool:
+        return self.inner.healthy()
+
+    def close(self) -> None:       # the inner runner belongs to the servable
+        pass
+
+
+def bytes_signature(output_key: str, classes: int):
+    from .backend import SignatureInfo
+    return SignatureInfo(BYTES_SIGNATURE, BYTES_INPUT_KEY, P.DT_STRING, output_key, input_shape=(-1,),
+                         output_shape=(-1, classes))

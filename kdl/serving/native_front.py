@@ -126,8 +126,8 @@ class NativeFront:
             gen = self._gen
         runner = s.runner(sig_name)
         sig = runner.sig
-        if sig.input_shape[1] <= 0 or not hasattr(runner, "batcher") or not runner.healthy():
-            return                                             # serving_image: resize path, slow
+        if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or not runner.healthy():
+            return                                             # serving_image / serving_bytes: slow path
         u8 = None
         if self.f32_exact_u8 and sig.input_dtype == P.DT_FLOAT and NATIVE_SIGNATURE in s.signatures:
             u8 = s.runner(NATIVE_SIGNATURE).batcher

@@ -45,6 +45,16 @@ class _Ctx:
         self.stream = torch.cuda.Stream(device=dev)
         self.cap_in = self.cap_out = 0
         self._retired: list[torch.Tensor] = []
+        # serving_bytes (jpeg.py): sample-plane scratch of the JPEG kernels, and what the stream
+        # still reads (resize tables, fallback pixels) until the request has synchronised
+        self.cap_planes = 0
+        self.d_planes: torch.Tensor | None = None
+        self.keep: list | None = None
+
+    def grow_planes(self, n: int) -> None:
+        if n > self.cap_planes:
+            self.cap_planes = max(n, 2 * self.cap_planes)
+            self.d_planes = torch.empty(self.cap_planes, dtype=torch.uint8, device=self.dev)
 
     def grow(self, n_in: int, n_out: int) -> None:
         if n_in > self.cap_in:

@@ -6,10 +6,12 @@ Routes (TF-Serving REST semantics):
   POST /v1/models/<name>[/versions/<v>|/labels/<l>]:predict
        {"signature_name"?, "instances": [...]}  -> {"predictions": [...]}
        {"signature_name"?, "inputs": ...}       -> {"outputs": ...}
+       (serving_bytes: every value is {"b64": "<base64 of the image file>"})
   GET  /monitoring/prometheus/metrics, /healthz (liveness), /readyz (readiness)
 """
 from __future__ import annotations
 
+import base64
 import json
 import time
 import re
@@ -91,6 +93,8 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 runner = s.runner(body.get("signature_name") or "serving_default")
                 sig = runner.sig
                 dt = np.uint8 if sig.input_dtype == P.DT_UINT8 else np.float32
+                if sig.input_dtype == P.DT_STRING:      # serving_bytes: {"b64": ...} per encoded image
+                    return self._predict_bytes(body, runner, t0)
                 if "instances" in body:
                     inst = body["instances"]
                     if inst and isinstance(inst[0], dict):
@@ -131,6 +135,41 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 return self._err(e)
             except (ValueError, KeyError, TypeError) as e:
                 return self._err(ServingError("INVALID_ARGUMENT", str(e)))
+
+        def _predict_bytes(self, body, runner, t0):
+            sig = runner.sig
+            rows = "instances" in body
+            if not rows and "inputs" not in body:
+                raise ServingError("INVALID_ARGUMENT", "request must contain 'instances' or 'inputs'")
+            items = body["instances"] if rows else body["inputs"]
+            if isinstance(items, dict) and "b64" not in items:
+                items = items[sig.input_key]
+            if isinstance(items, dict):                 # a scalar
+                items = [items]
+            images = []
+            for it in items:
+                if isinstance(it, dict) and "b64" not in it:
+                    it = it[sig.input_key]
+                if not isinstance(it, dict) or not isinstance(it.get("b64"), str):
+                    raise ServingError("INVALID_ARGUMENT", f"input '{sig.input_key}' takes {{\"b64\": ...}} values")
+                try:
+                    images.append(base64.b64decode(it["b64"], validate=True))
+                except ValueError as e:
+                    raise ServingError("INVALID_ARGUMENT", f"input '{sig.input_key}': bad base64: {e}") from e
+            if not images:
+                raise ServingError("INVALID_ARGUMENT", f"input '{sig.input_key}' is empty")
+            dl = self.headers.get("X-Deadline-Ms")
+            deadline = int(_lib.rt().now_us() + float(dl) * 1e3) if dl else 0
+            t1 = time.perf_counter()
+            out = runner.predict(images, len(images), deadline).tolist()
+            t2 = time.perf_counter()
+            r = self._send(200, {"predictions": out} if rows else {"outputs": out})
+            METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
+            METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")
+            METRICS.observe("kdl_stage_ms", (time.perf_counter() - t2) * 1e3, stage="respond")
+            METRICS.inc("kdl_requests_total", code="OK", method="RestPredict")
+            METRICS.observe("kdl_request_latency_ms", (time.perf_counter() - t0) * 1e3, method="RestPredict")
+            return r
 
     return H
 

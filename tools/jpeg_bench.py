@@ -1,0 +1,122 @@
+#!/usr/bin/env python
+"""serving_bytes micro-benchmarks (profiles/jpeg_serving.txt).
+
+  python tools/jpeg_bench.py --size 534x400                  # host: jpeg_parse vs Pillow, one core
+  python tools/jpeg_bench.py --size 534x400 --kernels --images 32   # MI355X: the two HIP kernels
+
+The image is tests/data/pants.png scaled to --size (HxW) and encoded as a quality-90 4:2:0 JPEG.
+Host: median microseconds per image of the entropy decode (kdl._rt.jpeg_parse into a reused
+buffer) against Pillow's full decode (Image.open().convert("RGB")) on the same core. --kernels:
+--images copies decoded in one call, device-event times of jpeg_idct_u8 and jpeg_sample_rgb_u8
+(-> 299x299) and the bytes each has to move over that time; needs a GPU, no fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+import numpy as np  # noqa: E402
+from PIL import Image  # noqa: E402
+
+
+def make_file(H: int, W: int) -> bytes:
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    im = Image.open(os.path.join(root, "tests", "data", "pants.png")).convert("RGB").resize((W, H), Image.BILINEAR)
+    buf = io.BytesIO()
+    im.save(buf, "JPEG", quality=90, subsampling=2)
+    return buf.getvalue()
+
+
+def _median_us(fn, iters: int) -> float:
+    fn()
+    ts = []
+    for _ in range(iters):
+        t = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t)
+    return statistics.median(ts) * 1e6
+
+
+def host(data: bytes, iters: int) -> dict:
+    from kdl.ops import _lib
+    rt = _lib.rt()
+    st, hd = rt.jpeg_probe(data)
+    assert st == rt.JPEG_OK, hd.why
+    coef = np.empty(hd.ncoef, np.int16)
+    parse = _median_us(lambda: rt.jpeg_parse(data, coef), iters)
+    pil = _median_us(lambda: Image.open(io.BytesIO(data)).convert("RGB"), iters)
+    return {"file_bytes": len(data), "jpeg_parse_us": round(parse, 1), "pillow_decode_us": round(pil, 1),
+            "parse_over_pillow": round(parse / pil, 3)}
+
+
+def kernels(data: bytes, n: int, iters: int, S: int = 299) -> dict:
+    import torch
+
+    from kdl.gateway.preprocess import nearest_indices
+    from kdl.ops import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("--kernels needs a GPU")
+    from kdl.serving.jpeg import CallLayout
+    rt, C = _lib.rt(), _lib.lib()
+    st, hd = rt.jpeg_probe(data)
+    assert st == rt.JPEG_OK, hd.why
+    lay = CallLayout([hd.ncoef] * n)
+    hin = np.zeros(lay.nbytes, np.uint8)
+    ys = torch.from_numpy(nearest_indices(hd.H, S)).cuda()
+    xs = torch.from_numpy(nearest_indices(hd.W, S)).cuda()
+    for k in range(n):
+        st, h = rt.jpeg_parse(data, lay.coef(hin, k, hd.ncoef))
+        assert st == rt.JPEG_OK
+        lay.add(hin, k, h, k, ys, xs)
+    d_in = torch.from_numpy(hin).cuda()
+    planes = torch.empty(lay.ncoef, dtype=torch.uint8, device="cuda")
+    out = torch.empty((n, S, S, 3), dtype=torch.uint8, device="cuda")
+    args = lay.args(hin.ctypes.data, d_in.data_ptr(), planes.data_ptr(), lay.ncoef, out.data_ptr(), n, S, S)
+    s = torch.cuda.current_stream().cuda_stream
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(iters)]
+    for _ in range(10):
+        C.jpeg_idct_u8(args, s)
+        C.jpeg_sample_rgb_u8(args, s)
+    torch.cuda.synchronize()
+    for e in ev:
+        e[0].record()
+        C.jpeg_idct_u8(args, s)
+        e[1].record()
+        C.jpeg_sample_rgb_u8(args, s)
+        e[2].record()
+    torch.cuda.synchronize()
+    idct = statistics.median(e[0].elapsed_time(e[1]) for e in ev) * 1e3
+    samp = statistics.median(e[1].elapsed_time(e[2]) for e in ev) * 1e3
+    # bytes the algorithm has to move: coefficients in (2 B) + samples out (1 B); then at most all
+    # samples in + the resized RGB out
+    b_idct, b_samp = 3 * hd.ncoef * n, hd.ncoef * n + n * S * S * 3
+    return {"images": n, "blocks": hd.ncoef // 64 * n, "idct_us": round(idct, 1), "sample_rgb_us": round(samp, 1),
+            "idct_GBps": round(b_idct / idct / 1e3, 1), "sample_rgb_GBps_upper": round(b_samp / samp / 1e3, 1),
+            "both_us_per_image": round((idct + samp) / n, 2)}
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="534x400", help="HxW")
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--kernels", action="store_true")
+    a = ap.parse_args(argv)
+    H, W = map(int, a.size.split("x"))
+    data = make_file(H, W)
+    res = {"size": a.size, **host(data, a.iters)}
+    if a.kernels:
+        res["kernels"] = kernels(data, a.images, a.iters)
+    print(json.dumps(res), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -6,6 +6,8 @@ server on a synthetic model unless --target is given.
 
   python tools/serve_bench.py --clients 64 --images 1 --seconds 20 --signature serving_uint8
   python tools/serve_bench.py --client native --conns 8 --clients 64 --device null   # front-end ceiling
+  python tools/serve_bench.py --payload jpeg --signature serving_bytes    # encoded files, decoded on the server
+  python tools/serve_bench.py --payload jpeg --signature serving_image    # the same files' pixels (PIL-decoded here)
 
 --client native drives the server with the C++ load generator (kdl._rt.grpc_load: HTTP/2
 connections each keeping clients/conns calls in flight); Python clients top out near 1-2k
@@ -52,6 +54,33 @@ def _client_proc(conn, threads: int, req: bytes, seconds: float, warm_s: float) 
     for t in ths:
         t.join()
     conn.send(lat)
+
+
+def _build_request(a) -> bytes:
+    """The serialized PredictRequest every client sends. --payload jpeg: tests/data/pants.png scaled
+    to --image-size and encoded as a quality-90 4:2:0 JPEG -- the file itself for serving_bytes,
+    its PIL-decoded pixels for serving_image, so the two signatures are compared on one image."""
+    from kdl.gateway.client import make_request
+    if a.payload == "jpeg":
+        import io
+
+        from PIL import Image
+        H, W = map(int, a.image_size.split("x"))
+        root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+        im = Image.open(os.path.join(root, "tests", "data", "pants.png")).convert("RGB").resize((W, H), Image.BILINEAR)
+        buf = io.BytesIO()
+        im.save(buf, "JPEG", quality=90, subsampling=2)
+        data = buf.getvalue()
+        if a.signature == "serving_bytes":
+            return make_request([data] * a.images, signature=a.signature, input_key="image_bytes").SerializeToString()
+        px = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), np.uint8)
+        return make_request(np.stack([px] * a.images), signature=a.signature, input_key="images").SerializeToString()
+    rng = np.random.default_rng(0)
+    H, W = (299, 299) if a.signature != "serving_image" else map(int, a.image_size.split("x"))
+    u8 = rng.integers(0, 256, (a.images, H, W, 3), dtype=np.uint8)
+    if a.signature != "serving_default":
+        return make_request(u8, signature=a.signature, input_key="images").SerializeToString()
+    return make_request(u8.astype(np.float32) / 127.5 - 1).SerializeToString()
 
 
 def _launch_procs(a):
@@ -101,7 +130,10 @@ def main(argv=None) -> int:
     ap.add_argument("--clients", type=int, default=32)
     ap.add_argument("--images", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=15)
-    ap.add_argument("--signature", default="serving_uint8", choices=["serving_uint8", "serving_default", "serving_image"])
+    ap.add_argument("--signature", default="serving_uint8", choices=["serving_uint8", "serving_default", "serving_image", "serving_bytes"])
+    ap.add_argument("--payload", choices=["random", "jpeg"], default="random",
+                    help="jpeg: a quality-90 4:2:0 JPEG of tests/data/pants.png at --image-size -- the file for "
+                         "serving_bytes, its decoded pixels for serving_image (random: seeded uniform pixels)")
     ap.add_argument("--image-size", default="534x400",
                     help="serving_image: HxW of the raw uint8 images the clients send (resized on the server)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -135,17 +167,12 @@ def main(argv=None) -> int:
                     help="run the clients in this many spawned processes (0: threads of the server "
                          "process, which then share its GIL with the server's handlers)")
     a = ap.parse_args(argv)
-    rng = np.random.default_rng(0)
-    H, W = (299, 299) if a.signature != "serving_image" else map(int, a.image_size.split("x"))
-    u8 = rng.integers(0, 256, (a.images, H, W, 3), dtype=np.uint8)
+    if (a.signature == "serving_bytes") != (a.payload == "jpeg") and a.signature != "serving_image":
+        ap.error("--signature serving_bytes goes with --payload jpeg (which serving_image also takes)")
     procs = []
     if a.client_procs and a.client == "python":
         import multiprocessing as mp
-        from kdl.gateway.client import make_request as _mk
-        if a.signature != "serving_default":
-            req0 = _mk(u8, signature=a.signature, input_key="images").SerializeToString()
-        else:
-            req0 = _mk(u8.astype(np.float32) / 127.5 - 1).SerializeToString()
+        req0 = _build_request(a)
         ctx = mp.get_context("spawn")         # before any GPU initialisation in this process
         per = [a.clients // a.client_procs + (1 if i < a.clients % a.client_procs else 0)
                for i in range(a.client_procs)]
@@ -155,7 +182,6 @@ def main(argv=None) -> int:
                              daemon=True)
             pr.start()
             procs.append((pr, parent))
-    from kdl.gateway.client import PredictionStub, make_request
     srv = None
     launcher = None
     target = a.target
@@ -180,10 +206,7 @@ def main(argv=None) -> int:
         if a.signature != "serving_default":
             srv.manager.get("clothing-model").runner(a.signature)
         target = f"127.0.0.1:{srv.grpc_port}"
-    if a.signature != "serving_default":
-        req = make_request(u8, signature=a.signature, input_key="images").SerializeToString()
-    else:
-        req = make_request(u8.astype(np.float32) / 127.5 - 1).SerializeToString()
+    req = _build_request(a)
     lat, lock = [], threading.Lock()
     native_load = None
     if a.client == "native":
@@ -236,10 +259,19 @@ def main(argv=None) -> int:
             ns = srv.native.stats()
             res["native_front"] = {k: ns[k] for k in ("fast_ok", "fast_err", "slow", "exact_u8")}
         run = srv.manager.get("clothing-model").runner(a.signature)
-        if a.signature == "serving_image":
+        if a.signature in ("serving_image", "serving_bytes"):
             res["image_size"] = a.image_size
+            res["payload"] = a.payload
+            res["request_bytes"] = len(req)
             res["resize_into_device_slot"] = bool(getattr(run, "device_path", False))
-        run = getattr(run, "inner", run)      # serving_image: the serving_uint8 runner behind the resize
+        if a.signature == "serving_bytes":
+            from kdl.serving.metrics import METRICS
+            snap = METRICS.snapshot()
+            res["jpeg_decoded"] = {k.split("=")[1].rstrip("}"): v for k, v in snap["counters"].items()
+                                   if k.startswith("kdl_jpeg_decoded_total")}
+            res["jpeg_entropy_ms"] = snap["histograms"].get("kdl_stage_ms{stage=jpeg_entropy}")
+            res["jpeg_threads"] = int(os.environ.get("KDL_JPEG_THREADS", "4"))
+        run = getattr(run, "inner", run)      # serving_image / serving_bytes: the serving_uint8 runner behind
         st = run.batcher.stats()
         res["mean_batch"] = round(st["items"] / max(1, st["batches"]), 2)
         if a.stages:
