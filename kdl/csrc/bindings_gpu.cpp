@@ -210,6 +210,21 @@ JpegArgs jpeg_args(const py::dict& d) {
   return a;
 }
 
+uint64_t U64(const py::dict& d, const char* k) {
+  if (!d.contains(k) || d[k].is_none()) return 0;
+  return d[k].cast<uint64_t>();
+}
+ResampleArgs resample_args(const py::dict& d) {
+  ResampleArgs a{};
+  a.desc = P<const ResampleDesc>(d, "desc"); a.h_desc = P<const ResampleDesc>(d, "h_desc");
+  a.jdesc = P<const JpegDesc>(d, "jdesc"); a.h_jdesc = P<const JpegDesc>(d, "h_jdesc");
+  a.planes = P<const uint8_t>(d, "planes"); a.tmp = P<uint8_t>(d, "tmp"); a.out = P<uint8_t>(d, "out");
+  a.plane_cap = U64(d, "plane_cap"); a.tmp_cap = U64(d, "tmp_cap");
+  a.n_jdesc = I(d, "n_jdesc"); a.n = I(d, "n"); a.out_rows = I(d, "out_rows");
+  a.OH = I(d, "OH"); a.OW = I(d, "OW");
+  return a;
+}
+
 DwArgs dw_args(const py::dict& d) {
   DwArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.w = P<const float>(d, "w"); a.y = P<uint16_t>(d, "y");
@@ -355,6 +370,18 @@ PYBIND11_MODULE(_C, m) {
     const auto a = jpeg_args(d);
     py::gil_scoped_release nogil;
     chk(jpeg_sample_rgb_u8(a, S(s)), "jpeg_sample_rgb_u8");
+  });
+  // Pillow's filtered resize (kernels/resample.hip): d = the ResampleArgs fields; h_desc, h_jdesc
+  // and the h_xb / h_yb of every descriptor are HOST addresses. kind: 0 raw pixels, 1 JPEG planes
+  m.def("resample_h_u8", [](py::dict d, int kind, uintptr_t s) {
+    const auto a = resample_args(d);
+    py::gil_scoped_release nogil;
+    chk(resample_h_u8(a, kind, S(s)), "resample_h_u8");
+  });
+  m.def("resample_v_u8", [](py::dict d, uintptr_t s) {
+    const auto a = resample_args(d);
+    py::gil_scoped_release nogil;
+    chk(resample_v_u8(a, S(s)), "resample_v_u8");
   });
   m.def("u8_to_bf16_norm", [](uintptr_t x, uintptr_t y, long npix, int ldy, uintptr_t s) {
     py::gil_scoped_release nogil;

@@ -20,6 +20,7 @@
 #include "runtime/grpc_load.h"
 #include "runtime/h2.h"
 #include "runtime/jpeg.h"
+#include "runtime/resample.h"
 #include "runtime/sstable.h"
 #include "runtime/tfproto.h"
 
@@ -508,6 +509,32 @@ PYBIND11_MODULE(_rt, m) {
   m.attr("JPEG_OK") = int(JPEG_OK);
   m.attr("JPEG_UNSUPPORTED") = int(JPEG_UNSUPPORTED);
   m.attr("JPEG_MALFORMED") = int(JPEG_MALFORMED);
+
+  // ---- Pillow's filtered resize as tables (runtime/resample.h); filter: 0 box, 1 bilinear,
+  // 2 hamming, 3 bicubic, 4 lanczos -> (bounds int32 [out, 2], kk int32 [out, ksize])
+  m.def("resample_coeffs", [](int in_size, int out_size, int filter) {
+    std::vector<int32_t> b, k;
+    int ksize;
+    {
+      py::gil_scoped_release nogil;
+      ksize = resample_coeffs(in_size, out_size, filter, &b, &k);
+    }
+    if (ksize < 1) throw std::invalid_argument("resample_coeffs: sizes must be >= 1 and the filter one of 0..4");
+    py::array_t<int32_t> bounds({out_size, 2}), kk({out_size, ksize});
+    std::memcpy(bounds.mutable_data(), b.data(), b.size() * sizeof(int32_t));
+    std::memcpy(kk.mutable_data(), k.data(), k.size() * sizeof(int32_t));
+    return py::make_tuple(bounds, kk);
+  }, py::arg("in_size"), py::arg("out_size"), py::arg("filter"));
+  // one image's descriptor of a GPU resample call -> raw ResampleDesc bytes
+  m.def("resample_desc", [](uint64_t src, uint64_t xb, uint64_t xk, uint64_t yb, uint64_t yk, uint64_t h_xb,
+                            uint64_t h_yb, uint64_t tmp_off, int32_t W, int32_t H, int32_t xksize, int32_t yksize,
+                            int32_t row0, int32_t rows, int32_t out_row) {
+    ResampleDesc d{src, xb, xk, yb, yk, h_xb, h_yb, tmp_off, W, H, xksize, yksize, row0, rows, out_row, 0};
+    return py::bytes(reinterpret_cast<const char*>(&d), sizeof(d));
+  }, py::arg("src"), py::arg("xb"), py::arg("xk"), py::arg("yb"), py::arg("yk"), py::arg("h_xb"), py::arg("h_yb"),
+     py::arg("tmp_off"), py::arg("W"), py::arg("H"), py::arg("xksize"), py::arg("yksize"), py::arg("row0"),
+     py::arg("rows"), py::arg("out_row"));
+  m.attr("RESAMPLE_DESC_BYTES") = int(sizeof(ResampleDesc));
 
   m.attr("ST_OK") = int(ST_OK);
   m.attr("ST_DEADLINE") = int(ST_DEADLINE);

@@ -50,8 +50,12 @@ GPU_SOURCES = sorted((HERE / "kernels").glob("*.hip")) + [HERE / "runtime" / "en
                                                          HERE / "runtime" / "dp_hiploop.cpp",
                                                          HERE / "bindings_gpu.cpp"]
 RT_SOURCES = [HERE / "runtime" / n for n in ("batcher.cpp", "executor.cpp", "tfproto.cpp", "sstable.cpp", "dp_loop.cpp",
-                                                "h2.cpp", "grpc_front.cpp", "grpc_load.cpp", "jpeg.cpp")] + [
+                                                "h2.cpp", "grpc_front.cpp", "grpc_load.cpp", "jpeg.cpp",
+                                                "resample.cpp")] + [
     HERE / "bindings_rt.cpp"]
+# resample.cpp reproduces Pillow's double-precision coefficient arithmetic operation by operation:
+# a fused multiply-add would move a coefficient by one unit
+RT_FLAGS = {"resample.cpp": ["-ffp-contract=off"]}
 HEADERS = sorted(HERE.rglob("*.h"))
 
 
@@ -117,7 +121,7 @@ def build_rt(force: bool = False, njobs: int = 8, verbose: bool = True) -> Path:
         obj = OBJ / (src.stem + "_rt.o")
         objs.append(obj)
         if force or _stale(obj, src):
-            jobs.append(([cxx, *common, "-c", str(src), "-o", str(obj)], obj))
+            jobs.append(([cxx, *common, *RT_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)], obj))
     if jobs and verbose:
         print(f"[kdl.build] compiling {len(jobs)} runtime source(s)", flush=True)
     _compile_all(jobs, njobs)

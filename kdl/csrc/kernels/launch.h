@@ -336,6 +336,26 @@ struct JpegArgs {
 hipError_t jpeg_idct_u8(const JpegArgs& a, hipStream_t s);
 hipError_t jpeg_sample_rgb_u8(const JpegArgs& a, hipStream_t s);
 
+// Pillow's filtered resize + crop (kernels/resample.hip): a table-driven separable convolution
+// over uint8 RGB. resample_h_u8 runs the horizontal pass of n images into the intermediate
+// scratch (kind 0: packed raw pixels; 1: the sample planes of jpeg_idct_u8), resample_v_u8 the
+// vertical pass into each image's row desc.out_row of out. Both launchers check every descriptor
+// and bounds table (the host copies) against the capacities given here.
+struct ResampleDesc;
+struct ResampleArgs {
+  const ResampleDesc* desc;    // [n] in device memory
+  const ResampleDesc* h_desc;  // the same [n] in host memory (checked, never dereferenced on the device)
+  const JpegDesc* jdesc;       // kind 1: the call's JPEG descriptors, n_jdesc of them (device / host copy)
+  const JpegDesc* h_jdesc;
+  const uint8_t* planes;       // kind 1: sample planes, plane_cap bytes
+  uint8_t* tmp;                // intermediate scratch, tmp_cap bytes
+  uint8_t* out;                // [out_rows][OH][OW][3]
+  uint64_t plane_cap, tmp_cap;
+  int n_jdesc, n, out_rows, OH, OW;
+};
+hipError_t resample_h_u8(const ResampleArgs& a, int kind, hipStream_t s);
+hipError_t resample_v_u8(const ResampleArgs& a, hipStream_t s);
+
 // Elementwise: uint8 HWC image -> Xception-normalised bf16 NHWC padded to ldy
 // (x/127.5 - 1), used by the non-folded path and by tests.
 hipError_t u8_to_bf16_norm(const uint8_t* x, uint16_t* y, long npix, int ldy, hipStream_t s);

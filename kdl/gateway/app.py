@@ -11,7 +11,9 @@ mode that ships uint8 pixels to the ``serving_uint8`` signature (4x fewer bytes)
 Env: TF_SERVING_HOST, MODEL_NAME, SIGNATURE, INPUT_KEY, OUTPUT_KEY, LABELS,
 GATEWAY_MODE=compat|uint8|raw|bytes (raw: decoded pixels at their own size to ``serving_image``,
 resized on the model server's GPU -- no resize here; bytes: the fetched file as it is to
-``serving_bytes``, decoded and resized on the model server -- no PIL here), PREDICT_TIMEOUT, GATEWAY_CHANNELS (gRPC connections to open:
+``serving_bytes``, decoded and resized on the model server -- no PIL here), GATEWAY_PREPROCESS
+(``<filter>[:<R>]``, default ``nearest``: the resize of the compat and uint8 modes, through Pillow),
+PREDICT_TIMEOUT, GATEWAY_CHANNELS (gRPC connections to open:
 each gets its own subchannel, so a node running one model-server process per GPU on a
 shared SO_REUSEPORT port -- ``--procs`` -- sees the gateway's requests spread over all
 of them instead of pinned to whichever process accepted a single connection).
@@ -48,6 +50,9 @@ class GatewayConfig:
         self.labels = [s for s in labels.split(",") if s] or list(DEFAULT_LABELS)
         self.timeout = float(env.get("PREDICT_TIMEOUT", "20.0"))
         self.channels = max(1, int(env.get("GATEWAY_CHANNELS", "1")))
+        # the resize of the compat / uint8 modes ("<filter>[:<R>]", preprocess.ResizeSpec) to the
+        # 299 x 299 model input; raw and bytes leave it to the model server (its --preprocess)
+        self.preprocess = pp.ResizeSpec.parse(env.get("GATEWAY_PREPROCESS", "nearest"), pp.TARGET[0])
 
 
 def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = None) -> Flask:
@@ -69,10 +74,13 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     app.config["kdl_gateway"] = cfg
 
     def tensor_from_image(img):
-        if cfg.mode == "uint8":
-            return pp.to_uint8(img)[None]
         if cfg.mode == "raw":
             return np.asarray(img, dtype=np.uint8)[None]
+        if cfg.preprocess != pp.NEAREST_SPEC:
+            px = pp.apply_spec_pil(img, cfg.preprocess, pp.TARGET[0])[None]
+            return px if cfg.mode == "uint8" else pp.xception_preprocess(px)
+        if cfg.mode == "uint8":
+            return pp.to_uint8(img)[None]
         return pp.image_to_tensor(img)
 
     def run(X):

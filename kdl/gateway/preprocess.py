@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import io
 import urllib.request
+from dataclasses import dataclass
 
 import numpy as np
 from PIL import Image
@@ -46,6 +47,83 @@ def resize_nearest_np(arr: np.ndarray, target=TARGET) -> np.ndarray:
     h, w = arr.shape[:2]
     ys, xs = nearest_indices(h, target[1]), nearest_indices(w, target[0])
     return arr[ys][:, xs]
+
+
+PIL_FILTERS = {"nearest": Image.NEAREST, "box": Image.BOX, "bilinear": Image.BILINEAR, "hamming": Image.HAMMING,
+               "bicubic": Image.BICUBIC, "lanczos": Image.LANCZOS}
+
+
+@dataclass(frozen=True)
+class ResizeSpec:
+    """How an image of any size becomes the model's S x S input: ``"<filter>[:<R>]"``.
+
+    Without ``R`` the image is resized to S x S (squash). With ``R >= S`` it is torchvision's
+    ``Resize(R)`` + ``CenterCrop(S)``: the shorter side becomes R, the longer ``int(R * long /
+    short)``, and the S x S window starts at ``int(round((side - S) / 2.0))``. ``nearest`` alone
+    is the default and the reference's keras_image_helper contract."""
+    filter: str = "nearest"
+    resize_to: int | None = None
+
+    def __post_init__(self):
+        if self.filter not in PIL_FILTERS:
+            raise ValueError(f"unknown resize filter {self.filter!r} (one of {', '.join(PIL_FILTERS)})")
+        if self.resize_to is not None and (not isinstance(self.resize_to, int) or self.resize_to < 1):
+            raise ValueError(f"resize target must be a positive integer, got {self.resize_to!r}")
+
+    @classmethod
+    def parse(cls, text: "str | ResizeSpec | None", size: int | None = None) -> "ResizeSpec":
+        """The spec of ``text`` ('' / None: the default); with ``size`` (the model input S) given,
+        ``R < S`` is rejected here."""
+        if isinstance(text, cls):
+            spec = text
+        else:
+            text = "" if text is None else str(text).strip()
+            name, sep, r = text.partition(":")
+            if sep and not (r.isascii() and r.isdigit()):
+                raise ValueError(f"bad preprocess spec {text!r}: expected '<filter>[:<R>]' with an integer R")
+            spec = cls((name or "nearest") if not sep else name, int(r) if sep else None)
+        if size is not None:
+            spec.check(size)
+        return spec
+
+    def check(self, S: int) -> None:
+        if self.resize_to is not None and self.resize_to < S:
+            raise ValueError(f"preprocess spec {self}: the resize target {self.resize_to} is smaller than the "
+                             f"model input {S}, a center crop of {S} does not fit")
+
+    @property
+    def squash(self) -> bool:
+        return self.resize_to is None
+
+    def geometry(self, H: int, W: int, S: int) -> tuple[int, int, int, int]:
+        """(nh, nw, top, left): the size the H x W image is resized to and the S x S window of it."""
+        self.check(S)
+        R = self.resize_to
+        if R is None:
+            return S, S, 0, 0
+        if W <= H:
+            nw, nh = R, int(R * H / W)
+        else:
+            nh, nw = R, int(R * W / H)
+        return nh, nw, int(round((nh - S) / 2.0)), int(round((nw - S) / 2.0))
+
+    def __str__(self) -> str:
+        return self.filter if self.resize_to is None else f"{self.filter}:{self.resize_to}"
+
+
+NEAREST_SPEC = ResizeSpec()
+
+
+def apply_spec_pil(img: Image.Image, spec: ResizeSpec, S: int) -> np.ndarray:
+    """uint8 [S, S, 3] of ``img`` under ``spec`` through Pillow itself: the definition of correct
+    for the GPU kernels, and the path of CPU servers and of the gateway's compat / uint8 modes."""
+    if img.mode != "RGB":
+        img = img.convert("RGB")
+    nh, nw, top, left = spec.geometry(img.height, img.width, S)
+    out = img.resize((nw, nh), PIL_FILTERS[spec.filter])
+    if (nh, nw) != (S, S):
+        out = out.crop((left, top, left + S, top + S))
+    return np.asarray(out, dtype=np.uint8)
 
 
 def xception_preprocess(x: np.ndarray) -> np.ndarray:

@@ -35,6 +35,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ..gateway.preprocess import NEAREST_SPEC, ResizeSpec
 from ..models import xception as X
 from ..ops import _lib
 from . import protos as P
@@ -79,6 +80,8 @@ class ModelSource:
     family: str = "xception"
     input_size: int = IMG
     classes: int = 10
+    # how serving_image / serving_bytes resize to input_size (gateway.preprocess.ResizeSpec)
+    preprocess: ResizeSpec = NEAREST_SPEC
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -97,9 +100,25 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
                        input_size=S, classes=n)
 
 
-def load_version_dir(path: Path, synthetic: bool = False) -> ModelSource:
-    """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic."""
+def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "") -> ModelSource:
+    """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
+    version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
+    "preprocess" string of its kdl_model.json / synthetic.json, else nearest."""
     path = Path(path)
+    src = _load_version_dir(path, synthetic)
+    declared = ""
+    for name in ("kdl_model.json", "synthetic.json"):
+        if (path / name).exists():
+            declared = json.loads((path / name).read_text()).get("preprocess", "")
+            break
+    try:
+        src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from e
+    return src
+
+
+def _load_version_dir(path: Path, synthetic: bool) -> ModelSource:
     sigs: dict[str, SignatureInfo] = {}
     if (path / "saved_model.pb").exists():
         from ..ingest.keras_map import to_xception_params
@@ -732,9 +751,11 @@ class Servable:
                     raise ServingError("INVALID_ARGUMENT", f"Serving signature name: \"{sig_name}\" not found "
                                        "in signature def")
                 if sig_name == IMAGE_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices)
+                    r = ImageRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
+                                    self.source.preprocess)
                 elif sig_name == BYTES_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices)
+                    r = BytesRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
+                                    self.source.preprocess)
                 else:
                     r = SignatureRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 self.runners[sig_name] = r

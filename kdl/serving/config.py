@@ -81,6 +81,9 @@ class ServerConfig:
     procs: int = 1
     gpu_index: int = -1
     warm_signatures: list[str] = field(default_factory=list)   # built at load, besides serving_default
+    # how serving_image / serving_bytes turn an image into the model input: "<filter>[:<R>]"
+    # (gateway.preprocess.ResizeSpec); "" = the model version's own "preprocess", else nearest
+    preprocess: str = ""
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -165,6 +168,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--warm_signatures", default="",
                     help="comma list of signatures whose engines / graphs are built at model load (like "
                          "TF-Serving warmup requests); serving_default always is")
+    ap.add_argument("--preprocess", default=None,
+                    help="resize of serving_image / serving_bytes: '<filter>[:<R>]', filter nearest | box | bilinear | "
+                         "hamming | bicubic | lanczos (Pillow-exact); without R the image is squashed to the model "
+                         "size, with R the shorter side becomes R and the center is cropped (torchvision "
+                         "Resize(R) + CenterCrop). Overrides the model version's \"preprocess\" (env KDL_PREPROCESS, "
+                         "default: the version's, else nearest)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -221,6 +230,7 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         exec_depth=a.exec_depth if a.exec_depth is not None else int(env.get("KDL_EXEC_DEPTH", "2")),
                         procs=max(1, a.procs), gpu_index=a.gpu_index,
                         warm_signatures=[s for s in a.warm_signatures.split(",") if s],
+                        preprocess=a.preprocess if a.preprocess is not None else env.get("KDL_PREPROCESS", ""),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

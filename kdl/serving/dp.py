@@ -80,7 +80,7 @@ def share_source(source, dev: torch.device):
         meta[0] = dict(keys=keys, shapes={k: tuple(source.params[k].shape) for k in keys},
                        dtypes={k: str(source.params[k].dtype) for k in keys}, head=source.head,
                        signatures=source.signatures, origin=source.origin, family=source.family,
-                       input_size=source.input_size, classes=source.classes)
+                       input_size=source.input_size, classes=source.classes, preprocess=source.preprocess)
     dist.broadcast_object_list(meta, src=0)
     m = meta[0]
     params = {k: v.float() for k, v in source.params.items()} if rank == 0 else None
@@ -90,7 +90,8 @@ def share_source(source, dev: torch.device):
     if rank == 0:
         return source
     return ModelSource(params=flat, head=m["head"], signatures=m["signatures"], origin=m["origin"] + " (C1 broadcast)",
-                       family=m["family"], input_size=m["input_size"], classes=m["classes"])
+                       family=m["family"], input_size=m["input_size"], classes=m["classes"],
+                       preprocess=m["preprocess"])
 
 
 # ---------------------------------------------------------------------- local forward

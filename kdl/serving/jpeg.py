@@ -15,6 +15,11 @@ native executors, the batch never returns to the host. The arithmetic is libjpeg
 default decode, so each row equals ``gateway.preprocess.to_uint8(load_image(data), (S, S))``
 bit for bit and the logits equal ``serving_image``'s for the PIL-decoded pixels.
 
+Under a filtered preprocess spec (serving/resize.py) the second launch is replaced by Pillow's two
+resize passes: ``jpeg_idct_u8`` -> ``resample_h_u8`` (JPEG kind: the horizontal pass reads the
+sample planes and converts each source pixel once on its way into LDS) -> ``resample_v_u8``; the
+rows then equal ``apply_spec_pil(load_image(data), spec, S)``.
+
 Files the decoder does not cover (progressive or arithmetic JPEG, CMYK, PNG, ...) are decoded by
 PIL on the host and resized by ``resize_nearest_u8`` into the same batch. Without a GPU the same
 arithmetic runs on the CPU (``jpeg_pixels_cpu``) followed by the numpy gather.
@@ -30,7 +35,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ..gateway.preprocess import load_image
+from ..gateway.preprocess import NEAREST_SPEC, ResizeSpec, apply_spec_pil, load_image
 from ..ops import _lib
 from . import protos as P
 from .metrics import METRICS
@@ -105,11 +110,13 @@ class BytesRunner:
     """The ``serving_bytes`` signature: decode + resize (GPU when the servable has one), then the
     ``serving_uint8`` runner's batcher and executors."""
 
-    def __init__(self, sig, inner, devices: list[int]):
+    def __init__(self, sig, inner, devices: list[int], spec: ResizeSpec | None = None):
         self.sig, self.inner = sig, inner
         self.source = inner.source
         self.S = inner.source.input_size
-        self.resizer = Resizer(self.S, devices or None)    # contexts, table cache, PIL-fallback resize
+        self.spec = spec if spec is not None else getattr(inner.source, "preprocess", NEAREST_SPEC)
+        # contexts, table cache, PIL-fallback resize
+        self.resizer = Resizer(self.S, devices or None, spec=self.spec)
         self.gpu = bool(devices)
         self.device_path = self.gpu and inner.takes_device_items()
 
@@ -180,8 +187,12 @@ class BytesRunner:
                 METRICS.inc("kdl_jpeg_decoded_total", path="cpu")
             else:
                 px = self._pil(i, data)
-            ys, xs = self.resizer._tables(px.shape[0], px.shape[1], None)
-            out[i] = px[ys][:, xs]
+            if self.resizer.filtered:               # Pillow itself: the definition of the filtered specs
+                out[i] = apply_spec_pil(Image.fromarray(px), self.spec, S)
+            else:
+                ys, xs = self.resizer._tables(px.shape[0], px.shape[1], None)
+                out[i] = px[ys][:, xs]
+        METRICS.inc("kdl_resize_total", filter=self.spec.filter)
         return out
 
     # ------------------------------------------------------------------ GPU
@@ -192,6 +203,9 @@ class BytesRunner:
         S, n = self.S, len(plan)
         slot = {i: k for k, i in enumerate(i for i, p in enumerate(plan) if p[1] is not None)}
         lay = CallLayout([plan[i][1].ncoef for i in slot])
+        METRICS.inc("kdl_resize_total", filter=self.spec.filter)
+        if self.resizer.filtered:
+            return self._resample_on(c, plan, slot, lay)
         n_in, n_out = lay.nbytes, n * S * S * 3
         c.grow(max(n_in, 1), n_out)
         c.grow_planes(max(lay.ncoef, 1))                # sample planes: one byte per coefficient
@@ -223,6 +237,59 @@ class BytesRunner:
                 keep += [ys, xs, src]
                 C.resize_nearest_u8(dict(src=_lib.ptr(src), dst=_lib.ptr(c.d_out) + i * S * S * 3, ytab=_lib.ptr(ys),
                                          xtab=_lib.ptr(xs), SH=px.shape[0], SW=px.shape[1], OH=S, OW=S, n=1), stream)
+        c.keep = keep
+        return n_out
+
+    def _resample_on(self, c, plan, slot, lay) -> int:
+        """``_decode_on`` of a filtered spec: jpeg_idct_u8, then the horizontal pass straight from the
+        sample planes (resample_h_u8, JPEG kind; raw kind for what PIL decoded), then one vertical pass
+        over all images of the request. Staging: [the CallLayout | one ResampleDesc per image]."""
+        C, D = _lib.lib(), _lib.rt().RESAMPLE_DESC_BYTES
+        S, n = self.S, len(plan)
+        off_desc = _align(lay.nbytes, 256)
+        n_in, n_out = off_desc + n * D, n * S * S * 3
+        c.grow(n_in, n_out)
+        c.grow_planes(max(lay.ncoef, 1))
+        hin = c.h_in.numpy()
+        self._parse_all(plan, {i: lay.coef(hin, k, plan[i][1].ncoef) for i, k in slot.items()})
+        # every host step that can fail comes before the first launch (see _decode_on)
+        pil = {i: self._pil(i, p[0]) for i, p in enumerate(plan) if p[1] is None}
+        keep, descs, raw, tmp = [], [], [], 0       # JPEG descriptors first, then the PIL-decoded images
+        for i, k in slot.items():
+            hd = plan[i][1]
+            if hd is None:
+                continue
+            t = self.resizer._tables(hd.H, hd.W, c.dev)
+            keep.append(t)
+            descs.append(t.desc(lay.n_desc, tmp, i))
+            lay.add(hin, k, hd, i, t.dev[2], t.dev[0])      # the nearest tables of the descriptor: unused here
+            tmp += t.tmp_bytes
+        for i, px in pil.items():
+            t = self.resizer._tables(px.shape[0], px.shape[1], c.dev)
+            src = torch.empty(px.shape, dtype=torch.uint8, device=c.dev)     # filled on the stream below
+            keep += [t, src]
+            raw.append((src, px))
+            descs.append(t.desc(_lib.ptr(src), tmp, i))
+            tmp += t.tmp_bytes
+        c.grow_tmp(tmp)
+        hin[off_desc:off_desc + n * D] = np.concatenate(descs)
+        nj, stream = lay.n_desc, int(c.stream.cuda_stream)
+        with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
+            c.d_in[:n_in].copy_(c.h_in[:n_in], non_blocking=True)
+            rs = dict(desc=_lib.ptr(c.d_in) + off_desc, h_desc=_lib.ptr(c.h_in) + off_desc, jdesc=_lib.ptr(c.d_in),
+                      h_jdesc=_lib.ptr(c.h_in), n_jdesc=nj, planes=_lib.ptr(c.d_planes), plane_cap=c.cap_planes,
+                      tmp=_lib.ptr(c.d_tmp), tmp_cap=c.cap_tmp, out=_lib.ptr(c.d_out), out_rows=n, OH=S, OW=S, n=n)
+            if nj:
+                C.jpeg_idct_u8(lay.args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_planes), c.cap_planes,
+                                        _lib.ptr(c.d_out), n, S, S), stream)
+                C.resample_h_u8({**rs, "n": nj}, 1, stream)
+                METRICS.inc("kdl_jpeg_decoded_total", nj, path="gpu")
+            if n > nj:
+                for src, px in raw:
+                    src.copy_(torch.from_numpy(np.ascontiguousarray(px)))
+                C.resample_h_u8({**rs, "desc": rs["desc"] + nj * D, "h_desc": rs["h_desc"] + nj * D, "n": n - nj},
+                                0, stream)
+            C.resample_v_u8(rs, stream)
         c.keep = keep
         return n_out
 

@@ -37,7 +37,7 @@ def latest_version_source(cfg: ServerConfig):
     versions = list_versions(base) or ([1] if cfg.synthetic else [])
     if not versions:
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
-    return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic)
+    return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess)
 
 
 class ModelManager:
@@ -73,7 +73,7 @@ class ModelManager:
             self.states[v] = (LOADING, "")
         t0 = time.perf_counter()
         try:
-            src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic)
+            src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)
@@ -85,7 +85,7 @@ class ModelManager:
             self.states[v] = (AVAILABLE, "")
             old = [k for k in self.servables if k != v]
         self._changed()
-        log.info("loaded %s version %d (%s) on %s in %.1fs", self.name, v, src.origin,
+        log.info("loaded %s version %d (%s, preprocess %s) on %s in %.1fs", self.name, v, src.origin, src.preprocess,
                  f"gpus {self.devices}" if self.devices else "cpu", time.perf_counter() - t0)
         for k in old:  # latest policy: retire older versions once the new one is live
             self._unload(k)
