@@ -6,6 +6,7 @@
 #include <pybind11/stl.h>
 
 #include "kernels/launch.h"
+#include "runtime/jpeg_huff.h"
 #include "runtime/engine.h"
 #include "runtime/comm.h"
 #include "runtime/dp_hiploop.h"
@@ -214,6 +215,14 @@ uint64_t U64(const py::dict& d, const char* k) {
   if (!d.contains(k) || d[k].is_none()) return 0;
   return d[k].cast<uint64_t>();
 }
+JpegHuffArgs jpeg_huff_args(const py::dict& d) {
+  JpegHuffArgs a{};
+  a.desc = P<const JpegHuffDesc>(d, "desc"); a.h_desc = P<const JpegHuffDesc>(d, "h_desc");
+  a.stage = P<const uint8_t>(d, "stage"); a.coef = P<int16_t>(d, "coef"); a.status = P<uint32_t>(d, "status");
+  a.stage_cap = U64(d, "stage_cap"); a.coef_cap = U64(d, "coef_cap");
+  a.status_cap = I(d, "status_cap"); a.n = I(d, "n");
+  return a;
+}
 ResampleArgs resample_args(const py::dict& d) {
   ResampleArgs a{};
   a.desc = P<const ResampleDesc>(d, "desc"); a.h_desc = P<const ResampleDesc>(d, "h_desc");
@@ -371,6 +380,20 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(jpeg_sample_rgb_u8(a, S(s)), "jpeg_sample_rgb_u8");
   });
+  // baseline JPEG entropy decode (kernels/jpeg_huff.hip): d = the JpegHuffArgs fields; h_desc is a HOST address
+  m.def("jpeg_huff_decode", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_huff_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_huff_decode(a, S(s)), "jpeg_huff_decode");
+  });
+  m.def("jpeg_dc_scan", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_huff_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_dc_scan(a, S(s)), "jpeg_dc_scan");
+  });
+  m.attr("JPEG_HUFF_SUB_BITS") = int(kJpegHuffSubBits);
+  m.attr("JPEG_HUFF_CHUNK") = int(kJpegHuffChunk);
+  m.attr("JPEG_HUFF_DESC_BYTES") = int(sizeof(JpegHuffDesc));
   // Pillow's filtered resize (kernels/resample.hip): d = the ResampleArgs fields; h_desc, h_jdesc
   // and the h_xb / h_yb of every descriptor are HOST addresses. kind: 0 raw pixels, 1 JPEG planes
   m.def("resample_h_u8", [](py::dict d, int kind, uintptr_t s) {

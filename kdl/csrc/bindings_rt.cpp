@@ -20,6 +20,7 @@
 #include "runtime/grpc_load.h"
 #include "runtime/h2.h"
 #include "runtime/jpeg.h"
+#include "runtime/jpeg_huff.h"
 #include "runtime/resample.h"
 #include "runtime/sstable.h"
 #include "runtime/tfproto.h"
@@ -505,6 +506,66 @@ PYBIND11_MODULE(_rt, m) {
     return py::make_tuple(py::bytes(reinterpret_cast<const char*>(&d), sizeof(d)), wg);
   }, py::arg("header"), py::arg("coef_base"), py::arg("plane_base"), py::arg("qt_base"), py::arg("wg"),
      py::arg("out_row"), py::arg("ytab"), py::arg("xtab"));
+  // ---- the scan prepared for the device entropy decode (runtime/jpeg_huff.h) and its host emulation
+  py::class_<JpegHuffInfo>(m, "JpegHuffInfo")
+      .def_readonly("nbits", &JpegHuffInfo::nbits)
+      .def_readonly("scan_bytes", &JpegHuffInfo::scan_bytes)
+      .def_readonly("scan_off", &JpegHuffInfo::scan_off)
+      .def_readonly("nblocks", &JpegHuffInfo::nblocks)
+      .def_readonly("nbytes", &JpegHuffInfo::nbytes)
+      .def_readonly("nb", &JpegHuffInfo::nb)
+      .def_readonly("device_ok", &JpegHuffInfo::device_ok)
+      .def_property_readonly("comp", [](const JpegHuffInfo& i) {
+        return std::vector<int>(i.comp, i.comp + (i.nb > 0 && i.nb <= 8 ? i.nb : 0));
+      });
+  m.def("jpeg_prepare_bound", [](uint64_t n) { return jpeg_prepare_bound(n); });
+  // `out`: a writable, 4-byte aligned buffer of at least jpeg_prepare_bound(len(data)) bytes
+  m.def("jpeg_scan_prepare", [](py::bytes data, py::buffer out, uint64_t max_pixels) {
+    std::string_view sv = data;
+    py::buffer_info oi = out.request(true);
+    if (reinterpret_cast<uintptr_t>(oi.ptr) % 4) throw std::invalid_argument("jpeg_scan_prepare: unaligned buffer");
+    const uint64_t cap = uint64_t(oi.size) * uint64_t(oi.itemsize);
+    JpegHeader h;
+    JpegHuffInfo info;
+    int st;
+    {
+      py::gil_scoped_release nogil;
+      st = jpeg_scan_prepare(reinterpret_cast<const uint8_t*>(sv.data()), sv.size(), max_pixels,
+                             static_cast<uint8_t*>(oi.ptr), cap, &h, &info);
+    }
+    return py::make_tuple(st, h, info);
+  }, py::arg("data"), py::arg("out"), py::arg("max_pixels") = uint64_t(64) << 20);
+  // one image's descriptor of a device entropy decode: the prepared buffer sits at byte
+  // `stage_base` of the call's staging, the planes at `coef_base` of its coefficients
+  m.def("jpeg_huff_desc", [](const JpegHeader& h, const JpegHuffInfo& info, uint64_t stage_base, uint64_t coef_base) {
+    JpegHuffDesc d;
+    jpeg_huff_fill_desc(h, info, stage_base, coef_base, &d);
+    return py::bytes(reinterpret_cast<const char*>(&d), sizeof(d));
+  }, py::arg("header"), py::arg("info"), py::arg("stage_base"), py::arg("coef_base"));
+  // the kernels' procedure on the host -> (error word, most rounds of a chunk, indices out of bounds)
+  m.def("jpeg_huff_cpu", [](py::bytes desc, py::buffer stage, py::buffer coef) {
+    std::string_view dv = desc;
+    if (dv.size() != sizeof(JpegHuffDesc)) throw std::invalid_argument("jpeg_huff_cpu: not a JpegHuffDesc");
+    JpegHuffDesc d;
+    std::memcpy(&d, dv.data(), sizeof(d));
+    py::buffer_info si = stage.request(), ci = coef.request(true);
+    if (reinterpret_cast<uintptr_t>(si.ptr) % 4 || reinterpret_cast<uintptr_t>(ci.ptr) % alignof(int16_t))
+      throw std::invalid_argument("jpeg_huff_cpu: unaligned buffer");
+    const uint64_t scap = uint64_t(si.size) * uint64_t(si.itemsize);
+    const uint64_t ccap = uint64_t(ci.size) * uint64_t(ci.itemsize) / sizeof(int16_t);
+    uint32_t err = 0, rounds = 0;
+    uint64_t bad;
+    {
+      py::gil_scoped_release nogil;
+      bad = jpeg_huff_cpu(d, static_cast<const uint8_t*>(si.ptr), scap, static_cast<int16_t*>(ci.ptr), ccap, &err,
+                          &rounds);
+    }
+    return py::make_tuple(err, rounds, bad);
+  }, py::arg("desc"), py::arg("stage"), py::arg("coef"));
+  m.attr("JPEG_HUFF_SUB_BITS") = int(kJpegHuffSubBits);
+  m.attr("JPEG_HUFF_CHUNK") = int(kJpegHuffChunk);
+  m.attr("JPEG_HUFF_DESC_BYTES") = int(sizeof(JpegHuffDesc));
+  m.attr("JPEG_HUFF_TAB_BYTES") = int(kJpegHuffTabBytes);
   m.attr("JPEG_DESC_BYTES") = int(sizeof(JpegDesc));
   m.attr("JPEG_OK") = int(JPEG_OK);
   m.attr("JPEG_UNSUPPORTED") = int(JPEG_UNSUPPORTED);

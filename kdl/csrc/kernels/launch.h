@@ -336,6 +336,25 @@ struct JpegArgs {
 hipError_t jpeg_idct_u8(const JpegArgs& a, hipStream_t s);
 hipError_t jpeg_sample_rgb_u8(const JpegArgs& a, hipStream_t s);
 
+// Baseline JPEG entropy decode (kernels/jpeg_huff.hip): the host has staged each image's Huffman
+// tables and unstuffed scan (jpeg_scan_prepare, runtime/jpeg_huff.h); jpeg_huff_decode clears the
+// image's coefficient planes and Huffman-decodes the scan into them (AC values, DC differences),
+// jpeg_dc_scan sums the DC differences. The planes are then what jpeg_idct_u8 reads. Both
+// launchers check every descriptor (the host copy) against the capacities given here.
+struct JpegHuffDesc;
+struct JpegHuffArgs {
+  const JpegHuffDesc* desc;    // [n] in device memory
+  const JpegHuffDesc* h_desc;  // the same [n] in host memory (checked, never dereferenced on the device)
+  const uint8_t* stage;        // tables and scans, stage_cap bytes
+  int16_t* coef;               // coefficients, coef_cap int16
+  uint32_t* status;            // per image: error word (non-zero = ask the host decoder), most rounds of a chunk
+  uint64_t stage_cap, coef_cap;
+  int status_cap;              // uint32 of status: at least 2 * n
+  int n;
+};
+hipError_t jpeg_huff_decode(const JpegHuffArgs& a, hipStream_t s);
+hipError_t jpeg_dc_scan(const JpegHuffArgs& a, hipStream_t s);
+
 // Pillow's filtered resize + crop (kernels/resample.hip): a table-driven separable convolution
 // over uint8 RGB. resample_h_u8 runs the horizontal pass of n images into the intermediate
 // scratch (kind 0: packed raw pixels; 1: the sample planes of jpeg_idct_u8), resample_v_u8 the

@@ -1,6 +1,7 @@
 // Baseline JPEG: marker walk + Huffman decode on the host, and the CPU pixel path (jpeg.h).
 // The input is untrusted: every read is bounded by the buffer and every index by its table.
 #include "runtime/jpeg.h"
+#include "runtime/jpeg_huff.h"
 
 #include <cstring>
 #include <vector>
@@ -155,6 +156,10 @@ struct Parser {
   bool have_qt[4] = {false, false, false, false};
   bool have_sof = false, jfif = false, adobe = false;
   int adobe_transform = 0;
+  // jpeg_scan_prepare: stage the scan for the device decode instead of decoding it
+  uint8_t* prep = nullptr;
+  uint64_t prep_cap = 0;
+  JpegHuffInfo* info = nullptr;
 
   JpegStatus sof0(const uint8_t* s, size_t sl) {
     if (have_sof) return fail(h, JPEG_MALFORMED, "two frame headers");
@@ -258,6 +263,7 @@ struct Parser {
       const bool ids = h->comp[0].id == 1 && h->comp[1].id == 2 && h->comp[2].id == 3;
       if (!jfif && !adobe && !ids) return fail(h, JPEG_UNSUPPORTED, "colour space is not known to be YCbCr");
     }
+    if (info) return prepare(tdc, tac, ns, pos);
     if (cap < h->ncoef || coef == nullptr) return fail(h, JPEG_MALFORMED, "coefficient buffer too small");
 
     Bits b{data + pos, data + n};
@@ -328,6 +334,75 @@ struct Parser {
         if (h->restart) --left;
       }
     }
+    return JPEG_OK;
+  }
+
+  // one table in the device's form (jpeg_huff.h)
+  static void pack_table(const Huff& t, uint32_t* w) {
+    std::memset(w, 0, kJpegHuffTabBytes);
+    for (int i = 0; i < (1 << kFast); ++i) w[i >> 1] |= (uint32_t)t.fast[i] << (16 * (i & 1));
+    for (int l = 1; l <= 16; ++l) {
+      w[kHtMax + l] = (uint32_t)t.maxcode[l];
+      w[kHtOff + l] = (uint32_t)t.valoff[l];
+    }
+    w[kHtMax] = (uint32_t)-1;
+    w[kHtN] = (uint32_t)t.nvals;
+    for (int i = 0; i < t.nvals; ++i) w[kHtVals + (i >> 2)] |= (uint32_t)t.vals[i] << (8 * (i & 3));
+  }
+
+  // tables + the scan with its byte stuffing removed, exactly the bytes that Bits would feed:
+  // FF 00 -> FF, fill bytes dropped, the end at the first marker (or a lone FF at the end)
+  JpegStatus prepare(const Huff* const* tdc, const Huff* const* tac, int ns, size_t pos) {
+    static_assert(kFast == kJpegHuffFastBits, "the device tables mirror the host's first level");
+    const uint64_t tabs = (uint64_t)2 * ns * kJpegHuffTabBytes;
+    if (reinterpret_cast<uintptr_t>(prep) % 4 || prep_cap < tabs + 8)
+      return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+    uint32_t* w = reinterpret_cast<uint32_t*>(prep);
+    for (int c = 0; c < ns; ++c) {
+      pack_table(*tdc[c], w + (2 * c) * kJpegHuffTabWords);
+      pack_table(*tac[c], w + (2 * c + 1) * kJpegHuffTabWords);
+    }
+    uint32_t* sw = w + 2 * ns * kJpegHuffTabWords;
+    const uint64_t room = (prep_cap - tabs) / 4;       // words
+    uint64_t nbytes = 0;
+    uint32_t acc = 0;
+    const uint8_t* p = data + pos;
+    const uint8_t* end = data + n;
+    while (p < end) {
+      uint32_t b = *p;
+      if (b != 0xFF) {
+        ++p;
+      } else if (p + 1 >= end) {
+        break;
+      } else if (p[1] == 0x00) {
+        p += 2;
+      } else if (p[1] == 0xFF) {
+        ++p;
+        continue;
+      } else {
+        break;
+      }
+      acc = (acc << 8) | b;
+      if ((++nbytes & 3) == 0) {
+        if (nbytes / 4 > room) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+        sw[nbytes / 4 - 1] = acc;
+        acc = 0;
+      }
+    }
+    uint64_t nwords = nbytes / 4;
+    if (nwords + 2 > room) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+    if (nbytes & 3) sw[nwords++] = acc << (8 * (4 - (nbytes & 3)));
+    sw[nwords++] = 0;                                    // the zero bits behind the data
+    const int mx = h->comp[0].bw / h->comp[0].h, my = h->comp[0].bh / h->comp[0].v;
+    info->nb = 0;
+    for (int c = 0; c < ns; ++c)
+      for (int i = 0; i < h->comp[c].h * h->comp[c].v; ++i) info->comp[info->nb++] = (uint8_t)c;
+    info->nbits = (uint32_t)(nbytes * 8);
+    info->scan_off = (uint32_t)tabs;
+    info->scan_bytes = (uint32_t)(nwords * 4);
+    info->nbytes = (uint32_t)(tabs + nwords * 4);
+    info->nblocks = (uint32_t)((uint64_t)mx * my * info->nb);
+    info->device_ok = h->restart == 0 && nbytes < (1u << 27);
     return JPEG_OK;
   }
 
@@ -415,6 +490,181 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, uint64_t max_pixels, int16_
   std::vector<Parser> p(1);
   p[0].data = data; p[0].n = n; p[0].max_pixels = max_pixels; p[0].h = h;
   return p[0].run(coef, cap, false);
+}
+
+JpegStatus jpeg_scan_prepare(const uint8_t* data, size_t n, uint64_t max_pixels, uint8_t* out, uint64_t cap,
+                             JpegHeader* h, JpegHuffInfo* info) {
+  *h = JpegHeader{};
+  *info = JpegHuffInfo{};
+  if (n >= (1ull << 31)) return fail(h, JPEG_MALFORMED, "file too large");
+  std::vector<Parser> p(1);
+  p[0].data = data; p[0].n = n; p[0].max_pixels = max_pixels; p[0].h = h;
+  p[0].prep = out; p[0].prep_cap = cap; p[0].info = info;
+  return p[0].run(nullptr, 0, false);
+}
+
+void jpeg_huff_fill_desc(const JpegHeader& h, const JpegHuffInfo& info, uint64_t stage_base, uint64_t coef_base,
+                         JpegHuffDesc* d) {
+  std::memset(d, 0, sizeof(*d));
+  int j = 0;
+  for (int c = 0; c < 3; ++c) {
+    const JpegComp& k = h.comp[c < h.ncomp ? c : 0];
+    d->coef_off[c] = coef_base + k.coef_off;
+    d->bw[c] = k.bw; d->bh[c] = k.bh; d->h[c] = k.h; d->v[c] = k.v;
+    d->tab_off[2 * c] = (uint32_t)(stage_base + (uint64_t)(2 * c) * kJpegHuffTabBytes);
+    d->tab_off[2 * c + 1] = (uint32_t)(stage_base + (uint64_t)(2 * c + 1) * kJpegHuffTabBytes);
+    if (c >= h.ncomp) {
+      d->tab_off[2 * c] = d->tab_off[0];
+      d->tab_off[2 * c + 1] = d->tab_off[1];
+      continue;
+    }
+    for (int v = 0; v < k.v; ++v)
+      for (int u = 0; u < k.h; ++u, ++j) {
+        if (j >= 8) continue;
+        d->comp[j] = (uint8_t)c; d->bu[j] = (uint8_t)u; d->bv[j] = (uint8_t)v;
+      }
+  }
+  d->scan_off = stage_base + info.scan_off;
+  d->scan_bytes = info.scan_bytes; d->nbits = info.nbits; d->nblocks = info.nblocks;
+  d->ncomp = h.ncomp; d->nb = info.nb;
+  d->mx = h.comp[0].h ? h.comp[0].bw / h.comp[0].h : 0;
+  d->my = h.comp[0].v ? h.comp[0].bh / h.comp[0].v : 0;
+}
+
+namespace {
+
+// the kernels' memory as the emulation sees it: every index is checked a second time behind the
+// check of the shared code, and counted when that one let it through
+struct EmuMem {
+  const uint32_t* lds;        // the staged chunk
+  uint32_t w0;                // its first scan word
+  const uint32_t* tabs[6];
+  int16_t* coef;
+  uint64_t coef_cap;
+  uint64_t* bad;
+  uint32_t word(uint32_t w) const {
+    const uint32_t r = w - w0;
+    if (r >= (uint32_t)kJpegHuffStaged) return 0;
+    const uint32_t i = jpeg_huff_lds_index(r);
+    if (i >= (uint32_t)kJpegHuffLdsWords) { ++*bad; return 0; }
+    return lds[i];
+  }
+  const uint32_t* table(int t) const {
+    if (t < 0 || t > 5) { ++*bad; return tabs[0]; }
+    return tabs[t];
+  }
+  void store(uint64_t off, int16_t v) const {
+    if (off >= coef_cap) { ++*bad; return; }
+    coef[off] = v;
+  }
+  uint32_t zz(uint32_t k) const {
+    if (k > 63) { ++*bad; return 0; }
+    return kZigzag[k];
+  }
+};
+
+}  // namespace
+
+uint64_t jpeg_huff_cpu(const JpegHuffDesc& d, const uint8_t* stage, uint64_t stage_cap, int16_t* coef,
+                       uint64_t coef_cap, uint32_t* err, uint32_t* rounds) {
+  *err = 1;
+  *rounds = 0;
+  if (!jpeg_huff_desc_valid(d, stage_cap, coef_cap) || reinterpret_cast<uintptr_t>(stage) % 4) return 0;
+  *err = 0;
+  uint64_t bad = 0;
+  constexpr int T = kJpegHuffChunk;
+  constexpr uint32_t S = kJpegHuffSubBits;
+  for (int c = 0; c < d.ncomp; ++c) {                                  // step 8
+    const uint64_t nc = (uint64_t)d.bw[c] * d.bh[c] * 64;
+    for (uint64_t i = 0; i < nc; ++i) {
+      if (d.coef_off[c] + i >= coef_cap) { ++bad; break; }
+      coef[d.coef_off[c] + i] = 0;
+    }
+  }
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(stage + d.scan_off);
+  const uint32_t nwords = d.scan_bytes / 4;
+  std::vector<uint32_t> lds(kJpegHuffLdsWords);
+  EmuMem m{lds.data(), 0, {}, coef, coef_cap, &bad};
+  for (int t = 0; t < 6; ++t) m.tabs[t] = reinterpret_cast<const uint32_t*>(stage + d.tab_off[t]);
+  const uint32_t nsub = (d.nbits + S - 1) / S;
+  const uint32_t nchunk = (nsub + T - 1) / T;
+  JpegHuffState entry{0, 0};
+  uint32_t base = 0;                                                   // blocks completed before the chunk
+  std::vector<JpegHuffState> ex(T), in(T), last(T);
+  std::vector<uint32_t> cnt(T), excl(T);
+  for (uint32_t ch = 0; ch < nchunk; ++ch) {
+    m.w0 = ch * (uint32_t)kJpegHuffChunkWords;
+    for (uint32_t r = 0; r < (uint32_t)kJpegHuffStaged; ++r) {
+      const uint32_t i = jpeg_huff_lds_index(r);
+      if (i >= (uint32_t)kJpegHuffLdsWords) { ++bad; continue; }
+      lds[i] = m.w0 + r < nwords ? words[m.w0 + r] : 0;
+    }
+    auto end_of = [&](int i) {
+      const uint64_t e = ((uint64_t)ch * T + i + 1) * S;
+      return (uint32_t)(e < d.nbits ? e : d.nbits);
+    };
+    // subsequences that start behind the data decode nothing: left out of the rounds, they do
+    // not hand a change on one thread per round (only the last chunk has any, so its exit state
+    // is needed by nobody)
+    const uint32_t left = nsub - ch * (uint32_t)T;
+    const int live = left < (uint32_t)T ? (int)left : T;
+    for (int i = 0; i < T; ++i) {                                      // steps 1, 2: the cold pass
+      cnt[i] = 0;
+      if (i >= live) continue;
+      last[i] = i ? JpegHuffState{(ch * (uint32_t)T + i) * S, 0} : entry;
+      ex[i] = last[i];
+      cnt[i] = jpeg_huff_run<false>(d, m, &ex[i], end_of(i), 0, err);
+    }
+    uint32_t r = 0;
+    for (; r < (uint32_t)T; ++r) {                                     // steps 3, 4: to the fixed point
+      for (int i = 1; i < T; ++i) in[i] = ex[i - 1];
+      bool any = false;
+      for (int i = 1; i < live; ++i) {
+        if (in[i] == last[i]) continue;
+        last[i] = in[i];
+        JpegHuffState e = in[i];
+        cnt[i] = jpeg_huff_run<false>(d, m, &e, end_of(i), 0, err);
+        if (!(e == ex[i])) any = true;
+        ex[i] = e;
+      }
+      if (!any) break;
+    }
+    if (r + 1 > *rounds) *rounds = r + 1;
+    uint32_t sum = 0;                                                  // step 5
+    for (int i = 0; i < T; ++i) {
+      excl[i] = sum;
+      sum += cnt[i];
+    }
+    for (int i = 0; i < live; ++i) {                                   // step 6: the write pass
+      JpegHuffState st = i ? ex[i - 1] : entry;
+      jpeg_huff_run<true>(d, m, &st, end_of(i), base + excl[i], err);
+    }
+    entry = ex[T - 1];
+    base += sum;
+  }
+  if (base < d.nblocks) *err = 1;                                      // the data ends before the last MCU
+  for (int c = 0; c < d.ncomp; ++c) {                                  // step 7, partitioned as the kernel does
+    const uint32_t n = (uint32_t)d.bw[c] * (uint32_t)d.bh[c], per = (n + T - 1) / T;
+    std::vector<uint32_t> tot(T, 0);
+    for (int i = 0; i < T; ++i)
+      for (uint32_t k = i * per; k < n && k < (i + 1) * per; ++k) {
+        const uint64_t off = jpeg_huff_dc_off(d, c, k);
+        if (off >= coef_cap) { ++bad; continue; }
+        tot[i] += (uint16_t)coef[off];
+      }
+    uint32_t run = 0;
+    for (int i = 0; i < T; ++i) {
+      uint32_t acc = run;
+      for (uint32_t k = i * per; k < n && k < (i + 1) * per; ++k) {
+        const uint64_t off = jpeg_huff_dc_off(d, c, k);
+        if (off >= coef_cap) { ++bad; continue; }
+        acc += (uint16_t)coef[off];
+        coef[off] = (int16_t)(uint16_t)acc;
+      }
+      run += tot[i];
+    }
+  }
+  return bad;
 }
 
 void jpeg_fill_desc(const JpegHeader& h, uint64_t coef_base, uint64_t plane_base, int32_t qt_base, int32_t* wg,

@@ -8,6 +8,7 @@
 // for the tests. The arithmetic is libjpeg-turbo's default decode (JDCT_ISLOW, fancy
 // upsampling), which is what Pillow produces, and lives in this header ONCE (jpeg_idct_1d,
 // jpeg_descale, jpeg_pixel) so that the CPU and the GPU path cannot drift apart.
+// The entropy decode has an opt-in device path as well: runtime/jpeg_huff.h, kernels/jpeg_huff.hip.
 //
 // Self-contained on purpose: plain C++17, no HIP, no libjpeg, referenced only by
 // bindings_rt.cpp (host) and kernels/jpeg.hip + bindings_gpu.cpp (descriptor + arithmetic).

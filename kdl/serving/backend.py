@@ -755,7 +755,7 @@ class Servable:
                                     self.source.preprocess)
                 elif sig_name == BYTES_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
                     r = BytesRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
-                                    self.source.preprocess)
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
                 else:
                     r = SignatureRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 self.runners[sig_name] = r

@@ -84,6 +84,9 @@ class ServerConfig:
     # how serving_image / serving_bytes turn an image into the model input: "<filter>[:<R>]"
     # (gateway.preprocess.ResizeSpec); "" = the model version's own "preprocess", else nearest
     preprocess: str = ""
+    # where serving_bytes Huffman-decodes baseline JPEG scans: "host" (csrc/runtime/jpeg.cpp) or "gpu"
+    # (csrc/kernels/jpeg_huff.hip; files with restart intervals and rejected scans still go to the host)
+    jpeg_entropy: str = "host"
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -174,6 +177,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "size, with R the shorter side becomes R and the center is cropped (torchvision "
                          "Resize(R) + CenterCrop). Overrides the model version's \"preprocess\" (env KDL_PREPROCESS, "
                          "default: the version's, else nearest)")
+    ap.add_argument("--jpeg_entropy", choices=["host", "gpu"], default=None,
+                    help="where serving_bytes Huffman-decodes baseline JPEG scans: host cores, or the GPU (the host "
+                         "then only walks the markers, builds the tables and removes the byte stuffing); env "
+                         "KDL_JPEG_ENTROPY (default host)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -231,6 +238,7 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         procs=max(1, a.procs), gpu_index=a.gpu_index,
                         warm_signatures=[s for s in a.warm_signatures.split(",") if s],
                         preprocess=a.preprocess if a.preprocess is not None else env.get("KDL_PREPROCESS", ""),
+                        jpeg_entropy=a.jpeg_entropy or env.get("KDL_JPEG_ENTROPY", "") or "host",
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

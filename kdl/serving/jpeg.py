@@ -20,6 +20,16 @@ resize passes: ``jpeg_idct_u8`` -> ``resample_h_u8`` (JPEG kind: the horizontal 
 sample planes and converts each source pixel once on its way into LDS) -> ``resample_v_u8``; the
 rows then equal ``apply_spec_pil(load_image(data), spec, S)``.
 
+With ``entropy="gpu"`` (``--jpeg_entropy gpu``, env ``KDL_JPEG_ENTROPY``; the default is ``host``)
+the Huffman decode moves to the device too (csrc/kernels/jpeg_huff.hip). The host only walks the
+markers, builds the code tables and removes the byte stuffing (``kdl._rt.jpeg_scan_prepare``); the
+tables and scans -- about the size of the files -- are staged instead of the coefficients, and
+``jpeg_huff_decode`` + ``jpeg_dc_scan`` fill the coefficient planes, which live in a device-only
+buffer, in front of the unchanged ``jpeg_idct_u8``. Each image's error word returns with the
+request's synchronise; if one is set the whole request is decoded again through the host path,
+whose answer (success, or ``INVALID_ARGUMENT`` with its message) is the request's. A request that
+holds a file with restart intervals takes the host path as a whole.
+
 Files the decoder does not cover (progressive or arithmetic JPEG, CMYK, PNG, ...) are decoded by
 PIL on the host and resized by ``resize_nearest_u8`` into the same batch. Without a GPU the same
 arithmetic runs on the CPU (``jpeg_pixels_cpu``) followed by the numpy gather.
@@ -70,9 +80,14 @@ def _bad(msg: str):
 class CallLayout:
     """Where one GPU decode call keeps its inputs in the staging buffer (pinned on the host, mirrored
     on the device): [descriptors | 4 quantisation tables per image | coefficient planes, each
-    128-byte aligned]. ``ncoefs``: the coefficient count of every image that may join the call."""
+    128-byte aligned]. ``ncoefs``: the coefficient count of every image that may join the call.
 
-    def __init__(self, ncoefs: list[int]):
+    The second form, for the device entropy decode (``prepared``: per image the bound of its prepared
+    buffer, ``kdl._rt.jpeg_prepare_bound``): [descriptors | quantisation tables | one JpegHuffDesc per
+    image | per image its Huffman tables and unstuffed scan]. The coefficient planes then are not
+    staged: they live in a device buffer of ``ncoef`` int16 with the same ``coef_at`` offsets."""
+
+    def __init__(self, ncoefs: list[int], prepared: list[int] | None = None):
         self.desc_bytes = _lib.rt().JPEG_DESC_BYTES
         n = len(ncoefs)
         self.off_qt = _align(n * self.desc_bytes, 256)
@@ -83,6 +98,32 @@ class CallLayout:
             self.ncoef += _align(k, 64)
         self.nbytes = self.off_coef + 2 * self.ncoef
         self.n_desc = self.n_wg = 0
+        self.device_entropy = prepared is not None
+        if prepared is not None:
+            self.huff_bytes = _lib.rt().JPEG_HUFF_DESC_BYTES
+            self.off_huff, self.n_huff = self.off_coef, 0
+            self.prep_at, o = [], _align(self.off_huff + n * self.huff_bytes, 256)
+            for b in prepared:
+                self.prep_at.append(o)
+                o += _align(b, 256)
+            self.nbytes = o
+
+    def prep(self, hin: np.ndarray, k: int) -> np.ndarray:
+        """Slot ``k``'s room for its prepared tables and scan inside the staging array ``hin``."""
+        end = self.prep_at[k + 1] if k + 1 < len(self.prep_at) else self.nbytes
+        return hin[self.prep_at[k]:end]
+
+    def add_huff(self, hin: np.ndarray, k: int, header, info) -> None:
+        """Stage the entropy-decode descriptor of slot ``k``; call in the order of ``add``."""
+        j, D = self.n_huff, self.huff_bytes
+        desc = _lib.rt().jpeg_huff_desc(header, info, self.prep_at[k], self.coef_at[k])
+        hin[self.off_huff + j * D:self.off_huff + (j + 1) * D] = np.frombuffer(desc, np.uint8)
+        self.n_huff = j + 1
+
+    def huff_args(self, h_in: int, d_in: int, coef: int, status: int, status_cap: int) -> dict:
+        """The argument dict of kdl._C.jpeg_huff_decode / jpeg_dc_scan (addresses as ints)."""
+        return dict(desc=d_in + self.off_huff, h_desc=h_in + self.off_huff, stage=d_in, stage_cap=self.nbytes, coef=coef,
+                    coef_cap=self.ncoef, status=status, status_cap=status_cap, n=self.n_huff)
 
     def coef(self, hin: np.ndarray, k: int, ncoef: int) -> np.ndarray:
         """The int16 coefficient buffer of slot ``k`` inside the uint8 staging array ``hin``."""
@@ -99,9 +140,12 @@ class CallLayout:
         hin[self.off_qt + j * 512: self.off_qt + (j + 1) * 512].view(np.uint16)[:] = header.qt.reshape(-1)
         self.n_desc = j + 1
 
-    def args(self, h_in: int, d_in: int, planes: int, plane_cap: int, out: int, out_rows: int, OH: int, OW: int) -> dict:
-        """The argument dict of kdl._C.jpeg_idct_u8 / jpeg_sample_rgb_u8 (addresses as ints)."""
-        return dict(desc=d_in, h_desc=h_in, qt=d_in + self.off_qt, coef=d_in + self.off_coef, planes=planes, out=out,
+    def args(self, h_in: int, d_in: int, planes: int, plane_cap: int, out: int, out_rows: int, OH: int, OW: int,
+             coef: int | None = None) -> dict:
+        """The argument dict of kdl._C.jpeg_idct_u8 / jpeg_sample_rgb_u8 (addresses as ints); ``coef``:
+        the device coefficient buffer of the second form."""
+        return dict(desc=d_in, h_desc=h_in, qt=d_in + self.off_qt, coef=d_in + self.off_coef if coef is None else coef,
+                    planes=planes, out=out,
                     coef_cap=self.ncoef, plane_cap=plane_cap, qt_cap=self.n_desc * 256, n=self.n_desc, n_wg=self.n_wg,
                     out_rows=out_rows, OH=OH, OW=OW)
 
@@ -110,8 +154,11 @@ class BytesRunner:
     """The ``serving_bytes`` signature: decode + resize (GPU when the servable has one), then the
     ``serving_uint8`` runner's batcher and executors."""
 
-    def __init__(self, sig, inner, devices: list[int], spec: ResizeSpec | None = None):
+    def __init__(self, sig, inner, devices: list[int], spec: ResizeSpec | None = None, entropy: str = "host"):
+        if entropy not in ("host", "gpu"):
+            raise ValueError(f"jpeg entropy decode {entropy!r}: expected 'host' or 'gpu'")
         self.sig, self.inner = sig, inner
+        self.entropy = entropy if devices else "host"       # CPU servers decode on the host
         self.source = inner.source
         self.S = inner.source.input_size
         self.spec = spec if spec is not None else getattr(inner.source, "preprocess", NEAREST_SPEC)
@@ -156,11 +203,13 @@ class BytesRunner:
         METRICS.inc("kdl_jpeg_decoded_total", path="pil")
         return px
 
-    def _parse_all(self, plan, buffers) -> None:
+    def _parse_all(self, plan, buffers, where: str = "host") -> None:
         """Entropy-decode every JPEG of ``plan`` into its int16 buffer; a file that turns out to be
         outside the decoder after its frame header (e.g. several scans) falls back to PIL."""
         rt = _lib.rt()
         jobs = [(i, p) for i, p in enumerate(plan) if p[1] is not None]
+        if jobs:                    # counted as work done, whether or not a file then turns out malformed
+            METRICS.inc("kdl_jpeg_entropy_total", len(jobs), where=where)
         t0 = time.perf_counter()
 
         def one(job):
@@ -173,6 +222,68 @@ class BytesRunner:
             p[1] = hd if st == rt.JPEG_OK else None
         if jobs:
             METRICS.observe("kdl_stage_ms", (time.perf_counter() - t0) * 1e3, stage="jpeg_entropy")
+
+    def _prepare_all(self, plan, lay, hin, slot) -> dict | None:
+        """Stage tables and scan of every JPEG of ``plan`` for the device decode -> {image: info}, or
+        None when a file has restart intervals: the request then is the host decoder's. As in
+        ``_parse_all`` a file outside the decoder falls back to PIL and a malformed header is rejected."""
+        rt = _lib.rt()
+        t0 = time.perf_counter()
+        infos, ok = {}, True
+        for i, k in slot.items():
+            st, hd, info = rt.jpeg_scan_prepare(plan[i][0], lay.prep(hin, k), MAX_PIXELS)
+            if st == rt.JPEG_MALFORMED:
+                raise _bad(f"image {i}: malformed JPEG ({hd.why})")
+            if st != rt.JPEG_OK:
+                plan[i][1] = None
+                continue
+            plan[i][1], infos[i] = hd, info
+            ok = ok and info.device_ok
+        METRICS.observe("kdl_stage_ms", (time.perf_counter() - t0) * 1e3, stage="jpeg_prepare")
+        return infos if ok else None
+
+    def _stage(self, c, plan, slot, extra: int, n_out: int, host: bool, where: str):
+        """Lay out and fill the request's staging (``extra`` bytes of room behind it): the scans for
+        the device decode when the runner has it and every file allows it, else the host-decoded
+        coefficients -> (layout, {image: JpegHuffInfo} | None, offset of the extra room)."""
+        ncoefs = [plan[i][1].ncoef for i in slot]
+        c.n_status = 0
+        if self.entropy == "gpu" and not host and slot:
+            rt = _lib.rt()
+            lay = CallLayout(ncoefs, [rt.jpeg_prepare_bound(len(plan[i][0])) for i in slot])
+            off = _align(lay.nbytes, 256)
+            c.grow(off + extra, n_out)
+            infos = self._prepare_all(plan, lay, c.h_in.numpy(), slot)
+            if infos is not None:
+                c.grow_coef(max(lay.ncoef, 1), len(slot))
+                return lay, infos, off
+            for i in slot:                              # the host decoder starts from the probed headers
+                plan[i][1] = rt.jpeg_probe(plan[i][0], 1 << 62)[1]
+        lay = CallLayout(ncoefs)
+        off = _align(lay.nbytes, 256)
+        c.grow(max(off + extra, 1), n_out)
+        hin = c.h_in.numpy()
+        self._parse_all(plan, {i: lay.coef(hin, k, plan[i][1].ncoef) for i, k in slot.items()}, where)
+        return lay, None, off
+
+    def _entropy_on(self, c, lay, stream: int) -> int | None:
+        """Launch the device entropy decode of a second-form layout (inside the stream context, after
+        the staging copy) -> the coefficient buffer's address for ``CallLayout.args``."""
+        if not lay.device_entropy or not lay.n_huff:
+            return None
+        C = _lib.lib()
+        ha = lay.huff_args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_coef), _lib.ptr(c.d_status), c.cap_status)
+        C.jpeg_huff_decode(ha, stream)
+        C.jpeg_dc_scan(ha, stream)
+        c.n_status = lay.n_huff
+        c.h_status[:2 * lay.n_huff].copy_(c.d_status[:2 * lay.n_huff], non_blocking=True)
+        METRICS.inc("kdl_jpeg_entropy_total", lay.n_huff, where="gpu")
+        return _lib.ptr(c.d_coef)
+
+    @staticmethod
+    def _rejected(c) -> bool:
+        """After the stream's synchronise: did the device decoder set an image's error word?"""
+        return bool(c.n_status) and bool(c.h_status[:2 * c.n_status:2].any())
 
     # ------------------------------------------------------------------ CPU
     def _decode_cpu(self, plan) -> np.ndarray:
@@ -196,21 +307,23 @@ class BytesRunner:
         return out
 
     # ------------------------------------------------------------------ GPU
-    def _decode_on(self, c, plan) -> int:
+    def _decode_on(self, c, plan, host: bool = False) -> int:
         """Decode + resize the request into ``c.d_out`` ([n, S, S, 3]) on the context's stream;
-        returns the output's element count. The caller synchronises the stream."""
+        returns the output's element count. The caller synchronises the stream and, under
+        ``entropy="gpu"``, asks ``_rejected``: a set error word means this call again with ``host``
+        (the retry through the host decoder) on a fresh plan."""
         C = _lib.lib()
         S, n = self.S, len(plan)
         slot = {i: k for k, i in enumerate(i for i, p in enumerate(plan) if p[1] is not None)}
-        lay = CallLayout([plan[i][1].ncoef for i in slot])
+        where = "retry" if host and self.entropy == "gpu" else "host"
         METRICS.inc("kdl_resize_total", filter=self.spec.filter)
         if self.resizer.filtered:
-            return self._resample_on(c, plan, slot, lay)
-        n_in, n_out = lay.nbytes, n * S * S * 3
-        c.grow(max(n_in, 1), n_out)
+            return self._resample_on(c, plan, slot, host, where)
+        n_out = n * S * S * 3
+        lay, infos, _ = self._stage(c, plan, slot, 0, n_out, host, where)
+        n_in = lay.nbytes
         c.grow_planes(max(lay.ncoef, 1))                # sample planes: one byte per coefficient
         hin = c.h_in.numpy()
-        self._parse_all(plan, {i: lay.coef(hin, k, plan[i][1].ncoef) for i, k in slot.items()})
         # every host step that can fail comes before the first launch: the stream never runs a
         # request that was rejected half way
         pil = {i: self._pil(i, p[0]) for i, p in enumerate(plan) if p[1] is None}
@@ -222,12 +335,14 @@ class BytesRunner:
             ys, xs = self.resizer._tables(hd.H, hd.W, c.dev)
             keep += [ys, xs]
             lay.add(hin, k, hd, i, ys, xs)
+            if infos is not None:
+                lay.add_huff(hin, k, hd, infos[i])
         stream = int(c.stream.cuda_stream)
         with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
             if lay.n_desc:
                 c.d_in[:n_in].copy_(c.h_in[:n_in], non_blocking=True)
                 args = lay.args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_planes), c.cap_planes,
-                                _lib.ptr(c.d_out), n, S, S)
+                                _lib.ptr(c.d_out), n, S, S, coef=self._entropy_on(c, lay, stream))
                 C.jpeg_idct_u8(args, stream)
                 C.jpeg_sample_rgb_u8(args, stream)
                 METRICS.inc("kdl_jpeg_decoded_total", lay.n_desc, path="gpu")
@@ -240,18 +355,17 @@ class BytesRunner:
         c.keep = keep
         return n_out
 
-    def _resample_on(self, c, plan, slot, lay) -> int:
+    def _resample_on(self, c, plan, slot, host: bool, where: str) -> int:
         """``_decode_on`` of a filtered spec: jpeg_idct_u8, then the horizontal pass straight from the
         sample planes (resample_h_u8, JPEG kind; raw kind for what PIL decoded), then one vertical pass
         over all images of the request. Staging: [the CallLayout | one ResampleDesc per image]."""
         C, D = _lib.lib(), _lib.rt().RESAMPLE_DESC_BYTES
         S, n = self.S, len(plan)
-        off_desc = _align(lay.nbytes, 256)
-        n_in, n_out = off_desc + n * D, n * S * S * 3
-        c.grow(n_in, n_out)
+        n_out = n * S * S * 3
+        lay, infos, off_desc = self._stage(c, plan, slot, n * D, n_out, host, where)
+        n_in = off_desc + n * D
         c.grow_planes(max(lay.ncoef, 1))
         hin = c.h_in.numpy()
-        self._parse_all(plan, {i: lay.coef(hin, k, plan[i][1].ncoef) for i, k in slot.items()})
         # every host step that can fail comes before the first launch (see _decode_on)
         pil = {i: self._pil(i, p[0]) for i, p in enumerate(plan) if p[1] is None}
         keep, descs, raw, tmp = [], [], [], 0       # JPEG descriptors first, then the PIL-decoded images
@@ -263,6 +377,8 @@ class BytesRunner:
             keep.append(t)
             descs.append(t.desc(lay.n_desc, tmp, i))
             lay.add(hin, k, hd, i, t.dev[2], t.dev[0])      # the nearest tables of the descriptor: unused here
+            if infos is not None:
+                lay.add_huff(hin, k, hd, infos[i])
             tmp += t.tmp_bytes
         for i, px in pil.items():
             t = self.resizer._tables(px.shape[0], px.shape[1], c.dev)
@@ -281,7 +397,7 @@ class BytesRunner:
                       tmp=_lib.ptr(c.d_tmp), tmp_cap=c.cap_tmp, out=_lib.ptr(c.d_out), out_rows=n, OH=S, OW=S, n=n)
             if nj:
                 C.jpeg_idct_u8(lay.args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_planes), c.cap_planes,
-                                        _lib.ptr(c.d_out), n, S, S), stream)
+                                        _lib.ptr(c.d_out), n, S, S, coef=self._entropy_on(c, lay, stream)), stream)
                 C.resample_h_u8({**rs, "n": nj}, 1, stream)
                 METRICS.inc("kdl_jpeg_decoded_total", nj, path="gpu")
             if n > nj:
@@ -304,6 +420,11 @@ class BytesRunner:
             with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
                 c.h_out[:n_out].copy_(c.d_out[:n_out], non_blocking=True)
             c.stream.synchronize()
+            if self._rejected(c):           # the device decoder refused a scan: the host decoder's answer counts
+                n_out = self._decode_on(c, self._probe(images), host=True)
+                with torch.cuda.device(c.dev), torch.cuda.stream(c.stream):
+                    c.h_out[:n_out].copy_(c.d_out[:n_out], non_blocking=True)
+                c.stream.synchronize()
             return c.h_out[:n_out].numpy().reshape(len(plan), self.S, self.S, 3).copy()
         finally:
             self._release(c)
@@ -319,6 +440,9 @@ class BytesRunner:
         try:                           # decoded straight into device memory: no host round trip
             self._decode_on(c, plan)
             c.stream.synchronize()
+            if self._rejected(c):
+                self._decode_on(c, self._probe(images), host=True)
+                c.stream.synchronize()
             return self.inner.predict_device(_lib.ptr(c.d_out), n, deadline_us)
         finally:
             self._release(c)

@@ -109,6 +109,22 @@ class _Ctx:
         # intermediate of the filtered resize (csrc/kernels/resample.hip): the horizontal pass's rows
         self.cap_tmp = 0
         self.d_tmp: torch.Tensor | None = None
+        # device entropy decode (csrc/kernels/jpeg_huff.hip): the coefficient planes never leave the
+        # device; per image an error word and a round count come back (n_status images in flight)
+        self.cap_coef = 0
+        self.d_coef: torch.Tensor | None = None
+        self.cap_status = self.n_status = 0
+        self.d_status: torch.Tensor | None = None
+        self.h_status: torch.Tensor | None = None
+
+    def grow_coef(self, n: int, images: int) -> None:
+        if n > self.cap_coef:
+            self.cap_coef = max(n, 2 * self.cap_coef)
+            self.d_coef = torch.empty(self.cap_coef, dtype=torch.int16, device=self.dev)
+        if 2 * images > self.cap_status:
+            self.cap_status = max(2 * images, 2 * self.cap_status)
+            self.d_status = torch.empty(self.cap_status, dtype=torch.int32, device=self.dev)
+            self.h_status = torch.empty(self.cap_status, dtype=torch.int32).pin_memory()
 
     def grow_tmp(self, n: int) -> None:
         if n > self.cap_tmp:

@@ -3,12 +3,16 @@
 
   python tools/jpeg_bench.py --size 534x400                  # host: jpeg_parse vs Pillow, one core
   python tools/jpeg_bench.py --size 534x400 --kernels --images 32   # MI355X: the two HIP kernels
+  python tools/jpeg_bench.py --size 534x400 --kernels --images 32 --entropy gpu   # + the device entropy decode
 
 The image is tests/data/pants.png scaled to --size (HxW) and encoded as a quality-90 4:2:0 JPEG.
 Host: median microseconds per image of the entropy decode (kdl._rt.jpeg_parse into a reused
 buffer) against Pillow's full decode (Image.open().convert("RGB")) on the same core. --kernels:
 --images copies decoded in one call, device-event times of jpeg_idct_u8 and jpeg_sample_rgb_u8
 (-> 299x299) and the bytes each has to move over that time; needs a GPU, no fallback.
+--entropy gpu adds the device entropy decode (profiles/jpeg_entropy_gpu.txt): on the host
+jpeg_scan_prepare beside jpeg_parse, on the GPU jpeg_huff_decode + jpeg_dc_scan in front of
+jpeg_idct_u8 in the same loop, with the fixed-point rounds the decode took.
 """
 from __future__ import annotations
 
@@ -54,6 +58,70 @@ def host(data: bytes, iters: int) -> dict:
     pil = _median_us(lambda: Image.open(io.BytesIO(data)).convert("RGB"), iters)
     return {"file_bytes": len(data), "jpeg_parse_us": round(parse, 1), "pillow_decode_us": round(pil, 1),
             "parse_over_pillow": round(parse / pil, 3)}
+
+
+def host_prepare(data: bytes, iters: int) -> dict:
+    """jpeg_scan_prepare -- all the host does for the device entropy decode -- into a reused buffer."""
+    from kdl.ops import _lib
+    rt = _lib.rt()
+    out = np.empty(rt.jpeg_prepare_bound(len(data)), np.uint8)
+    st, hd, info = rt.jpeg_scan_prepare(data, out)
+    assert st == rt.JPEG_OK and info.device_ok, hd.why
+    prep = _median_us(lambda: rt.jpeg_scan_prepare(data, out), iters)
+    return {"jpeg_scan_prepare_us": round(prep, 1), "staged_bytes": info.nbytes, "coefficient_bytes": 2 * hd.ncoef}
+
+
+def entropy_kernels(data: bytes, n: int, iters: int) -> dict:
+    """Device-event times of jpeg_huff_decode, jpeg_dc_scan and jpeg_idct_u8 over ``n`` copies."""
+    import torch
+
+    from kdl.ops import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("--kernels needs a GPU")
+    from kdl.serving.jpeg import CallLayout
+    rt, C = _lib.rt(), _lib.lib()
+    st, hd = rt.jpeg_probe(data)
+    assert st == rt.JPEG_OK, hd.why
+    lay = CallLayout([hd.ncoef] * n, [rt.jpeg_prepare_bound(len(data))] * n)
+    hin = np.zeros(lay.nbytes, np.uint8)
+    idx = torch.zeros(1, dtype=torch.int32, device="cuda")      # jpeg_idct_u8 reads no resize table
+    for k in range(n):
+        st, h, info = rt.jpeg_scan_prepare(data, lay.prep(hin, k))
+        assert st == rt.JPEG_OK and info.device_ok
+        lay.add(hin, k, h, k, idx, idx)
+        lay.add_huff(hin, k, h, info)
+    d_in = torch.from_numpy(hin).cuda()
+    coef = torch.empty(lay.ncoef, dtype=torch.int16, device="cuda")
+    planes = torch.empty(lay.ncoef, dtype=torch.uint8, device="cuda")
+    out = torch.empty((n, 1, 1, 3), dtype=torch.uint8, device="cuda")
+    status = torch.zeros(2 * n, dtype=torch.int32, device="cuda")
+    ha = lay.huff_args(hin.ctypes.data, d_in.data_ptr(), coef.data_ptr(), status.data_ptr(), 2 * n)
+    ia = lay.args(hin.ctypes.data, d_in.data_ptr(), planes.data_ptr(), lay.ncoef, out.data_ptr(), n, 1, 1,
+                  coef=coef.data_ptr())
+    s = torch.cuda.current_stream().cuda_stream
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(iters)]
+
+    def once(e=None):
+        for i, fn in enumerate((lambda: C.jpeg_huff_decode(ha, s), lambda: C.jpeg_dc_scan(ha, s),
+                                lambda: C.jpeg_idct_u8(ia, s))):
+            if e:
+                e[i].record()
+            fn()
+        if e:
+            e[3].record()
+    for _ in range(10):
+        once()
+    torch.cuda.synchronize()
+    for e in ev:
+        once(e)
+    torch.cuda.synchronize()
+    st = status.cpu().numpy().reshape(n, 2)
+    assert not st[:, 0].any(), "the device decoder rejected the benchmark's own file"
+    us = [round(statistics.median(e[i].elapsed_time(e[i + 1]) for e in ev) * 1e3, 1) for i in range(3)]
+    return {"images": n, "sub_bits": rt.JPEG_HUFF_SUB_BITS, "chunk": rt.JPEG_HUFF_CHUNK,
+            "chunks_per_image": -(-info.nbits // (rt.JPEG_HUFF_SUB_BITS * rt.JPEG_HUFF_CHUNK)),
+            "most_rounds_of_a_chunk": int(st[:, 1].max()), "huff_decode_us": us[0], "dc_scan_us": us[1],
+            "idct_us": us[2], "entropy_us_per_image": round((us[0] + us[1]) / n, 2)}
 
 
 def kernels(data: bytes, n: int, iters: int, S: int = 299) -> dict:
@@ -108,12 +176,19 @@ def main(argv=None) -> int:
     ap.add_argument("--images", type=int, default=32)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--entropy", choices=["host", "gpu"], default="host",
+                    help="gpu: also time jpeg_scan_prepare and, with --kernels, the device entropy decode")
     a = ap.parse_args(argv)
     H, W = map(int, a.size.split("x"))
     data = make_file(H, W)
     res = {"size": a.size, **host(data, a.iters)}
+    if a.entropy == "gpu":
+        res.update(host_prepare(data, a.iters))
+        res["parse_over_prepare"] = round(res["jpeg_parse_us"] / res["jpeg_scan_prepare_us"], 1)
     if a.kernels:
         res["kernels"] = kernels(data, a.images, a.iters)
+        if a.entropy == "gpu":
+            res["entropy_kernels"] = entropy_kernels(data, a.images, a.iters)
     print(json.dumps(res), flush=True)
     return 0
 

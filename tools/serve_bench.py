@@ -104,6 +104,7 @@ def _launch_procs(a):
     if a.executors_per_gpu:
         cmd.append(f"--executors_per_gpu={a.executors_per_gpu}")
     cmd.append(f"--grpc_frontend={a.frontend}")
+    cmd.append(f"--jpeg_entropy={a.entropy}")
     p = subprocess.Popen(cmd, cwd=root, env=dict(os.environ, PYTHONPATH=root), stdout=subprocess.DEVNULL,
                          stderr=subprocess.DEVNULL, start_new_session=True)
     target = f"127.0.0.1:{port}"
@@ -136,6 +137,9 @@ def main(argv=None) -> int:
                          "serving_bytes, its decoded pixels for serving_image (random: seeded uniform pixels)")
     ap.add_argument("--image-size", default="534x400",
                     help="serving_image: HxW of the raw uint8 images the clients send (resized on the server)")
+    ap.add_argument("--entropy", choices=["host", "gpu"], default=os.environ.get("KDL_JPEG_ENTROPY") or "host",
+                    help="serving_bytes: where the JPEG scans are Huffman-decoded (the server's --jpeg_entropy; "
+                         "default: env KDL_JPEG_ENTROPY, else host)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--timeout-us", type=int, default=1000)
@@ -199,7 +203,7 @@ def main(argv=None) -> int:
         cfg = ServerConfig(port=0, rest_api_port=0, model_base_path=base, device=a.device, gpus=a.gpus,
                            executors_per_gpu=a.executors_per_gpu,
                            host="127.0.0.1", file_system_poll_wait_seconds=0, grpc_max_threads=max(64, a.clients * 2),
-                           f32_exact_u8=not a.no_f32_exact, grpc_frontend=a.frontend,
+                           f32_exact_u8=not a.no_f32_exact, grpc_frontend=a.frontend, jpeg_entropy=a.entropy,
                            batching=BatchingParams(max_batch_size=a.max_batch, batch_timeout_micros=a.timeout_us,
                                                    allowed_batch_sizes=sizes, eager_when_idle=not a.no_eager))
         srv = ModelServer(cfg).start(block_until_loaded=True)
@@ -270,6 +274,10 @@ def main(argv=None) -> int:
             res["jpeg_decoded"] = {k.split("=")[1].rstrip("}"): v for k, v in snap["counters"].items()
                                    if k.startswith("kdl_jpeg_decoded_total")}
             res["jpeg_entropy_ms"] = snap["histograms"].get("kdl_stage_ms{stage=jpeg_entropy}")
+            res["entropy"] = a.entropy
+            res["jpeg_entropy_where"] = {k.split("=")[1].rstrip("}"): v for k, v in snap["counters"].items()
+                                         if k.startswith("kdl_jpeg_entropy_total")}
+            res["jpeg_prepare_ms"] = snap["histograms"].get("kdl_stage_ms{stage=jpeg_prepare}")
             res["jpeg_threads"] = int(os.environ.get("KDL_JPEG_THREADS", "4"))
         run = getattr(run, "inner", run)      # serving_image / serving_bytes: the serving_uint8 runner behind
         st = run.batcher.stats()
