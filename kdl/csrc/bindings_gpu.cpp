@@ -221,6 +221,7 @@ JpegHuffArgs jpeg_huff_args(const py::dict& d) {
   a.stage = P<const uint8_t>(d, "stage"); a.coef = P<int16_t>(d, "coef"); a.status = P<uint32_t>(d, "status");
   a.stage_cap = U64(d, "stage_cap"); a.coef_cap = U64(d, "coef_cap");
   a.status_cap = I(d, "status_cap"); a.n = I(d, "n");
+  a.h_stage = P<const uint8_t>(d, "h_stage");
   return a;
 }
 ResampleArgs resample_args(const py::dict& d) {
@@ -390,6 +391,17 @@ PYBIND11_MODULE(_C, m) {
     const auto a = jpeg_huff_args(d);
     py::gil_scoped_release nogil;
     chk(jpeg_dc_scan(a, S(s)), "jpeg_dc_scan");
+  });
+  // the same for files with restart intervals; h_stage is the HOST address of the staging's copy
+  m.def("jpeg_huff_rst_decode", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_huff_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_huff_rst_decode(a, S(s)), "jpeg_huff_rst_decode");
+  });
+  m.def("jpeg_dc_rst_scan", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_huff_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_dc_rst_scan(a, S(s)), "jpeg_dc_rst_scan");
   });
   m.attr("JPEG_HUFF_SUB_BITS") = int(kJpegHuffSubBits);
   m.attr("JPEG_HUFF_CHUNK") = int(kJpegHuffChunk);

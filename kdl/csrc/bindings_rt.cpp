@@ -515,10 +515,18 @@ PYBIND11_MODULE(_rt, m) {
       .def_readonly("nbytes", &JpegHuffInfo::nbytes)
       .def_readonly("nb", &JpegHuffInfo::nb)
       .def_readonly("device_ok", &JpegHuffInfo::device_ok)
+      .def_readonly("restart_ok", &JpegHuffInfo::restart_ok)
+      .def_readonly("ri", &JpegHuffInfo::ri)
+      .def_readonly("nint", &JpegHuffInfo::nint)
+      .def_readonly("ngroup", &JpegHuffInfo::ngroup)
+      .def_readonly("int_off", &JpegHuffInfo::int_off)
+      .def_readonly("grp_off", &JpegHuffInfo::grp_off)
       .def_property_readonly("comp", [](const JpegHuffInfo& i) {
         return std::vector<int>(i.comp, i.comp + (i.nb > 0 && i.nb <= 8 ? i.nb : 0));
       });
-  m.def("jpeg_prepare_bound", [](uint64_t n) { return jpeg_prepare_bound(n); });
+  // `nint`: the restart intervals the probed header announces, ceil(MCUs / restart); 0 without DRI
+  m.def("jpeg_prepare_bound", [](uint64_t n, uint64_t nint) { return jpeg_prepare_bound(n, nint); }, py::arg("n"),
+        py::arg("nint") = uint64_t(0));
   // `out`: a writable, 4-byte aligned buffer of at least jpeg_prepare_bound(len(data)) bytes
   m.def("jpeg_scan_prepare", [](py::bytes data, py::buffer out, uint64_t max_pixels) {
     std::string_view sv = data;
@@ -542,6 +550,17 @@ PYBIND11_MODULE(_rt, m) {
     jpeg_huff_fill_desc(h, info, stage_base, coef_base, &d);
     return py::bytes(reinterpret_cast<const char*>(&d), sizeof(d));
   }, py::arg("header"), py::arg("info"), py::arg("stage_base"), py::arg("coef_base"));
+  // would the launchers take this descriptor? `stage`: the call's staging, `coef_cap` in int16
+  m.def("jpeg_huff_desc_valid", [](py::bytes desc, py::buffer stage, uint64_t coef_cap) {
+    std::string_view dv = desc;
+    if (dv.size() != sizeof(JpegHuffDesc)) throw std::invalid_argument("jpeg_huff_desc_valid: not a JpegHuffDesc");
+    JpegHuffDesc d;
+    std::memcpy(&d, dv.data(), sizeof(d));
+    py::buffer_info si = stage.request();
+    if (reinterpret_cast<uintptr_t>(si.ptr) % 4) throw std::invalid_argument("jpeg_huff_desc_valid: unaligned buffer");
+    return jpeg_huff_desc_valid(d, uint64_t(si.size) * uint64_t(si.itemsize), coef_cap,
+                                static_cast<const uint8_t*>(si.ptr));
+  }, py::arg("desc"), py::arg("stage"), py::arg("coef_cap"));
   // the kernels' procedure on the host -> (error word, most rounds of a chunk, indices out of bounds)
   m.def("jpeg_huff_cpu", [](py::bytes desc, py::buffer stage, py::buffer coef) {
     std::string_view dv = desc;

@@ -351,9 +351,16 @@ struct JpegHuffArgs {
   uint64_t stage_cap, coef_cap;
   int status_cap;              // uint32 of status: at least 2 * n
   int n;
+  const uint8_t* h_stage;      // the restart launchers: the host's copy of stage (its tables are checked, see below)
 };
 hipError_t jpeg_huff_decode(const JpegHuffArgs& a, hipStream_t s);
 hipError_t jpeg_dc_scan(const JpegHuffArgs& a, hipStream_t s);
+// The same for files with restart intervals, whose descriptors carry an interval and a group table
+// (runtime/jpeg_huff.h): one workgroup per (image, group of intervals), each from the known entry
+// state of its intervals, and DC sums that start again at every interval. The workgroups of an
+// image share its two status words: jpeg_huff_rst_decode clears them on the stream first.
+hipError_t jpeg_huff_rst_decode(const JpegHuffArgs& a, hipStream_t s);
+hipError_t jpeg_dc_rst_scan(const JpegHuffArgs& a, hipStream_t s);
 
 // Pillow's filtered resize + crop (kernels/resample.hip): a table-driven separable convolution
 // over uint8 RGB. resample_h_u8 runs the horizontal pass of n images into the intermediate

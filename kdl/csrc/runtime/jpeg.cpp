@@ -4,6 +4,7 @@
 #include "runtime/jpeg_huff.h"
 
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace kdl {
@@ -364,6 +365,13 @@ struct Parser {
     }
     uint32_t* sw = w + 2 * ns * kJpegHuffTabWords;
     const uint64_t room = (prep_cap - tabs) / 4;       // words
+    const int mx = h->comp[0].bw / h->comp[0].h, my = h->comp[0].bh / h->comp[0].v;
+    info->nb = 0;
+    for (int c = 0; c < ns; ++c)
+      for (int i = 0; i < h->comp[c].h * h->comp[c].v; ++i) info->comp[info->nb++] = (uint8_t)c;
+    info->nblocks = (uint32_t)((uint64_t)mx * my * info->nb);
+    info->scan_off = (uint32_t)tabs;
+    if (h->restart > 0) return prepare_restart(sw, room, tabs, pos, (uint64_t)mx * my);
     uint64_t nbytes = 0;
     uint32_t acc = 0;
     const uint8_t* p = data + pos;
@@ -393,16 +401,99 @@ struct Parser {
     if (nwords + 2 > room) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
     if (nbytes & 3) sw[nwords++] = acc << (8 * (4 - (nbytes & 3)));
     sw[nwords++] = 0;                                    // the zero bits behind the data
-    const int mx = h->comp[0].bw / h->comp[0].h, my = h->comp[0].bh / h->comp[0].v;
-    info->nb = 0;
-    for (int c = 0; c < ns; ++c)
-      for (int i = 0; i < h->comp[c].h * h->comp[c].v; ++i) info->comp[info->nb++] = (uint8_t)c;
     info->nbits = (uint32_t)(nbytes * 8);
-    info->scan_off = (uint32_t)tabs;
     info->scan_bytes = (uint32_t)(nwords * 4);
     info->nbytes = (uint32_t)(tabs + nwords * 4);
-    info->nblocks = (uint32_t)((uint64_t)mx * my * info->nb);
-    info->device_ok = h->restart == 0 && nbytes < (1u << 27);
+    info->device_ok = nbytes < (1u << 27);
+    return JPEG_OK;
+  }
+
+  // The scan of a file with restart intervals: the same unstuffing, carried on through the RSTm
+  // markers. Every interval starts on a word boundary (the padding bits in front of a marker are
+  // dropped, as the host decoder drops them) and is followed by one zero word; behind the scan come
+  // the interval table and the groups of the kernel (jpeg_huff.h). Markers that are not exactly
+  // RST0, RST1, ... in order and in number, or an empty interval, leave restart_ok false: what such
+  // a file means is for the host decoder to say.
+  JpegStatus prepare_restart(uint32_t* sw, uint64_t room, uint64_t tabs, size_t pos, uint64_t mcus) {
+    const uint64_t ri = (uint64_t)h->restart, expect = (mcus + ri - 1) / ri;
+    std::vector<JpegHuffInterval> iv;
+    uint64_t nwords = 0, nbytes = 0, total = 0, first = 0, nmark = 0;
+    uint32_t acc = 0;
+    bool ok = true;
+    auto close = [&]() {                                 // false: out of room
+      if (nwords + 2 > room) return false;
+      if (nbytes & 3) sw[nwords++] = acc << (8 * (4 - (nbytes & 3)));
+      sw[nwords++] = 0;                                  // the zero bits behind the interval
+      if (nbytes == 0) ok = false;
+      iv.push_back(JpegHuffInterval{(uint32_t)first, (uint32_t)(nbytes * 8)});
+      total += nbytes;
+      first = nwords;
+      nbytes = 0;
+      acc = 0;
+      return true;
+    };
+    const uint8_t* p = data + pos;
+    const uint8_t* end = data + n;
+    while (p < end && ok) {
+      uint32_t b = *p;
+      if (b != 0xFF) {
+        ++p;
+      } else if (p + 1 >= end) {
+        break;
+      } else if (p[1] == 0x00) {
+        p += 2;
+      } else if (p[1] == 0xFF) {
+        ++p;
+        continue;
+      } else if (p[1] >= 0xD0 && p[1] <= 0xD7) {
+        if (p[1] != 0xD0 + (nmark & 7) || nmark + 1 >= expect) ok = false;     // misnumbered, or one too many
+        if (!close()) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+        ++nmark;
+        p += 2;
+        continue;
+      } else {
+        break;
+      }
+      acc = (acc << 8) | b;
+      if ((++nbytes & 3) == 0) {
+        if (nwords + 1 > room) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+        sw[nwords++] = acc;
+        acc = 0;
+      }
+    }
+    if (ok && !close()) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+    info->scan_bytes = (uint32_t)(nwords * 4);
+    info->nbytes = (uint32_t)(tabs + nwords * 4);
+    info->nbits = (uint32_t)(total * 8);
+    info->ri = (uint32_t)ri;
+    if (!ok || iv.size() != expect || total >= (1u << 27)) {
+      info->nbits = 0;
+      return JPEG_OK;
+    }
+    std::vector<JpegHuffGroup> gr;                       // greedy, by the rule of jpeg_huff_group_fits
+    uint64_t nsub = 0;
+    for (uint32_t j = 0; j < (uint32_t)iv.size(); ++j) {
+      const uint64_t s = jpeg_huff_nsub(iv[j].bits), wend = (uint64_t)iv[j].word + jpeg_huff_interval_words(iv[j].bits);
+      if (!gr.empty() && jpeg_huff_group_fits(nsub + s, wend - iv[gr.back().first].word)) {
+        ++gr.back().count;
+        nsub += s;
+      } else {
+        gr.push_back(JpegHuffGroup{j, 1});
+        nsub = s;
+      }
+    }
+    const uint64_t need = 2 * (uint64_t)iv.size() + 2 * (uint64_t)gr.size();
+    if (nwords + need > room) return fail(h, JPEG_MALFORMED, "prepare buffer too small");
+    info->int_off = (uint32_t)(tabs + nwords * 4);
+    std::memcpy(sw + nwords, iv.data(), iv.size() * sizeof(JpegHuffInterval));
+    nwords += 2 * iv.size();
+    info->grp_off = (uint32_t)(tabs + nwords * 4);
+    std::memcpy(sw + nwords, gr.data(), gr.size() * sizeof(JpegHuffGroup));
+    nwords += 2 * gr.size();
+    info->nint = (uint32_t)iv.size();
+    info->ngroup = (uint32_t)gr.size();
+    info->nbytes = (uint32_t)(tabs + nwords * 4);
+    info->restart_ok = true;
     return JPEG_OK;
   }
 
@@ -529,6 +620,11 @@ void jpeg_huff_fill_desc(const JpegHeader& h, const JpegHuffInfo& info, uint64_t
   d->ncomp = h.ncomp; d->nb = info.nb;
   d->mx = h.comp[0].h ? h.comp[0].bw / h.comp[0].h : 0;
   d->my = h.comp[0].v ? h.comp[0].bh / h.comp[0].v : 0;
+  if (info.restart_ok) {       // the tables of jpeg_huff_rst_decode; zero for every other file
+    d->ri = info.ri; d->nint = info.nint; d->ngroup = info.ngroup;
+    d->int_off = (uint32_t)(stage_base + info.int_off);
+    d->grp_off = (uint32_t)(stage_base + info.grp_off);
+  }
 }
 
 namespace {
@@ -565,65 +661,61 @@ struct EmuMem {
 
 }  // namespace
 
-uint64_t jpeg_huff_cpu(const JpegHuffDesc& d, const uint8_t* stage, uint64_t stage_cap, int16_t* coef,
-                       uint64_t coef_cap, uint32_t* err, uint32_t* rounds) {
-  *err = 1;
-  *rounds = 0;
-  if (!jpeg_huff_desc_valid(d, stage_cap, coef_cap) || reinterpret_cast<uintptr_t>(stage) % 4) return 0;
-  *err = 0;
-  uint64_t bad = 0;
-  constexpr int T = kJpegHuffChunk;
-  constexpr uint32_t S = kJpegHuffSubBits;
-  for (int c = 0; c < d.ncomp; ++c) {                                  // step 8
-    const uint64_t nc = (uint64_t)d.bw[c] * d.bh[c] * 64;
-    for (uint64_t i = 0; i < nc; ++i) {
-      if (d.coef_off[c] + i >= coef_cap) { ++bad; break; }
-      coef[d.coef_off[c] + i] = 0;
-    }
+namespace {
+
+constexpr int kT = kJpegHuffChunk;
+
+// the state of the emulated workgroup
+struct Emu {
+  const JpegHuffDesc& d;
+  EmuMem m;
+  std::vector<uint32_t> lds;
+  const uint32_t* words;      // the image's scan
+  uint32_t nwords;
+  std::vector<JpegHuffLane> lane;
+  std::vector<JpegHuffState> ex, in, last;
+  std::vector<uint32_t> cnt, incl;
+  uint32_t* err;
+  uint32_t* rounds;
+  uint64_t* bad;
+
+  Emu(const JpegHuffDesc& d_, const uint8_t* stage, int16_t* coef, uint64_t coef_cap, uint32_t* err_, uint32_t* rounds_,
+      uint64_t* bad_)
+      : d(d_), m{nullptr, 0, {}, coef, coef_cap, bad_}, lds(kJpegHuffLdsWords),
+        words(reinterpret_cast<const uint32_t*>(stage + d_.scan_off)), nwords(d_.scan_bytes / 4), lane(kT), ex(kT),
+        in(kT), last(kT), cnt(kT), incl(kT), err(err_), rounds(rounds_), bad(bad_) {
+    m.lds = lds.data();
+    for (int t = 0; t < 6; ++t) m.tabs[t] = reinterpret_cast<const uint32_t*>(stage + d.tab_off[t]);
   }
-  const uint32_t* words = reinterpret_cast<const uint32_t*>(stage + d.scan_off);
-  const uint32_t nwords = d.scan_bytes / 4;
-  std::vector<uint32_t> lds(kJpegHuffLdsWords);
-  EmuMem m{lds.data(), 0, {}, coef, coef_cap, &bad};
-  for (int t = 0; t < 6; ++t) m.tabs[t] = reinterpret_cast<const uint32_t*>(stage + d.tab_off[t]);
-  const uint32_t nsub = (d.nbits + S - 1) / S;
-  const uint32_t nchunk = (nsub + T - 1) / T;
-  JpegHuffState entry{0, 0};
-  uint32_t base = 0;                                                   // blocks completed before the chunk
-  std::vector<JpegHuffState> ex(T), in(T), last(T);
-  std::vector<uint32_t> cnt(T), excl(T);
-  for (uint32_t ch = 0; ch < nchunk; ++ch) {
-    m.w0 = ch * (uint32_t)kJpegHuffChunkWords;
+
+  // One chunk staged from scan word w0 (words from ``w_end`` on read as zero), lane[] filled in:
+  // the cold pass, the rounds (at most ``bound``), the scan of the counts and the write pass.
+  // Leaves the exit states in ex[] and the inclusive sums of the blocks completed in incl[].
+  void chunk(uint32_t w0, uint32_t w_end, uint32_t bound) {
+    m.w0 = w0;
     for (uint32_t r = 0; r < (uint32_t)kJpegHuffStaged; ++r) {
       const uint32_t i = jpeg_huff_lds_index(r);
-      if (i >= (uint32_t)kJpegHuffLdsWords) { ++bad; continue; }
-      lds[i] = m.w0 + r < nwords ? words[m.w0 + r] : 0;
+      if (i >= (uint32_t)kJpegHuffLdsWords) { ++*bad; continue; }
+      const uint64_t w = (uint64_t)w0 + r;
+      if (w < w_end && w >= nwords) { ++*bad; continue; }
+      lds[i] = w < w_end ? words[w] : 0;
     }
-    auto end_of = [&](int i) {
-      const uint64_t e = ((uint64_t)ch * T + i + 1) * S;
-      return (uint32_t)(e < d.nbits ? e : d.nbits);
-    };
-    // subsequences that start behind the data decode nothing: left out of the rounds, they do
-    // not hand a change on one thread per round (only the last chunk has any, so its exit state
-    // is needed by nobody)
-    const uint32_t left = nsub - ch * (uint32_t)T;
-    const int live = left < (uint32_t)T ? (int)left : T;
-    for (int i = 0; i < T; ++i) {                                      // steps 1, 2: the cold pass
+    // subsequences that start behind the data are not live: they decode nothing and stay out of
+    // the rounds, where they would hand a change on one thread per round
+    for (int i = 0; i < kT; ++i) {                                     // steps 1, 2: the cold pass
       cnt[i] = 0;
-      if (i >= live) continue;
-      last[i] = i ? JpegHuffState{(ch * (uint32_t)T + i) * S, 0} : entry;
-      ex[i] = last[i];
-      cnt[i] = jpeg_huff_run<false>(d, m, &ex[i], end_of(i), 0, err);
+      last[i] = ex[i] = lane[i].in0;
+      if (lane[i].live) cnt[i] = jpeg_huff_run<false>(d, m, &ex[i], lane[i].end, 0, err);
     }
     uint32_t r = 0;
-    for (; r < (uint32_t)T; ++r) {                                     // steps 3, 4: to the fixed point
-      for (int i = 1; i < T; ++i) in[i] = ex[i - 1];
+    for (; r < bound; ++r) {                                           // steps 3, 4: to the fixed point
+      for (int i = 1; i < kT; ++i) in[i] = ex[i - 1];
       bool any = false;
-      for (int i = 1; i < live; ++i) {
-        if (in[i] == last[i]) continue;
+      for (int i = 1; i < kT; ++i) {
+        if (lane[i].head || !lane[i].live || in[i] == last[i]) continue;
         last[i] = in[i];
         JpegHuffState e = in[i];
-        cnt[i] = jpeg_huff_run<false>(d, m, &e, end_of(i), 0, err);
+        cnt[i] = jpeg_huff_run<false>(d, m, &e, lane[i].end, 0, err);
         if (!(e == ex[i])) any = true;
         ex[i] = e;
       }
@@ -631,38 +723,107 @@ uint64_t jpeg_huff_cpu(const JpegHuffDesc& d, const uint8_t* stage, uint64_t sta
     }
     if (r + 1 > *rounds) *rounds = r + 1;
     uint32_t sum = 0;                                                  // step 5
-    for (int i = 0; i < T; ++i) {
-      excl[i] = sum;
-      sum += cnt[i];
+    for (int i = 0; i < kT; ++i) incl[i] = sum += cnt[i];
+    for (int i = 0; i < kT; ++i) {                                     // step 6: the write pass
+      const JpegHuffLane& l = lane[i];
+      if (!l.live) continue;
+      if (l.seg > (uint32_t)i) { ++*bad; continue; }
+      JpegHuffState st = (l.head || i == 0) ? l.in0 : ex[i - 1];
+      const uint32_t g = l.g0 + (incl[i] - cnt[i]) - (l.seg ? incl[l.seg - 1] : 0);
+      jpeg_huff_run_to<true>(d, m, &st, l.end, g, l.g_end, l.p_end, err);
     }
-    for (int i = 0; i < live; ++i) {                                   // step 6: the write pass
-      JpegHuffState st = i ? ex[i - 1] : entry;
-      jpeg_huff_run<true>(d, m, &st, end_of(i), base + excl[i], err);
-    }
-    entry = ex[T - 1];
-    base += sum;
   }
-  if (base < d.nblocks) *err = 1;                                      // the data ends before the last MCU
-  for (int c = 0; c < d.ncomp; ++c) {                                  // step 7, partitioned as the kernel does
-    const uint32_t n = (uint32_t)d.bw[c] * (uint32_t)d.bh[c], per = (n + T - 1) / T;
-    std::vector<uint32_t> tot(T, 0);
-    for (int i = 0; i < T; ++i)
-      for (uint32_t k = i * per; k < n && k < (i + 1) * per; ++k) {
-        const uint64_t off = jpeg_huff_dc_off(d, c, k);
-        if (off >= coef_cap) { ++bad; continue; }
-        tot[i] += (uint16_t)coef[off];
-      }
-    uint32_t run = 0;
-    for (int i = 0; i < T; ++i) {
-      uint32_t acc = run;
-      for (uint32_t k = i * per; k < n && k < (i + 1) * per; ++k) {
-        const uint64_t off = jpeg_huff_dc_off(d, c, k);
-        if (off >= coef_cap) { ++bad; continue; }
-        acc += (uint16_t)coef[off];
-        coef[off] = (int16_t)(uint16_t)acc;
-      }
-      run += tot[i];
+
+  // a walk in chunks over ``bits`` bits from scan word ``word``, into the blocks [g0, g_end)
+  void walk(uint32_t word, uint32_t bits, uint32_t g0, uint32_t g_end) {
+    const uint32_t nsub = jpeg_huff_nsub(bits), nchunk = (nsub + kT - 1) / kT;
+    const uint64_t w_lim = (uint64_t)word + jpeg_huff_interval_words(bits);
+    const uint32_t w_end = (uint32_t)(w_lim < nwords ? w_lim : nwords);
+    JpegHuffState entry{word * 32u, 0};
+    uint32_t base = g0;
+    for (uint32_t ch = 0; ch < nchunk; ++ch) {
+      for (int i = 0; i < kT; ++i) lane[i] = jpeg_huff_walk_lane(word * 32u, bits, ch, (uint32_t)i, entry, base, g_end);
+      chunk(word + ch * (uint32_t)kJpegHuffChunkWords, w_end, (uint32_t)kT);
+      entry = ex[kT - 1];
+      base += incl[kT - 1];
     }
+    if (base < g_end) *err = 1;                                        // the data ends before the last MCU
+  }
+
+  void clear(uint32_t g0, uint32_t g_end) {                            // step 8, the blocks of [g0, g_end)
+    for (uint32_t g = g0; g < g_end; ++g) {
+      const uint64_t off = jpeg_huff_block_off(d, g);
+      for (int k = 0; k < 64; ++k) {
+        if (off + k >= m.coef_cap) { ++*bad; break; }
+        m.coef[off + k] = 0;
+      }
+    }
+  }
+
+  void group(const JpegHuffInterval* iv, const JpegHuffGroup& gr) {
+    const uint32_t g0 = jpeg_huff_interval_block(d, gr.first);
+    clear(g0, jpeg_huff_interval_block(d, (uint64_t)gr.first + gr.count));
+    if (gr.count == 1) {
+      walk(iv[gr.first].word, iv[gr.first].bits, g0, jpeg_huff_interval_block(d, (uint64_t)gr.first + 1));
+      return;
+    }
+    uint32_t n = 0, most = 0;
+    for (uint32_t j = gr.first; j < gr.first + gr.count; ++j) {
+      const uint32_t nsub = jpeg_huff_nsub(iv[j].bits);
+      most = nsub > most ? nsub : most;
+      for (uint32_t s = 0; s < nsub; ++s, ++n) {
+        if (n >= (uint32_t)kT) { ++*bad; continue; }
+        lane[n] = jpeg_huff_group_lane(d, iv[j], j, s, n);
+      }
+    }
+    for (uint32_t i = n; i < (uint32_t)kT; ++i) lane[i] = JpegHuffLane{};
+    const JpegHuffInterval& z = iv[gr.first + gr.count - 1];
+    const uint64_t w_lim = (uint64_t)z.word + jpeg_huff_interval_words(z.bits);
+    chunk(iv[gr.first].word, (uint32_t)(w_lim < nwords ? w_lim : nwords), most);
+    for (uint32_t i = 0; i < n && i < (uint32_t)kT; ++i) {             // an interval that ends before its last block
+      if (i + 1 < n && !lane[i + 1].head) continue;
+      const uint32_t total = incl[i] - (lane[i].seg ? incl[lane[i].seg - 1] : 0);
+      if (total < lane[i].g_end - lane[i].g0) *err = 1;
+    }
+  }
+};
+
+// step 7, the DC sums of one segment of component c: blocks [lo, hi) of its scan order
+void emu_dc(const JpegHuffDesc& d, int c, uint32_t lo, uint32_t hi, int16_t* coef, uint64_t coef_cap, uint64_t* bad) {
+  uint32_t acc = 0;
+  for (uint32_t k = lo; k < hi; ++k) {
+    const uint64_t off = jpeg_huff_dc_off(d, c, k);
+    if (off >= coef_cap) { ++*bad; continue; }
+    acc += (uint16_t)coef[off];
+    coef[off] = (int16_t)(uint16_t)acc;
+  }
+}
+
+}  // namespace
+
+uint64_t jpeg_huff_cpu(const JpegHuffDesc& d, const uint8_t* stage, uint64_t stage_cap, int16_t* coef,
+                       uint64_t coef_cap, uint32_t* err, uint32_t* rounds) {
+  *err = 1;
+  *rounds = 0;
+  if (!jpeg_huff_desc_valid(d, stage_cap, coef_cap, stage) || reinterpret_cast<uintptr_t>(stage) % 4) return 0;
+  *err = 0;
+  uint64_t bad = 0;
+  const std::unique_ptr<Emu> emu(new Emu(d, stage, coef, coef_cap, err, rounds, &bad));   // its vectors are the LDS
+  Emu& e = *emu;
+  if (!jpeg_huff_desc_is_rst(d)) {
+    e.clear(0, d.nblocks);
+    e.walk(0, d.nbits, 0, d.nblocks);
+    // the wrapping sums do not depend on how the kernel splits them over its threads
+    for (int c = 0; c < d.ncomp; ++c) emu_dc(d, c, 0, (uint32_t)d.bw[c] * (uint32_t)d.bh[c], coef, coef_cap, &bad);
+    return bad;
+  }
+  const JpegHuffInterval* iv = reinterpret_cast<const JpegHuffInterval*>(stage + d.int_off);
+  const JpegHuffGroup* gr = reinterpret_cast<const JpegHuffGroup*>(stage + d.grp_off);
+  for (uint32_t g = 0; g < d.ngroup; ++g) e.group(iv, gr[g]);
+  for (int c = 0; c < d.ncomp; ++c) {                                  // the predictors start again at every interval
+    const uint32_t n = (uint32_t)d.bw[c] * (uint32_t)d.bh[c];
+    const uint64_t per = (uint64_t)d.ri * (uint32_t)(d.h[c] * d.v[c]);
+    for (uint64_t lo = 0; lo < n; lo += per) emu_dc(d, c, (uint32_t)lo, (uint32_t)(lo + per < n ? lo + per : n), coef, coef_cap, &bad);
   }
   return bad;
 }

@@ -51,7 +51,8 @@ constexpr int kJpegHuffTabBytes = kJpegHuffTabWords * 4;
 constexpr int kHtMax = 256, kHtOff = 273, kHtN = 290, kHtVals = 291;
 
 // What jpeg_scan_prepare found besides the header. The prepared buffer is
-// [2 * ncomp tables (DC, AC per scan component) | the unstuffed scan as big-endian 32-bit words].
+// [2 * ncomp tables (DC, AC per scan component) | the unstuffed scan as big-endian 32-bit words],
+// and for a file with restart intervals [... | interval table | group table] behind it.
 struct JpegHuffInfo {
   uint32_t nbits = 0;        // bits of entropy-coded data after unstuffing
   uint32_t scan_bytes = 0;   // staged scan: whole words, zero padded
@@ -60,7 +61,14 @@ struct JpegHuffInfo {
   uint32_t nbytes = 0;       // bytes of the prepared buffer in use
   int32_t nb = 0;            // blocks per MCU: 1, 3, 4 or 6
   uint8_t comp[8] = {};      // component of each block of the MCU
-  bool device_ok = false;    // false: restart intervals (the host decoder's work)
+  bool device_ok = false;    // false: restart intervals (jpeg_huff_decode does not take them)
+  // A file with restart intervals (DRI): the scan words hold the intervals one after another, each
+  // from a word boundary and followed by one zero word; behind the scan sit the interval table
+  // (nint x {first scan word, bits}) and the group table (ngroup x {first interval, count}).
+  bool restart_ok = false;   // the markers are RST0, RST1, ... in order and in number: jpeg_huff_rst_decode may run
+  uint32_t ri = 0;           // MCUs per interval
+  uint32_t nint = 0, ngroup = 0;
+  uint32_t int_off = 0, grp_off = 0;   // bytes from the start of the prepared buffer
 };
 
 // One image of a GPU entropy-decode call (device memory; built and validated on the host).
@@ -72,12 +80,37 @@ struct JpegHuffDesc {
   int32_t bw[3], bh[3], h[3], v[3];
   int32_t ncomp, nb, mx, my;
   uint8_t comp[8], bu[8], bv[8];   // per block of the MCU: component, column and row inside the MCU
-  uint32_t pad_;
+  // restart intervals (all zero for a file without): MCUs per interval, the interval table
+  // (nint x JpegHuffInterval) and the group table (ngroup x JpegHuffGroup), bytes from the staging base
+  uint32_t ri, nint, ngroup, int_off, grp_off;
 };
+struct JpegHuffInterval {
+  uint32_t word;             // its first scan word
+  uint32_t bits;             // its length after unstuffing; one zero word follows its last word
+};
+// The intervals that one workgroup of jpeg_huff_rst_decode takes: consecutive ones whose
+// subsequences ceil(bits / S) sum to at most T and whose words fit one staged chunk, or a single
+// interval of any length, which the workgroup walks in chunks.
+struct JpegHuffGroup {
+  uint32_t first, count;
+};
+KDL_JPEG_HD uint32_t jpeg_huff_nsub(uint32_t bits) {
+  return bits / (uint32_t)kJpegHuffSubBits + (bits % (uint32_t)kJpegHuffSubBits ? 1u : 0u);
+}
+KDL_JPEG_HD uint32_t jpeg_huff_interval_words(uint32_t bits) { return bits / 32u + (bits % 32u ? 1u : 0u) + 1u; }
+// the rule of a group of more than one interval, over its running sums
+KDL_JPEG_HD bool jpeg_huff_group_fits(uint64_t nsub, uint64_t words) {
+  return nsub <= (uint64_t)kJpegHuffChunk && words <= (uint64_t)kJpegHuffChunkWords;
+}
 static_assert(sizeof(JpegHuffDesc) % 8 == 0, "JpegHuffDesc is copied as raw bytes");
 
-// upper bound of the prepared buffer of an n-byte file
-inline uint64_t jpeg_prepare_bound(uint64_t n) { return 6ull * kJpegHuffTabBytes + n + 16; }
+// upper bound of the prepared buffer of an n-byte file; ``nint``: the restart intervals its header
+// announces (0 without DRI). An interval adds its padding and its table entries, and the file holds
+// at most one marker per two bytes, so a header cannot claim more than the file's size allows.
+inline uint64_t jpeg_prepare_bound(uint64_t n, uint64_t nint = 0) {
+  const uint64_t most = n / 2 + 1;
+  return 6ull * kJpegHuffTabBytes + n + 16 + 24ull * (nint < most ? nint : most);
+}
 
 // Same marker walk, checks and statuses as jpeg_parse up to the scan; nothing is decoded.
 // Writes the tables and the unstuffed scan into ``out`` (capacity ``cap`` bytes, 4-byte aligned).
@@ -86,8 +119,14 @@ JpegStatus jpeg_scan_prepare(const uint8_t* data, size_t n, uint64_t max_pixels,
 // ``stage_base``: where the prepared buffer sits in the call's staging, in bytes
 void jpeg_huff_fill_desc(const JpegHeader& h, const JpegHuffInfo& info, uint64_t stage_base, uint64_t coef_base,
                          JpegHuffDesc* d);
-// every offset the kernels will follow against the capacities of the call (stage_cap bytes, coef_cap int16)
-inline bool jpeg_huff_desc_valid(const JpegHuffDesc& d, uint64_t stage_cap, uint64_t coef_cap) {
+KDL_JPEG_HD bool jpeg_huff_desc_is_rst(const JpegHuffDesc& d) {
+  return (d.ri | d.nint | d.ngroup | d.int_off | d.grp_off) != 0;
+}
+// every offset the kernels will follow against the capacities of the call (stage_cap bytes, coef_cap
+// int16). A descriptor with restart intervals has tables in the staging: ``h_stage`` is the host's
+// copy of it, and without one such a descriptor is refused.
+inline bool jpeg_huff_desc_valid(const JpegHuffDesc& d, uint64_t stage_cap, uint64_t coef_cap,
+                                 const uint8_t* h_stage = nullptr) {
   if (d.ncomp != 1 && d.ncomp != 3) return false;
   if (d.mx < 1 || d.my < 1 || d.mx > 8192 || d.my > 8192) return false;
   int nb = 0;
@@ -108,10 +147,37 @@ inline bool jpeg_huff_desc_valid(const JpegHuffDesc& d, uint64_t stage_cap, uint
   for (int t = 0; t < 6; ++t)
     if (d.tab_off[t] % 4 || d.tab_off[t] > stage_cap || (uint64_t)kJpegHuffTabBytes > stage_cap - d.tab_off[t])
       return false;
-  return true;
+  if (!jpeg_huff_desc_is_rst(d)) return true;
+  if (!h_stage || reinterpret_cast<uintptr_t>(h_stage) % 4) return false;
+  const uint64_t mcus = (uint64_t)d.mx * d.my;
+  if (d.ri < 1 || (uint64_t)d.nint != (mcus + d.ri - 1) / d.ri || d.ngroup < 1 || d.ngroup > d.nint) return false;
+  if (d.int_off % 4 || d.int_off > stage_cap || 8ull * d.nint > stage_cap - d.int_off) return false;
+  if (d.grp_off % 4 || d.grp_off > stage_cap || 8ull * d.ngroup > stage_cap - d.grp_off) return false;
+  const JpegHuffInterval* iv = reinterpret_cast<const JpegHuffInterval*>(h_stage + d.int_off);
+  const JpegHuffGroup* gr = reinterpret_cast<const JpegHuffGroup*>(h_stage + d.grp_off);
+  uint64_t next = 0;                           // the intervals follow each other inside the image's scan words
+  for (uint32_t j = 0; j < d.nint; ++j) {
+    if (iv[j].bits < 1 || iv[j].bits >= (1u << 30) || iv[j].word < next) return false;
+    next = (uint64_t)iv[j].word + jpeg_huff_interval_words(iv[j].bits);
+    if (next > d.scan_bytes / 4) return false;
+  }
+  next = 0;                                    // the groups tile the interval table
+  for (uint32_t g = 0; g < d.ngroup; ++g) {
+    if (gr[g].first != next || gr[g].count < 1 || gr[g].count > d.nint - gr[g].first) return false;
+    next += gr[g].count;
+    if (gr[g].count == 1) continue;
+    uint64_t nsub = 0;
+    for (uint32_t j = gr[g].first; j < next; ++j) nsub += jpeg_huff_nsub(iv[j].bits);
+    const JpegHuffInterval& z = iv[next - 1];
+    if (!jpeg_huff_group_fits(nsub, (uint64_t)z.word + jpeg_huff_interval_words(z.bits) - iv[gr[g].first].word))
+      return false;
+  }
+  return next == d.nint;
 }
 // The kernels' procedure on the host, serially over the "threads": clears the planes, decodes
 // ``stage`` (the call's staging, stage_cap bytes) into coef (coef_cap int16) and sums the DC.
+// A descriptor with restart intervals takes the procedure of jpeg_huff_rst_decode and
+// jpeg_dc_rst_scan: group after group, the same lanes, rounds, per-interval scans and checks.
 // err: the error word (non-zero = ask jpeg_parse); rounds: most fixed-point rounds of a chunk;
 // returns the number of indices that fell outside their buffer behind the checks (must be 0).
 uint64_t jpeg_huff_cpu(const JpegHuffDesc& d, const uint8_t* stage, uint64_t stage_cap, int16_t* coef,
@@ -173,9 +239,11 @@ KDL_JPEG_HD bool operator==(const JpegHuffState& a, const JpegHuffState& b) { re
 // for what the host decoder rejects. Without it the pass runs on states that may be wrong: on a
 // bit string that is no code it moves one bit and carries on, and reports nothing.
 // Every iteration consumes at least one bit, so the loop ends after at most end - p of them.
+// ``g_end`` / ``p_end``: the write pass stops behind block g_end - 1, which must not have used bits
+// past p_end: the image's blocks and bits, or those of one restart interval.
 template <bool kWrite, class Mem>
-KDL_JPEG_HD uint32_t jpeg_huff_run(const JpegHuffDesc& d, Mem& m, JpegHuffState* st, uint32_t end, uint32_t g,
-                                   uint32_t* err) {
+KDL_JPEG_HD uint32_t jpeg_huff_run_to(const JpegHuffDesc& d, Mem& m, JpegHuffState* st, uint32_t end, uint32_t g,
+                                      uint32_t g_end, uint32_t p_end, uint32_t* err) {
   uint32_t p = st->p, b = st->bk >> 8, k = st->bk & 255u, done = 0;
   if (b >= (uint32_t)d.nb) b = 0;
   if (k > 63) k = 0;
@@ -185,7 +253,7 @@ KDL_JPEG_HD uint32_t jpeg_huff_run(const JpegHuffDesc& d, Mem& m, JpegHuffState*
   const uint32_t* tdc = m.table(2 * d.comp[b]);       // the tables of the block's component
   const uint32_t* tac = m.table(2 * d.comp[b] + 1);
   while (p < end) {
-    if (kWrite && g >= d.nblocks) break;              // bits after the last MCU are ignored
+    if (kWrite && g >= g_end) break;                  // bits after the last MCU are ignored
     if ((p >> 5) != wi) {                             // a step is at most 31 bits: the next word
       hi = (p >> 5) == wi + 1 ? lo : m.word(p >> 5);
       wi = p >> 5;
@@ -240,7 +308,7 @@ KDL_JPEG_HD uint32_t jpeg_huff_run(const JpegHuffDesc& d, Mem& m, JpegHuffState*
       ++done;
       if (kWrite) {
         ++g;
-        if (g == d.nblocks && p > d.nbits) *err = 1;  // the last MCU used bits that are not there
+        if (g == g_end && p > p_end) *err = 1;        // the last MCU used bits that are not there
         off = jpeg_huff_block_off(d, g);
       }
     }
@@ -248,6 +316,62 @@ KDL_JPEG_HD uint32_t jpeg_huff_run(const JpegHuffDesc& d, Mem& m, JpegHuffState*
   st->p = p;
   st->bk = (b << 8) | k;
   return done;
+}
+template <bool kWrite, class Mem>
+KDL_JPEG_HD uint32_t jpeg_huff_run(const JpegHuffDesc& d, Mem& m, JpegHuffState* st, uint32_t end, uint32_t g,
+                                   uint32_t* err) {
+  return jpeg_huff_run_to<kWrite>(d, m, st, end, g, d.nblocks, d.nbits, err);
+}
+
+// What one thread brings to a chunk. A head enters with a true state and never re-runs; the others
+// start cold and take the exit of the thread before them. Threads from a head up to the next one
+// form a segment: the whole chunk for jpeg_huff_decode, one restart interval for
+// jpeg_huff_rst_decode, whose write pass stays inside the interval's own blocks and bits.
+struct JpegHuffLane {
+  uint32_t live, head;
+  JpegHuffState in0;         // the true entry of a head, the cold start (its first bit, 0, 0) of the others
+  uint32_t end;              // the bit behind its subsequence
+  uint32_t seg;              // the thread of its segment's head
+  uint32_t g0, g_end;        // the segment's first block, and the block behind its last
+  uint32_t p_end;            // the bit behind the segment's data
+};
+// thread i of chunk ch of a walk over ``bits`` bits from bit p0: the scan of a file without restart
+// intervals (p0 = 0), or a single interval longer than a chunk. ``entry``: the chunk's true entry.
+KDL_JPEG_HD JpegHuffLane jpeg_huff_walk_lane(uint32_t p0, uint32_t bits, uint32_t ch, uint32_t i, JpegHuffState entry,
+                                             uint32_t g0, uint32_t g_end) {
+  const uint32_t sub = ch * (uint32_t)kJpegHuffChunk + i, nsub = jpeg_huff_nsub(bits);
+  const uint64_t stop = ((uint64_t)sub + 1) * (uint32_t)kJpegHuffSubBits;
+  JpegHuffLane l;
+  l.live = sub < nsub;
+  l.head = i == 0;
+  l.in0 = i ? JpegHuffState{p0 + sub * (uint32_t)kJpegHuffSubBits, 0} : entry;
+  l.end = p0 + (uint32_t)(stop < bits ? stop : bits);
+  l.seg = 0;
+  l.g0 = g0;
+  l.g_end = g_end;
+  l.p_end = p0 + bits;
+  return l;
+}
+// [first block, the block behind the last) of the intervals [j, j + count) of a restart descriptor
+KDL_JPEG_HD uint32_t jpeg_huff_interval_block(const JpegHuffDesc& d, uint64_t j) {
+  const uint64_t g = j * d.ri * (uint32_t)d.nb;
+  return (uint32_t)(g < d.nblocks ? g : d.nblocks);
+}
+// subsequence s of interval j (iv) of a group of several intervals; the thread is i
+KDL_JPEG_HD JpegHuffLane jpeg_huff_group_lane(const JpegHuffDesc& d, const JpegHuffInterval& iv, uint32_t j, uint32_t s,
+                                              uint32_t i) {
+  const uint32_t p0 = iv.word * 32u;
+  const uint64_t stop = ((uint64_t)s + 1) * (uint32_t)kJpegHuffSubBits;
+  JpegHuffLane l;
+  l.live = 1;
+  l.head = s == 0;
+  l.in0 = JpegHuffState{p0 + s * (uint32_t)kJpegHuffSubBits, 0};
+  l.end = p0 + (uint32_t)(stop < iv.bits ? stop : iv.bits);
+  l.seg = i - s;
+  l.g0 = jpeg_huff_interval_block(d, j);
+  l.g_end = jpeg_huff_interval_block(d, (uint64_t)j + 1);
+  l.p_end = p0 + iv.bits;
+  return l;
 }
 
 // DC differences -> DC values of one component: block n of its scan order

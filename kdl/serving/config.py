@@ -85,7 +85,9 @@ class ServerConfig:
     # (gateway.preprocess.ResizeSpec); "" = the model version's own "preprocess", else nearest
     preprocess: str = ""
     # where serving_bytes Huffman-decodes baseline JPEG scans: "host" (csrc/runtime/jpeg.cpp) or "gpu"
-    # (csrc/kernels/jpeg_huff.hip; files with restart intervals and rejected scans still go to the host)
+    # (csrc/kernels/jpeg_huff.hip; files with restart intervals and rejected scans still go to the host), or
+    # "gpu_rst": gpu, and files with restart intervals are decoded on the device too, one workgroup per
+    # group of intervals (a file whose RSTm markers are out of order or number still goes to the host)
     jpeg_entropy: str = "host"
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
@@ -177,9 +179,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "size, with R the shorter side becomes R and the center is cropped (torchvision "
                          "Resize(R) + CenterCrop). Overrides the model version's \"preprocess\" (env KDL_PREPROCESS, "
                          "default: the version's, else nearest)")
-    ap.add_argument("--jpeg_entropy", choices=["host", "gpu"], default=None,
+    ap.add_argument("--jpeg_entropy", choices=["host", "gpu", "gpu_rst"], default=None,
                     help="where serving_bytes Huffman-decodes baseline JPEG scans: host cores, or the GPU (the host "
-                         "then only walks the markers, builds the tables and removes the byte stuffing); env "
+                         "then only walks the markers, builds the tables and removes the byte stuffing); gpu_rst: "
+                         "as gpu, and files with restart intervals (DRI) are decoded on the GPU too, their "
+                         "intervals in parallel workgroups, instead of going to the host; env "
                          "KDL_JPEG_ENTROPY (default host)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "

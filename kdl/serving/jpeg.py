@@ -30,6 +30,15 @@ request's synchronise; if one is set the whole request is decoded again through 
 whose answer (success, or ``INVALID_ARGUMENT`` with its message) is the request's. A request that
 holds a file with restart intervals takes the host path as a whole.
 
+``entropy="gpu_rst"`` is ``gpu``, and files with restart intervals (a ``DRI`` segment: cameras,
+phones, hardware encoders) are decoded on the device too. Every interval starts byte-aligned at a
+known MCU with its DC predictors at zero, so ``jpeg_scan_prepare`` carries its unstuffing on through
+the ``RSTm`` markers and adds a table of the intervals, and ``jpeg_huff_rst_decode`` +
+``jpeg_dc_rst_scan`` give each group of intervals a workgroup of its own. In one request the plain
+files go through ``jpeg_huff_decode`` and the restart files through ``jpeg_huff_rst_decode``. A file
+whose markers are not exactly ``RST0, RST1, ...`` in order and in number (``restart_ok`` false)
+sends the request to the host decoder, as a restart file does under ``gpu``.
+
 Files the decoder does not cover (progressive or arithmetic JPEG, CMYK, PNG, ...) are decoded by
 PIL on the host and resized by ``resize_nearest_u8`` into the same batch. Without a GPU the same
 arithmetic runs on the CPU (``jpeg_pixels_cpu``) followed by the numpy gather.
@@ -72,6 +81,21 @@ def _align(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
 
+def _intervals(data: bytes, header) -> int:
+    """An upper bound of the restart intervals of a file, for ``jpeg_prepare_bound``: its MCUs over
+    the smallest interval that anything in it that reads as a DRI segment defines (the probed header
+    ends at the frame header, and encoders write DRI behind it). 0: no DRI segment."""
+    ri, at = 0, data.find(b"\xff\xdd\x00\x04")
+    while at >= 0:
+        r = int.from_bytes(data[at + 4:at + 6], "big")
+        ri = min(ri, r) if ri and r else ri or r
+        at = data.find(b"\xff\xdd\x00\x04", at + 2)
+    if not ri:
+        return 0
+    _, h, v, _, bw, bh = header.comps[0][:6]
+    return -(-((bw // h) * (bh // v)) // ri)
+
+
 def _bad(msg: str):
     from .backend import ServingError
     return ServingError("INVALID_ARGUMENT", msg)
@@ -101,7 +125,9 @@ class CallLayout:
         self.device_entropy = prepared is not None
         if prepared is not None:
             self.huff_bytes = _lib.rt().JPEG_HUFF_DESC_BYTES
-            self.off_huff, self.n_huff = self.off_coef, 0
+            # descriptors of plain files from the front, of restart files from the back: each
+            # launcher gets a contiguous range
+            self.off_huff, self.n_huff, self.n_rst, self.n_slots = self.off_coef, 0, 0, n
             self.prep_at, o = [], _align(self.off_huff + n * self.huff_bytes, 256)
             for b in prepared:
                 self.prep_at.append(o)
@@ -115,15 +141,28 @@ class CallLayout:
 
     def add_huff(self, hin: np.ndarray, k: int, header, info) -> None:
         """Stage the entropy-decode descriptor of slot ``k``; call in the order of ``add``."""
-        j, D = self.n_huff, self.huff_bytes
+        D = self.huff_bytes
         desc = _lib.rt().jpeg_huff_desc(header, info, self.prep_at[k], self.coef_at[k])
+        if info.restart_ok:
+            self.n_rst += 1
+            j = self.n_slots - self.n_rst
+        else:
+            j = self.n_huff
+            self.n_huff = j + 1
+        assert self.n_huff + self.n_rst <= self.n_slots
         hin[self.off_huff + j * D:self.off_huff + (j + 1) * D] = np.frombuffer(desc, np.uint8)
-        self.n_huff = j + 1
 
     def huff_args(self, h_in: int, d_in: int, coef: int, status: int, status_cap: int) -> dict:
         """The argument dict of kdl._C.jpeg_huff_decode / jpeg_dc_scan (addresses as ints)."""
         return dict(desc=d_in + self.off_huff, h_desc=h_in + self.off_huff, stage=d_in, stage_cap=self.nbytes, coef=coef,
                     coef_cap=self.ncoef, status=status, status_cap=status_cap, n=self.n_huff)
+
+    def huff_rst_args(self, h_in: int, d_in: int, coef: int, status: int, status_cap: int) -> dict:
+        """The argument dict of kdl._C.jpeg_huff_rst_decode / jpeg_dc_rst_scan for the restart files of
+        the call; ``status``: where their status words start (behind the plain files')."""
+        at = self.off_huff + (self.n_slots - self.n_rst) * self.huff_bytes
+        return dict(desc=d_in + at, h_desc=h_in + at, stage=d_in, h_stage=h_in, stage_cap=self.nbytes, coef=coef,
+                    coef_cap=self.ncoef, status=status, status_cap=status_cap, n=self.n_rst)
 
     def coef(self, hin: np.ndarray, k: int, ncoef: int) -> np.ndarray:
         """The int16 coefficient buffer of slot ``k`` inside the uint8 staging array ``hin``."""
@@ -155,8 +194,8 @@ class BytesRunner:
     ``serving_uint8`` runner's batcher and executors."""
 
     def __init__(self, sig, inner, devices: list[int], spec: ResizeSpec | None = None, entropy: str = "host"):
-        if entropy not in ("host", "gpu"):
-            raise ValueError(f"jpeg entropy decode {entropy!r}: expected 'host' or 'gpu'")
+        if entropy not in ("host", "gpu", "gpu_rst"):
+            raise ValueError(f"jpeg entropy decode {entropy!r}: expected 'host', 'gpu' or 'gpu_rst'")
         self.sig, self.inner = sig, inner
         self.entropy = entropy if devices else "host"       # CPU servers decode on the host
         self.source = inner.source
@@ -225,20 +264,24 @@ class BytesRunner:
 
     def _prepare_all(self, plan, lay, hin, slot) -> dict | None:
         """Stage tables and scan of every JPEG of ``plan`` for the device decode -> {image: info}, or
-        None when a file has restart intervals: the request then is the host decoder's. As in
+        None when a file is not for the device (restart intervals under ``gpu``; under ``gpu_rst`` only
+        those whose markers are out of order or number): the request then is the host decoder's. As in
         ``_parse_all`` a file outside the decoder falls back to PIL and a malformed header is rejected."""
         rt = _lib.rt()
         t0 = time.perf_counter()
         infos, ok = {}, True
         for i, k in slot.items():
             st, hd, info = rt.jpeg_scan_prepare(plan[i][0], lay.prep(hin, k), MAX_PIXELS)
+            if st == rt.JPEG_MALFORMED and hd.why == "prepare buffer too small":
+                ok = False                              # more intervals than its headers let expect
+                continue
             if st == rt.JPEG_MALFORMED:
                 raise _bad(f"image {i}: malformed JPEG ({hd.why})")
             if st != rt.JPEG_OK:
                 plan[i][1] = None
                 continue
             plan[i][1], infos[i] = hd, info
-            ok = ok and info.device_ok
+            ok = ok and (info.device_ok or (self.entropy == "gpu_rst" and info.restart_ok))
         METRICS.observe("kdl_stage_ms", (time.perf_counter() - t0) * 1e3, stage="jpeg_prepare")
         return infos if ok else None
 
@@ -248,9 +291,11 @@ class BytesRunner:
         coefficients -> (layout, {image: JpegHuffInfo} | None, offset of the extra room)."""
         ncoefs = [plan[i][1].ncoef for i in slot]
         c.n_status = 0
-        if self.entropy == "gpu" and not host and slot:
+        if self.entropy != "host" and not host and slot:
             rt = _lib.rt()
-            lay = CallLayout(ncoefs, [rt.jpeg_prepare_bound(len(plan[i][0])) for i in slot])
+            rst = self.entropy == "gpu_rst"
+            lay = CallLayout(ncoefs, [rt.jpeg_prepare_bound(len(plan[i][0]), _intervals(*plan[i]) if rst else 0)
+                                      for i in slot])
             off = _align(lay.nbytes, 256)
             c.grow(off + extra, n_out)
             infos = self._prepare_all(plan, lay, c.h_in.numpy(), slot)
@@ -269,15 +314,22 @@ class BytesRunner:
     def _entropy_on(self, c, lay, stream: int) -> int | None:
         """Launch the device entropy decode of a second-form layout (inside the stream context, after
         the staging copy) -> the coefficient buffer's address for ``CallLayout.args``."""
-        if not lay.device_entropy or not lay.n_huff:
+        n = lay.n_huff + lay.n_rst if lay.device_entropy else 0
+        if not n:
             return None
         C = _lib.lib()
-        ha = lay.huff_args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_coef), _lib.ptr(c.d_status), c.cap_status)
-        C.jpeg_huff_decode(ha, stream)
-        C.jpeg_dc_scan(ha, stream)
-        c.n_status = lay.n_huff
-        c.h_status[:2 * lay.n_huff].copy_(c.d_status[:2 * lay.n_huff], non_blocking=True)
-        METRICS.inc("kdl_jpeg_entropy_total", lay.n_huff, where="gpu")
+        if lay.n_huff:
+            ha = lay.huff_args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_coef), _lib.ptr(c.d_status), c.cap_status)
+            C.jpeg_huff_decode(ha, stream)
+            C.jpeg_dc_scan(ha, stream)
+        if lay.n_rst:                                   # their status words follow the plain files'
+            ha = lay.huff_rst_args(_lib.ptr(c.h_in), _lib.ptr(c.d_in), _lib.ptr(c.d_coef),
+                                   _lib.ptr(c.d_status) + 8 * lay.n_huff, c.cap_status - 2 * lay.n_huff)
+            C.jpeg_huff_rst_decode(ha, stream)
+            C.jpeg_dc_rst_scan(ha, stream)
+        c.n_status = n
+        c.h_status[:2 * n].copy_(c.d_status[:2 * n], non_blocking=True)
+        METRICS.inc("kdl_jpeg_entropy_total", n, where="gpu")
         return _lib.ptr(c.d_coef)
 
     @staticmethod
@@ -315,7 +367,7 @@ class BytesRunner:
         C = _lib.lib()
         S, n = self.S, len(plan)
         slot = {i: k for k, i in enumerate(i for i, p in enumerate(plan) if p[1] is not None)}
-        where = "retry" if host and self.entropy == "gpu" else "host"
+        where = "retry" if host and self.entropy != "host" else "host"
         METRICS.inc("kdl_resize_total", filter=self.spec.filter)
         if self.resizer.filtered:
             return self._resample_on(c, plan, slot, host, where)

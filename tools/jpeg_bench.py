@@ -13,6 +13,10 @@ buffer) against Pillow's full decode (Image.open().convert("RGB")) on the same c
 --entropy gpu adds the device entropy decode (profiles/jpeg_entropy_gpu.txt): on the host
 jpeg_scan_prepare beside jpeg_parse, on the GPU jpeg_huff_decode + jpeg_dc_scan in front of
 jpeg_idct_u8 in the same loop, with the fixed-point rounds the decode took.
+--restart rows:N | blocks:N encodes the file with restart markers every N MCU rows / N MCUs
+(profiles/jpeg_restart_gpu.txt): the host numbers are of that file, the entropy kernels are
+jpeg_huff_rst_decode + jpeg_dc_rst_scan, and "yardstick_entropy_kernels" times jpeg_huff_decode +
+jpeg_dc_scan on the same image encoded without markers, in the same run.
 """
 from __future__ import annotations
 
@@ -30,11 +34,21 @@ import numpy as np  # noqa: E402
 from PIL import Image  # noqa: E402
 
 
-def make_file(H: int, W: int) -> bytes:
+def restart_kw(spec: str | None) -> dict:
+    """--restart rows:N | blocks:N -> the keyword of Pillow's JPEG encoder."""
+    if not spec:
+        return {}
+    kind, _, n = spec.partition(":")
+    if kind not in ("rows", "blocks") or not n.isdigit() or int(n) < 1:
+        raise SystemExit(f"--restart {spec!r}: expected rows:N or blocks:N")
+    return {f"restart_marker_{kind}": int(n)}
+
+
+def make_file(H: int, W: int, restart: str | None = None) -> bytes:
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     im = Image.open(os.path.join(root, "tests", "data", "pants.png")).convert("RGB").resize((W, H), Image.BILINEAR)
     buf = io.BytesIO()
-    im.save(buf, "JPEG", quality=90, subsampling=2)
+    im.save(buf, "JPEG", quality=90, subsampling=2, **restart_kw(restart))
     return buf.getvalue()
 
 
@@ -64,30 +78,35 @@ def host_prepare(data: bytes, iters: int) -> dict:
     """jpeg_scan_prepare -- all the host does for the device entropy decode -- into a reused buffer."""
     from kdl.ops import _lib
     rt = _lib.rt()
-    out = np.empty(rt.jpeg_prepare_bound(len(data)), np.uint8)
+    from kdl.serving.jpeg import _intervals
+    out = np.empty(rt.jpeg_prepare_bound(len(data), _intervals(data, rt.jpeg_probe(data)[1])), np.uint8)
     st, hd, info = rt.jpeg_scan_prepare(data, out)
-    assert st == rt.JPEG_OK and info.device_ok, hd.why
+    assert st == rt.JPEG_OK and (info.device_ok or info.restart_ok), hd.why
     prep = _median_us(lambda: rt.jpeg_scan_prepare(data, out), iters)
-    return {"jpeg_scan_prepare_us": round(prep, 1), "staged_bytes": info.nbytes, "coefficient_bytes": 2 * hd.ncoef}
+    res = {"jpeg_scan_prepare_us": round(prep, 1), "staged_bytes": info.nbytes, "coefficient_bytes": 2 * hd.ncoef}
+    if info.restart_ok:
+        res.update(restart_interval=info.ri, intervals=info.nint, groups=info.ngroup)
+    return res
 
 
 def entropy_kernels(data: bytes, n: int, iters: int) -> dict:
-    """Device-event times of jpeg_huff_decode, jpeg_dc_scan and jpeg_idct_u8 over ``n`` copies."""
+    """Device-event times of jpeg_huff_decode, jpeg_dc_scan and jpeg_idct_u8 over ``n`` copies; of
+    jpeg_huff_rst_decode and jpeg_dc_rst_scan for a file with restart intervals."""
     import torch
 
     from kdl.ops import _lib
     if not torch.cuda.is_available():
         raise SystemExit("--kernels needs a GPU")
-    from kdl.serving.jpeg import CallLayout
+    from kdl.serving.jpeg import CallLayout, _intervals
     rt, C = _lib.rt(), _lib.lib()
     st, hd = rt.jpeg_probe(data)
     assert st == rt.JPEG_OK, hd.why
-    lay = CallLayout([hd.ncoef] * n, [rt.jpeg_prepare_bound(len(data))] * n)
+    lay = CallLayout([hd.ncoef] * n, [rt.jpeg_prepare_bound(len(data), _intervals(data, hd))] * n)
     hin = np.zeros(lay.nbytes, np.uint8)
     idx = torch.zeros(1, dtype=torch.int32, device="cuda")      # jpeg_idct_u8 reads no resize table
     for k in range(n):
         st, h, info = rt.jpeg_scan_prepare(data, lay.prep(hin, k))
-        assert st == rt.JPEG_OK and info.device_ok
+        assert st == rt.JPEG_OK and (info.device_ok or info.restart_ok)
         lay.add(hin, k, h, k, idx, idx)
         lay.add_huff(hin, k, h, info)
     d_in = torch.from_numpy(hin).cuda()
@@ -95,14 +114,17 @@ def entropy_kernels(data: bytes, n: int, iters: int) -> dict:
     planes = torch.empty(lay.ncoef, dtype=torch.uint8, device="cuda")
     out = torch.empty((n, 1, 1, 3), dtype=torch.uint8, device="cuda")
     status = torch.zeros(2 * n, dtype=torch.int32, device="cuda")
-    ha = lay.huff_args(hin.ctypes.data, d_in.data_ptr(), coef.data_ptr(), status.data_ptr(), 2 * n)
+    rst = bool(info.restart_ok)
+    ha = (lay.huff_rst_args if rst else lay.huff_args)(hin.ctypes.data, d_in.data_ptr(), coef.data_ptr(),
+                                                       status.data_ptr(), 2 * n)
+    huff, dc = (C.jpeg_huff_rst_decode, C.jpeg_dc_rst_scan) if rst else (C.jpeg_huff_decode, C.jpeg_dc_scan)
     ia = lay.args(hin.ctypes.data, d_in.data_ptr(), planes.data_ptr(), lay.ncoef, out.data_ptr(), n, 1, 1,
                   coef=coef.data_ptr())
     s = torch.cuda.current_stream().cuda_stream
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(iters)]
 
     def once(e=None):
-        for i, fn in enumerate((lambda: C.jpeg_huff_decode(ha, s), lambda: C.jpeg_dc_scan(ha, s),
+        for i, fn in enumerate((lambda: huff(ha, s), lambda: dc(ha, s),
                                 lambda: C.jpeg_idct_u8(ia, s))):
             if e:
                 e[i].record()
@@ -118,8 +140,9 @@ def entropy_kernels(data: bytes, n: int, iters: int) -> dict:
     st = status.cpu().numpy().reshape(n, 2)
     assert not st[:, 0].any(), "the device decoder rejected the benchmark's own file"
     us = [round(statistics.median(e[i].elapsed_time(e[i + 1]) for e in ev) * 1e3, 1) for i in range(3)]
-    return {"images": n, "sub_bits": rt.JPEG_HUFF_SUB_BITS, "chunk": rt.JPEG_HUFF_CHUNK,
-            "chunks_per_image": -(-info.nbits // (rt.JPEG_HUFF_SUB_BITS * rt.JPEG_HUFF_CHUNK)),
+    shape = ({"intervals": info.nint, "groups_per_image": info.ngroup} if rst else
+             {"chunks_per_image": -(-info.nbits // (rt.JPEG_HUFF_SUB_BITS * rt.JPEG_HUFF_CHUNK))})
+    return {"images": n, "sub_bits": rt.JPEG_HUFF_SUB_BITS, "chunk": rt.JPEG_HUFF_CHUNK, **shape,
             "most_rounds_of_a_chunk": int(st[:, 1].max()), "huff_decode_us": us[0], "dc_scan_us": us[1],
             "idct_us": us[2], "entropy_us_per_image": round((us[0] + us[1]) / n, 2)}
 
@@ -178,9 +201,12 @@ def main(argv=None) -> int:
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--entropy", choices=["host", "gpu"], default="host",
                     help="gpu: also time jpeg_scan_prepare and, with --kernels, the device entropy decode")
+    ap.add_argument("--restart", default=None, metavar="rows:N|blocks:N",
+                    help="encode the file with restart markers every N MCU rows / N MCUs; with --entropy gpu the "
+                         "restart kernels are timed, and the plain ones on the file without markers beside them")
     a = ap.parse_args(argv)
     H, W = map(int, a.size.split("x"))
-    data = make_file(H, W)
+    data = make_file(H, W, a.restart)
     res = {"size": a.size, **host(data, a.iters)}
     if a.entropy == "gpu":
         res.update(host_prepare(data, a.iters))
@@ -189,6 +215,8 @@ def main(argv=None) -> int:
         res["kernels"] = kernels(data, a.images, a.iters)
         if a.entropy == "gpu":
             res["entropy_kernels"] = entropy_kernels(data, a.images, a.iters)
+            if a.restart:
+                res["yardstick_entropy_kernels"] = entropy_kernels(make_file(H, W), a.images, a.iters)
     print(json.dumps(res), flush=True)
     return 0
 

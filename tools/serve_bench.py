@@ -69,7 +69,13 @@ def _build_request(a) -> bytes:
         root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
         im = Image.open(os.path.join(root, "tests", "data", "pants.png")).convert("RGB").resize((W, H), Image.BILINEAR)
         buf = io.BytesIO()
-        im.save(buf, "JPEG", quality=90, subsampling=2)
+        restart = {}
+        if a.restart:                   # rows:N | blocks:N -> restart markers every N MCU rows / N MCUs
+            kind, _, num = a.restart.partition(":")
+            if kind not in ("rows", "blocks") or not num.isdigit() or int(num) < 1:
+                raise SystemExit(f"--restart {a.restart!r}: expected rows:N or blocks:N")
+            restart = {f"restart_marker_{kind}": int(num)}
+        im.save(buf, "JPEG", quality=90, subsampling=2, **restart)
         data = buf.getvalue()
         if a.signature == "serving_bytes":
             return make_request([data] * a.images, signature=a.signature, input_key="image_bytes").SerializeToString()
@@ -137,7 +143,10 @@ def main(argv=None) -> int:
                          "serving_bytes, its decoded pixels for serving_image (random: seeded uniform pixels)")
     ap.add_argument("--image-size", default="534x400",
                     help="serving_image: HxW of the raw uint8 images the clients send (resized on the server)")
-    ap.add_argument("--entropy", choices=["host", "gpu"], default=os.environ.get("KDL_JPEG_ENTROPY") or "host",
+    ap.add_argument("--restart", default=None, metavar="rows:N|blocks:N",
+                    help="--payload jpeg: encode the file with restart markers every N MCU rows / N MCUs (what "
+                         "--entropy gpu_rst decodes on the device)")
+    ap.add_argument("--entropy", choices=["host", "gpu", "gpu_rst"], default=os.environ.get("KDL_JPEG_ENTROPY") or "host",
                     help="serving_bytes: where the JPEG scans are Huffman-decoded (the server's --jpeg_entropy; "
                          "default: env KDL_JPEG_ENTROPY, else host)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,6 +275,8 @@ def main(argv=None) -> int:
         if a.signature in ("serving_image", "serving_bytes"):
             res["image_size"] = a.image_size
             res["payload"] = a.payload
+            if a.restart:
+                res["restart"] = a.restart
             res["request_bytes"] = len(req)
             res["resize_into_device_slot"] = bool(getattr(run, "device_path", False))
         if a.signature == "serving_bytes":
