@@ -72,6 +72,15 @@ StemArgs stem_args(const py::dict& d) {
   a.rows = I(d, "rows", 0);
   return a;
 }
+StemConvArgs stem_conv_args(const py::dict& d) {
+  StemConvArgs a{};
+  a.x = P<const uint8_t>(d, "x"); a.wp1 = P<const uint16_t>(d, "wp1"); a.b1 = P<const float>(d, "b1");
+  a.wp2 = P<const uint16_t>(d, "wp2"); a.b2 = P<const float>(d, "b2"); a.y = P<uint16_t>(d, "y");
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.H1 = I(d, "H1"); a.W1 = I(d, "W1");
+  a.OH = I(d, "OH"); a.OW = I(d, "OW"); a.ldy = I(d, "ldy"); a.NF = I(d, "NF"); a.nstore = I(d, "nstore");
+  a.relu_out = I(d, "relu_out"); a.grid = I(d, "grid");
+  return a;
+}
 GapArgs gap_args(const py::dict& d) {
   GapArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.y = P<float>(d, "y"); a.yb = P<uint16_t>(d, "yb");
@@ -278,6 +287,16 @@ PYBIND11_MODULE(_C, m) {
     const auto a = stem_args(d);
     py::gil_scoped_release nogil;
     chk(stem_conv(a, S(s)), "stem_conv");
+  });
+  m.def("stem_conv3x3", [](int cfg, py::dict d, uintptr_t s) {
+    const auto a = stem_conv_args(d);
+    py::gil_scoped_release nogil;
+    chk(stem_conv3x3(cfg, a, S(s)), "stem_conv3x3");
+  });
+  m.def("stem_conv3x3_config", [](int cfg) {
+    int bm = 0, bn = 0, th = 0;
+    if (stem_conv3x3_config(cfg, &bm, &bn, &th) != 0) throw std::out_of_range("bad stem_conv3x3 config");
+    return py::make_tuple(bm, bn, th);
   });
   m.def("pool_add", [](py::dict d, uintptr_t s) {
     const auto a = pool_args(d);
@@ -593,6 +612,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_stem", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_STEM; op.name = name; op.st = stem_args(d); p.add(op);
+      })
+      .def("add_stem_conv", [](Program& p, const std::string& name, int cfg, py::dict d) {
+        Op op; op.kind = OP_STEM_CONV; op.name = name; op.cfg = cfg; op.sc = stem_conv_args(d); p.add(op);
       })
       .def("add_pool_add", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_POOL_ADD; op.name = name; op.pa = pool_args(d); p.add(op);

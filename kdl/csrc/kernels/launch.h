@@ -146,6 +146,28 @@ struct StemArgs {
 };
 hipError_t stem_conv(const StemArgs& a, hipStream_t s);
 
+// Xception block1_conv1 + block1_conv2 in one launch (stem_conv3x3.hip): the 3x3/2 'valid' stem
+// (uint8 image, 3 -> 32, bias + ReLU; normalisation folded into the weights) is computed per tile
+// of the following 3x3 'valid' stride-1 conv (32 -> NF*16, bias, optional ReLU); the 32-channel
+// map in between lives only in LDS. Same values as stem_conv (rows = 1) followed by conv3x3_2d.
+struct StemConvArgs {
+  const uint8_t* x;       // [B][H][W][3] uint8
+  const uint16_t* wp1;    // stem weights, packed [2][2][64][8], row-run K layout (k = ky*16 + kx*3 + c)
+  const float* b1;        // [32]
+  const uint16_t* wp2;    // second conv, packed [NF][9][64][8] (k = tap*32 + c)
+  const float* b2;        // [NF*16]
+  uint16_t* y;            // [B][OH][OW][ldy] bf16
+  int B, H, W;            // image
+  int H1, W1;             // stem map: (H-3)/2+1, (W-3)/2+1
+  int OH, OW;             // output: H1-2, W1-2
+  int ldy, NF, nstore;    // output channel stride; 16-wide fragments in wp2; channels written
+  int relu_out;           // 0 none, 1 ReLU
+  int grid;               // cap on the workgroups (0 = every resident workgroup of the chip)
+};
+// cfg: KDL_SC3_CONFIGS (tile of conv3x3_2d's config 7; producer waves / ring depth)
+hipError_t stem_conv3x3(int cfg, const StemConvArgs& a, hipStream_t s);
+int stem_conv3x3_config(int cfg, int* bm, int* bn, int* threads);
+
 // TF-'same' 3x3/2 max-pool of `x` plus `res` (Xception entry/exit block tail).
 struct PoolAddArgs {
   const uint16_t* x;      // [B][H][W][C]

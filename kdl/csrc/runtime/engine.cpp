@@ -29,6 +29,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_CHSCALE: return channel_scale(op.cs, s);
     case OP_GEMM_F8: return gemm_f8(op.cfg, op.f8, s);
     case OP_ENTRY_BLOCK: return entry_block(op.cfg, op.eb, s);
+    case OP_STEM_CONV: return stem_conv3x3(op.cfg, op.sc, s);
   }
   return hipErrorInvalidValue;
 }

@@ -2,7 +2,9 @@
 
 Walks ``kdl.models.xception.SPEC`` and lowers it to fused HIP launches:
 
-    stem_conv            block1_conv1 + BN + ReLU (normalisation folded, uint8 in)
+    stem_conv3x3         block1_conv1 + BN + ReLU (normalisation folded, uint8 in) computed per tile of
+                         block1_conv2 3x3 + BN + ReLU in ONE launch (stem_conv3x3.hip; KDL_STEM_FUSED)
+    stem_conv            ... or, with KDL_STEM_FUSED=0 / f32 input, block1_conv1 on its own, then
     conv_gemm MODE_CONV  block1_conv2 3x3 + BN + ReLU (implicit GEMM)
     conv_gemm MODE_DW    every SeparableConv2D + BN (+ReLU in/out)(+residual add)
     conv_gemm MODE_PW    residual 1x1/2 convs + BN
@@ -11,7 +13,7 @@ Walks ``kdl.models.xception.SPEC`` and lowers it to fused HIP launches:
                          as ONE persistent launch each (kdl/ops/entry_block.py; KDL_ENTRY_BLOCK)
     head_dense           GAP -> Dense(100)+ReLU -> Dense(10) logits
 
-= 44 launches per forward with the tuned table (vs ~168 unfused TF ops; split
+= 42 launches per forward with the tuned table (vs ~168 unfused TF ops; split
 separable convs count twice: depthwise + GEMM), captured into
 one hipGraph per batch bucket. All buffers are allocated once for the largest
 bucket (static memory plan); smaller buckets use prefixes of the same buffers.
@@ -31,6 +33,10 @@ from ..ops import _lib
 from ..ops.conv import MODE_CONV, MODE_DW, MODE_PW, ConvGemmLayer, Geometry, conv_weights_nk
 from ..ops.pack import bn_scale_shift, pack_fragments, round_up, rowrun_weights
 from .base import EngineBase, Step
+
+
+STEM_FUSED_NAME = "block1_stem_conv"   # the fused block1_conv1 + block1_conv2 step (and its tuning key)
+STEM_FUSED_CONFIGS = 4                 # KDL_SC3_CONFIGS in stem_conv3x3.hip
 
 
 class XceptionEngine(EngineBase):
@@ -84,15 +90,26 @@ class XceptionEngine(EngineBase):
         else:
             self.stem_wp = pack_fragments(w, 2, 1).to(dev).contiguous()
         self.stem_bias = bias.float().to(dev)
-        self.steps.append(Step("stem", c1.name, src="input", dst="stem1", geom=(S, S, oh1, oh1)))
-        self.shapes["stem1"] = (oh1, oh1, 32)
         # --- stem 2: 3x3 valid 32 -> 64 implicit GEMM
         c2 = st[0].main[1]
         s, t = bn_scale_shift(p, c2.bn)
         w = conv_weights_nk(p[f"{c2.name}/kernel"], 32) * s[:, None]
         lay = ConvGemmLayer(c2.name, MODE_CONV, w, t, cin_pad=32, n=64, relu_out=True, device=dev)
         h = oh1 - 2
-        self.steps.append(Step("conv", c2.name, lay, "stem1", "stem2", geom=(oh1, oh1, h, h)))
+        # KDL_STEM_FUSED (default on; uint8 row-run stem only): both convs in ONE launch
+        # (stem_conv3x3.hip) -- the stem is computed per tile of block1_conv2 into its LDS patch, so
+        # the 32-channel stem1 map is neither allocated, written nor read back; bit-identical to the
+        # two launches ("0"). KDL_STEM_FUSED_CFG / the tuning table's optional "block1_stem_conv"
+        # entry pick the kernel config (producer waves, ring depth).
+        self.stem_fused = self.stem_rows and os.environ.get("KDL_STEM_FUSED", "1") != "0"
+        self.stem_fused_cfg = int(os.environ.get("KDL_STEM_FUSED_CFG", "0"))
+        if self.stem_fused:
+            self.steps.append(Step("stemconv", STEM_FUSED_NAME, lay, "input", "stem2", geom=(S, S, h, h),
+                                   extra=dict(h1=oh1)))
+        else:
+            self.steps.append(Step("stem", c1.name, src="input", dst="stem1", geom=(S, S, oh1, oh1)))
+            self.shapes["stem1"] = (oh1, oh1, 32)
+            self.steps.append(Step("conv", c2.name, lay, "stem1", "stem2", geom=(oh1, oh1, h, h)))
         self.shapes["stem2"] = (h, h, 64)
         cur, H = "stem2", h
         for bi, blk in enumerate(st[1:], start=1):
@@ -227,6 +244,13 @@ class XceptionEngine(EngineBase):
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
 
 
+    def apply_tuning(self, d: dict) -> None:
+        """The conv layers' table plus the optional fused-stem entry (an int: stem_conv3x3 config)."""
+        v = d.get(STEM_FUSED_NAME)
+        if isinstance(v, int) and 0 <= v < STEM_FUSED_CONFIGS and "KDL_STEM_FUSED_CFG" not in os.environ:
+            self.stem_fused_cfg = v
+        super().apply_tuning(d)
+
     def scratch_buffers(self) -> list[str]:
         """Buffers a step uses that are not its src / dst / res (stages.py privatises them)."""
         return ["__dwtmp"]
@@ -238,6 +262,14 @@ class XceptionEngine(EngineBase):
                                           bias=_lib.ptr(self.stem_bias), y=self._ptr(step.dst),
                                           B=b, H=H, W=W, OH=OH, OW=OW, ldy=32,
                                           in_kind=0 if self.in_kind == "u8" else 1, rows=int(self.stem_rows)))
+        elif step.kind == "stemconv":
+            lay, h1 = step.layer, step.extra["h1"]
+            assert lay.nf_max == 4 and lay.ldy == 64, "stem_conv3x3 holds all 64 outputs in one N tile"
+            prog.add_stem_conv(step.name, self.stem_fused_cfg,
+                               dict(x=self.input_ptr(), wp1=_lib.ptr(self.stem_wp), b1=_lib.ptr(self.stem_bias),
+                                    wp2=_lib.ptr(lay.wp), b2=_lib.ptr(lay.bias), y=self._ptr(step.dst),
+                                    B=b, H=H, W=W, H1=h1, W1=h1, OH=OH, OW=OW, ldy=lay.ldy, NF=lay.nf_max,
+                                    nstore=lay.ldy, relu_out=int(lay.relu_out)))
         elif step.kind == "conv":
             self._emit_conv(prog, step, b)
         elif step.kind == "pool":
