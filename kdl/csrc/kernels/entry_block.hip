@@ -168,6 +168,56 @@ __device__ __forceinline__ void eb_dw_store(uint8_t* dst, int lane, const u32x2 
   for (int g = 0; g < 2; ++g) *(u32x2*)(dst + (p16 + 16 * (2 * g + par)) * 16 + 8 * (kb & 1)) = out[g];
 }
 
+// the block-diagonal weight operand of depthwise MFMA j (tap pair j) from a channel's 16-B entry
+__device__ __forceinline__ u32x4 eb_dw_wop(const u32x4 we, int j, const uint32_t (&sel)[2][4]) {
+  const uint32_t wd = we[j >> 1];
+  u32x4 wf;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) wf[d] = __builtin_amdgcn_perm(wd, wd, sel[j & 1][d]);
+  return wf;
+}
+
+// Row-pair form of eb_dw_mfma_vals for ONE 16-channel group: output rows r and r+1 of a 16-pixel
+// fragment. Both rows take the same five weight operands (MFMA j: tap 2j in the parity-0 lanes, 2j+1 in
+// the parity-1 lanes, counted from each row's own first input row), so a wave whose items keep their
+// channels builds them once: wop(j) -> the operand (eb_dw_wop of the entry, or its copy in registers).
+// addr(ti) -> the input of tap ti counted over the FOUR input rows r-1..r+2 (ti = 3 * row + dx, 0..11)
+// of this lane's chunk: row r+1's tap t is tap t+3. Every operand is exactly eb_dw_mfma_vals', so the
+// sums are bit-identical to it. The ten 16-B reads stay: the two rows' windows share six taps, but
+// always in the other half-wave (profiles/entry_block_rowpair.txt: 7 reads with the k-halves of row
+// r+1 exchanged changed the sums, 8 reads with v_permlane32_swap cost more VALU than the reads saved).
+// out[0] = row r, out[1] = row r+1.
+template <bool RELU, class Addr, class Wop>
+__device__ __forceinline__ void eb_dw_mfma_rowpair(Addr addr, Wop wop, int lane, u32x2 (&out)[2]) {
+  const bool par = (lane & 32) != 0;
+  u32x4 r0[5], r1[5];                                // tap operands of row r / row r+1
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {                      // tap 9 (j 4, parity 1): any tap, its weight is 0
+    r0[j] = *(const u32x4*)(par ? addr(j < 4 ? 2 * j + 1 : 8) : addr(2 * j));
+    r1[j] = *(const u32x4*)(par ? addr(j < 4 ? 2 * j + 4 : 11) : addr(2 * j + 3));
+    if constexpr (RELU) {
+#pragma unroll
+      for (int d = 0; d < 4; ++d) { r0[j][d] = relu_bf16x2(r0[j][d]); r1[j][d] = relu_bf16x2(r1[j][d]); }
+    }
+  }
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const u32x4 wf = wop(j);
+    acc0 = mfma16(__builtin_bit_cast(s16x8, wf), __builtin_bit_cast(s16x8, r0[j]), acc0);
+    acc1 = mfma16(__builtin_bit_cast(s16x8, wf), __builtin_bit_cast(s16x8, r1[j]), acc1);
+  }
+  out[0] = (u32x2){pack_bf16(acc0[0], acc0[1]), pack_bf16(acc0[2], acc0[3])};
+  out[1] = (u32x2){pack_bf16(acc1[0], acc1[1]), pack_bf16(acc1[2], acc1[3])};
+}
+
+// one channel group's C fragment [16 ch][16 px], transposed into the A fragment at dst (eb_dw_store's
+// mapping for group g)
+__device__ __forceinline__ void eb_dw_store_g(uint8_t* dst, int lane, int g, u32x2 val) {
+  const int p16 = lane & 15, kb = lane >> 4;
+  *(u32x2*)(dst + (p16 + 16 * (2 * g + (kb >> 1))) * 16 + 8 * (kb & 1)) = val;
+}
+
 // workgroup barrier for LDS hand-offs only: LDS-scoped release / acquire fences around s_barrier, so
 // the compiler orders LDS accesses around it and emits only lgkmcnt(0). __syncthreads() (a fence over
 // every address space) lowers to s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier, which drained the next
@@ -614,8 +664,9 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
 // in the same phase (the round-4 kernel: four barriers per step, ~2k cycles per phase, all of them
 // LDS-throughput bound -- profiles/entry_block_ab_r4.txt). Rings: x 8 rows (each step's DMA one
 // iteration ahead), y1 6 rows (GEMM1(i-1) writes rows R+4, R+5 of step i-2 while dw2(i-2) reads its
-// rows R..R+3), A1 / A2 double-buffered, residual rows in a 4-slot buffer (written by producers at
-// step i, read by consumers three iterations later). 13-column strips keep the map at 142 KiB
+// rows R..R+3; slots counted by steps, see yslot), A1 / A2 double-buffered, residual rows in a 4-slot
+// buffer (written by producers at step i, read by consumers three iterations later). 13-column strips
+// keep the map at 142 KiB
 // (pitch 32 px, no padding). A consumer wave owns 32 output channels of every GEMM (register-resident
 // weights); a producer wave owns a quarter of each step's depthwise units.
 template <int C0, int C1, int PC, int NWAV, int NCW = NWAV / 2>
@@ -625,6 +676,7 @@ struct EbwGeom {
   static constexpr int XROW = (C0 / 8) * PLB, Y1ROW = (C1 / 8) * PLB;
   static constexpr int KT0 = C0 / 32, KT1 = C1 / 32;
   static constexpr int Y1F = (2 * Y1C + 15) / 16, Y2FR = (Y2C + 15) / 16, Y2F = 2 * Y2FR;
+  static constexpr int Y1FR = (Y1C + 15) / 16;       // row-pair builds: y1 fragments are [row][col / 16] too
   static constexpr int NC = NCW, NP = NWAV - NCW;  // consumer / producer waves (w, w+4, ... share a SIMD)
   static constexpr int CCH = C1 / NC;                // output channels per consumer wave
   static constexpr int NSL = CCH / 16;               // 16-channel slices per consumer wave
@@ -647,7 +699,14 @@ struct EbwGeom {
 #endif
 // CDW: dw2 units per step that every consumer wave computes too (the consumers idle half of an
 // iteration while the producers' depthwise is the critical path); the producers keep the rest
-template <int C0, int C1, int PC, int NWAV, int NCW, int PT, bool RELU1, bool STAMP, int CDW = 0>
+// RP: row-pair depthwise (eb_dw_mfma_rowpair). A step's two y1 rows and its two y2 rows are adjacent,
+// so the work is dealt out as (column fragment, channel group, k-step) items that produce both rows
+// with one set of weight operands: 2 Y1FR KT0 = 8 items for dw1 (its fragments become [row][col / 16],
+// with the same 6 wasted pixels as the 58 linearised ones) and 2 Y2FR KT1 = 16 for dw2. A wave's items
+// share k-step and channel group, so the producers build their weight operands once per kernel: the
+// operand perms were a third of the producers' VALU instructions, and the SIMDs' VALU issue, not the
+// LDS, bounds an iteration (10 VALU per MFMA in config 15; profiles/entry_block_rowpair.txt).
+template <int C0, int C1, int PC, int NWAV, int NCW, int PT, bool RELU1, bool STAMP, int CDW = 0, bool RP = false>
 __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(EntryBlockArgs a) {
   using G = EbwGeom<C0, C1, PC, NWAV, NCW>;
   constexpr int KT0 = G::KT0, KT1 = G::KT1, PLB = G::PLB, XROW = G::XROW, Y1ROW = G::Y1ROW, XDMA = G::XDMA;
@@ -658,6 +717,10 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   constexpr int CU2 = CDW * NC;                      // dw2 units 0..CU2-1: consumers (units w + NC j); the rest: producers
   static_assert(CU2 % KT1 == 0 && CU2 <= U2, "consumer dw2 units keep the producers' k-step per wave");
   constexpr int U1W = (U1 + NP - 1) / NP, U2W = (U2 - CU2 + NP - 1) / NP;
+  constexpr int Y1FR = G::Y1FR;
+  static_assert(!RP || (2 * Y1FR == Y1F && NP % (2 * KT0) == 0 && NP % (2 * KT1) == 0 && NC % (2 * KT1) == 0 &&
+                        CU2 % (2 * KT1) == 0),
+                "row-pair items of a wave share one k-step and one channel group; y1 fragments [row][col / 16]");
   static_assert(PT == 1, "the residual row 2k is x row R+1 of the step (odd map size: block2)");
   // distinct LDS objects: the compiler may reorder accesses of different regions
   __shared__ __attribute__((aligned(16))) uint8_t s_x[XR * XROW];
@@ -728,6 +791,12 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
       glds16_asm(src, s_x + ((sl0 + ii / XDMA) & (XR - 1)) * XROW + d * 1024);
     }
   };
+  // y1 ring slot of row R + d (d = 0..5) of step q, R = the step's first y2 input row. Counted by STEPS, not
+  // by rows: inside a run both advance by two per step, but where a run follows another in the same
+  // workgroup, GEMM1 of the new run's first step runs in the iteration in which dw2 still reads the old
+  // run's last rows, and row numbers of different runs can share a slot (they do not for a 147-row map,
+  // where the shared slots hold rows past the bottom edge: zeros, overwritten by zeros)
+  auto yslot = [&](int q, int d) { return (2 * (q - s0) + d) % YR; };
   auto stamp = [&](int it, int ph) {
     if constexpr (STAMP) {
       if (lane == 0 && (w == 0 || w == NC) && blockIdx.x < 8 && it - s0 < 64 && a.stamps)
@@ -742,7 +811,21 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   // The two roles run separate loops with the same trip count and one barrier per iteration (s_barrier
   // counts arrivals, not program counters): each role's registers are live in its own loop only, so
   // the consumers' register-resident weights do not sit in the producers' allocation (and the reverse)
+  // RP: the 16-B weight entry of item (k-step tq, group g) for this lane's channel and tap parity
+  auto rp_ent = [&](int tq, int g) {
+    return *(const u32x4*)(s_dw + tq * 1024 + ((g * 16 + p16) * 2 + (q16 >> 1)) * 16);
+  };
   if (!consumer) {
+    // RP: a producer's items keep (k-step, group), so the weight operands of its dw1 and dw2 items stay
+    // in registers for the whole kernel: 2 x 5 x 4 VGPRs (the producers have them to spare) instead of
+    // 20 perms per single-row unit in every iteration
+    u32x4 wk1[RP ? 5 : 1], wk2[RP ? 5 : 1];
+    if constexpr (RP) {
+      const u32x4 e1 = rp_ent((w - NC) % KT0, ((w - NC) / KT0) & 1);
+      const u32x4 e2 = rp_ent(KT0 + (w - NC) % KT1, ((w - NC) / KT1) & 1);
+#pragma unroll
+      for (int j = 0; j < 5; ++j) { wk1[j] = eb_dw_wop(e1, j, sel); wk2[j] = eb_dw_wop(e2, j, sel); }
+    }
     dma_for(s0);
     for (int it = s0; it < s1 + 3; ++it) {
       // step `it`'s x rows (their DMA, issued last iteration) must have landed
@@ -767,6 +850,16 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 #pragma unroll
         for (int i = 0; i < U1W; ++i) {
           const int u = pw + NP * i;
+          if constexpr (RP) {
+            if (u < U1) {                            // item (column fragment cf, group g1, k-step t1): rows R+2, R+3
+              const int g1 = (pw / KT0) & 1, cf = u / (2 * KT0);
+              const int col = min(cf * 16 + p16, Y1C - 1);
+              const uint8_t* base = s_x + (4 * t1 + 2 * g1 + (q16 & 1)) * PLB + col * 16;
+              auto addr = [&](int ti) { return base + ((xs + ti / 3) & (XR - 1)) * XROW + (ti % 3) * 16; };
+              eb_dw_mfma_rowpair<RELU1>(addr, [&](int j) { return wk1[j]; }, lane, dv1[i]);
+              d1[i] = A1 + (t1 * Y1F + cf) * 1024;
+            }
+          } else
           if (u < U1) {
             const int f = u / KT0;
             int pi = 16 * f + p16;
@@ -803,14 +896,21 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 #pragma unroll
           for (int i = 0; i < U2W; ++i) {
             const int u = CU2 + pw + NP * i;
+            if constexpr (RP) {
+              if (u < U2) {                          // item (cf, g2, t2): y2 rows R+1, R+2 from y1 rows R..R+3
+                const int g2 = (pw / KT1) & 1, cf = u / (2 * KT1);
+                const uint8_t* base = s_y1 + (4 * t2 + 2 * g2 + (q16 & 1)) * PLB + (cf * 16 + p16) * 16;
+                auto addr = [&](int ti) { return base + yslot(it - 2, ti / 3) * Y1ROW + (ti % 3) * 16; };
+                eb_dw_mfma_rowpair<false>(addr, [&](int j) { return wk2[j]; }, lane, dv2[i]);
+                d2[i] = A2 + (t2 * Y2F + cf) * 1024;
+              }
+            } else
             if (u < U2) {
               const int f = u / KT1;
               const int rr = f / Y2FR, col = (f % Y2FR) * 16 + p16;
-              const int row = R + 1 + rr;
               const uint8_t* base = s_y1 + (4 * t2 + (q16 & 1)) * PLB + col * 16;
               auto tap = [&](int g, int ti) {
-                const int yr = row - 1 + ti / 3;
-                return *(const u32x4*)(base + 2 * g * PLB + ((yr % YR + YR) % YR) * Y1ROW + (ti % 3) * 16);
+                return *(const u32x4*)(base + 2 * g * PLB + yslot(it - 2, rr + ti / 3) * Y1ROW + (ti % 3) * 16);
               };
               auto ent = [&](int g) {
                 return *(const u32x4*)(s_dw + (KT0 + t2) * 1024 + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
@@ -825,12 +925,27 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
           }
         }
       }
+      if constexpr (RP) {                            // dv[row]: the row r+1 fragment lies a fragment row further
 #pragma unroll
-      for (int i = 0; i < U1W; ++i)
-        if (d1[i]) eb_dw_store(d1[i], lane, dv1[i]);
+        for (int i = 0; i < U1W; ++i)
+          if (d1[i]) {
+            eb_dw_store_g(d1[i], lane, (pw / KT0) & 1, dv1[i][0]);
+            eb_dw_store_g(d1[i] + Y1FR * 1024, lane, (pw / KT0) & 1, dv1[i][1]);
+          }
 #pragma unroll
-      for (int i = 0; i < U2W; ++i)
-        if (d2[i]) eb_dw_store(d2[i], lane, dv2[i]);
+        for (int i = 0; i < U2W; ++i)
+          if (d2[i]) {
+            eb_dw_store_g(d2[i], lane, (pw / KT1) & 1, dv2[i][0]);
+            eb_dw_store_g(d2[i] + Y2FR * 1024, lane, (pw / KT1) & 1, dv2[i][1]);
+          }
+      } else {
+#pragma unroll
+        for (int i = 0; i < U1W; ++i)
+          if (d1[i]) eb_dw_store(d1[i], lane, dv1[i]);
+#pragma unroll
+        for (int i = 0; i < U2W; ++i)
+          if (d2[i]) eb_dw_store(d2[i], lane, dv2[i]);
+      }
       stamp(it, 3);
     }
   } else {
@@ -863,11 +978,9 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
             auto unit = [&](int u) {
               const int f = u / KT1;
               const int rr = f / Y2FR, col = (f % Y2FR) * 16 + p16;
-              const int row = R + 1 + rr;
               const uint8_t* base = s_y1 + (4 * t2 + (q16 & 1)) * PLB + col * 16;
               auto tap = [&](int g, int ti) {
-                const int yr = row - 1 + ti / 3;
-                return *(const u32x4*)(base + 2 * g * PLB + ((yr % YR + YR) % YR) * Y1ROW + (ti % 3) * 16);
+                return *(const u32x4*)(base + 2 * g * PLB + yslot(it - 2, rr + ti / 3) * Y1ROW + (ti % 3) * 16);
               };
               auto ent = [&](int g) {
                 return *(const u32x4*)(s_dw + (KT0 + t2) * 1024 + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
@@ -876,8 +989,24 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
               eb_dw_mfma_vals<false>(tap, ent, lane, sel, dv);
               eb_dw_store(s_a2 + (it & 1) * G::A2B + (t2 * Y2F + f) * 1024, lane, dv);
             };
-            unit(w);
-            if constexpr (CDW > 1) unit(w + NC);
+            auto item = [&](int u) {                 // RP: item (cf, g2, t2), both rows
+              const int g2 = (w / KT1) & 1, cf = u / (2 * KT1);
+              const uint8_t* base = s_y1 + (4 * t2 + 2 * g2 + (q16 & 1)) * PLB + (cf * 16 + p16) * 16;
+              auto addr = [&](int ti) { return base + yslot(it - 2, ti / 3) * Y1ROW + (ti % 3) * 16; };
+              const u32x4 e = rp_ent(KT0 + t2, g2);
+              u32x2 dv[2];
+              eb_dw_mfma_rowpair<false>(addr, [&](int j) { return eb_dw_wop(e, j, sel); }, lane, dv);
+              uint8_t* const dst = s_a2 + (it & 1) * G::A2B + (t2 * Y2F + cf) * 1024;
+              eb_dw_store_g(dst, lane, g2, dv[0]);
+              eb_dw_store_g(dst + Y2FR * 1024, lane, g2, dv[1]);
+            };
+            if constexpr (RP) {
+              item(w);
+              if constexpr (CDW > 1) item(w + NC);
+            } else {
+              unit(w);
+              if constexpr (CDW > 1) unit(w + NC);
+            }
           }
         }
       }
@@ -889,8 +1018,10 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
         const uint8_t* const A1 = s_a1 + ((it - 1) & 1) * G::A1B;
 #pragma unroll
         for (int f = 0; f < Y1F; ++f) {
-          const int pi = 16 * f + p16;
-          const int rr = pi >= Y1C, col = pi - rr * Y1C;
+          // fragment f: 16 of the two rows' 2 Y1C linearised pixels, or (RP) columns 16 (f % Y1FR).. of row f / Y1FR
+          const int pi = RP ? (f % Y1FR) * 16 + p16 : 16 * f + p16;
+          const int rr = RP ? f / Y1FR : pi >= Y1C, col = RP ? pi : pi - rr * Y1C;
+          const bool live = pi < (RP ? Y1C : 2 * Y1C);
           const int row = R + 2 + rr, gcol = 2 * pc0 - PT - 1 + col;
           const bool ok = (unsigned)row < (unsigned)H && (unsigned)gcol < (unsigned)W;
           s16x8 af[KT0];
@@ -901,13 +1032,13 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < KT0; ++t) acc = mfma16(w1[n][t], af[t], acc);
-            if (pi < 2 * Y1C) {
+            if (live) {
               const int c = CCH * w + 16 * n + 4 * q16;
               const float4 bv = bz[0][n];
               const float v0 = fmaxf(acc[0] + bv.x, 0.f), v1 = fmaxf(acc[1] + bv.y, 0.f);
               const float v2 = fmaxf(acc[2] + bv.z, 0.f), v3 = fmaxf(acc[3] + bv.w, 0.f);
               const u32x2 o = ok ? (u32x2){pack_bf16(v0, v1), pack_bf16(v2, v3)} : (u32x2){0u, 0u};
-              *(u32x2*)(s_y1 + ((row % YR + YR) % YR) * Y1ROW + (c / 8) * PLB + col * 16 + (c & 7) * 2) = o;
+              *(u32x2*)(s_y1 + yslot(it - 1, 2 + rr) * Y1ROW + (c / 8) * PLB + col * 16 + (c & 7) * 2) = o;
             }
           }
         }
@@ -1018,11 +1149,27 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 // 4 consumer + 12 producer waves (227.0 us: the 32-channel consumers spill 32 VGPRs), two dw2 units per
 // consumer (215.8 us: consumers 6,168 busy with 14 VGPRs spilled), and the residual-row copy moved to the
 // consumers as well (iteration 6,732 vs 6,676, bench -0.2 %).
+// 17 / 117 (block2's default), 19 / 119: configs 13 / 15 with the row-pair depthwise (RP): a step's two
+// rows per item, the producers' weight operands built once per kernel. Bit-identical to config 15
+// (tests/test_entry_block_rowpair_gpu.py; the bench logits equal the parent build's). One lease
+// (profiles/entry_block_rowpair.txt): config 15 iteration 6,440 cycles (producers 5,364, consumers 4,522),
+// 17: 5,324 (4,770 / 3,544), 19: 5,652 (4,220 / 4,456); in the step 191.2 -> 163.4 us, VALU per MFMA
+// 9.9 -> 7.1; bench +2.4 % in 12 of 12 interleaved pairs (A spread 0.64 %). The consumers' dw2 item of
+// config 19 no longer pays: it rebuilds its operands every iteration (no registers to keep them) on
+// SIMDs whose VALU issue is the limit. Measured and removed: sharing the tap READS between the two rows
+// (7 reads with row r+1's k-halves exchanged: iteration 6,176, but the MFMA sum depends on the half a
+// product sits in -- block outputs equal on small maps, bench logits off by 7.6e-3; 8 reads with
+// v_permlane32_swap: bit-identical, iteration 6,472: 24 swaps / selects + 16 copies per item cost more
+// than two reads), and block3 (VALU depthwise) was not changed: see the same file.
 #define KDL_EBW_CONFIGS(X) \
-  X(13, 64, 128, 13, 16, 8, 1, false, 0) \
-  X(15, 64, 128, 13, 16, 8, 1, false, 1) \
-  X(113, 64, 128, 13, 16, 8, 1, false, 0) \
-  X(115, 64, 128, 13, 16, 8, 1, false, 1)
+  X(13, 64, 128, 13, 16, 8, 1, false, 0, false) \
+  X(15, 64, 128, 13, 16, 8, 1, false, 1, false) \
+  X(17, 64, 128, 13, 16, 8, 1, false, 0, true) \
+  X(19, 64, 128, 13, 16, 8, 1, false, 1, true) \
+  X(113, 64, 128, 13, 16, 8, 1, false, 0, false) \
+  X(115, 64, 128, 13, 16, 8, 1, false, 1, false) \
+  X(117, 64, 128, 13, 16, 8, 1, false, 0, true) \
+  X(119, 64, 128, 13, 16, 8, 1, false, 1, true)
 
 #define KDL_EB_CONFIGS(X)                          \
   X(0, 64, 128, 15, 1, 1, false, false, 1)         \
@@ -1042,7 +1189,7 @@ int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds, int* occ) {
   case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbGeom<c0_, c1_, pc_, nfw, dwm>::BYTES; *occ = occ_; return 0;
     KDL_EB_CONFIGS(KDL_EBINFO)
 #undef KDL_EBINFO
-#define KDL_EBWINFO(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw) \
+#define KDL_EBWINFO(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) \
   case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbwGeom<c0_, c1_, pc_, nw, nc>::BYTES; *occ = 1; return 0;
     KDL_EBW_CONFIGS(KDL_EBWINFO)
 #undef KDL_EBWINFO
@@ -1055,7 +1202,7 @@ static int eb_pad(int cfg) {
 #define KDL_EBPAD(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_) case id: return pt;
     KDL_EB_CONFIGS(KDL_EBPAD)
 #undef KDL_EBPAD
-#define KDL_EBWPAD(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw) case id: return pt;
+#define KDL_EBWPAD(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) case id: return pt;
     KDL_EBW_CONFIGS(KDL_EBWPAD)
 #undef KDL_EBWPAD
     default: return -1;
@@ -1065,7 +1212,7 @@ static int eb_pad(int cfg) {
 hipError_t entry_block(int cfg, const EntryBlockArgs& a, hipStream_t s) {
   int c0, c1, pc, lds, occ;
   if (entry_block_config(cfg, &c0, &c1, &pc, &lds, &occ) != 0 || a.ldx != c0 || a.ldy != c1 || a.grid < 1 ||
-      a.OH != (a.H - 1) / 2 + 1 || a.OW != (a.W - 1) / 2 + 1 || a.H != a.W || !a.steps || !a.step_off ||
+      a.OH != (a.H - 1) / 2 + 1 || a.OW != (a.W - 1) / 2 + 1 || a.H % 2 != a.W % 2 || !a.steps || !a.step_off ||
       a.B > 256)                                     // the packed LDS step word holds an 8-bit image index
     return hipErrorInvalidValue;
   if (eb_pad(cfg) != (a.H % 2)) return hipErrorInvalidValue;   // TF 'same': leading pad 1 iff odd size
@@ -1077,9 +1224,9 @@ hipError_t entry_block(int cfg, const EntryBlockArgs& a, hipStream_t s) {
     break;
     KDL_EB_CONFIGS(KDL_EBCASE)
 #undef KDL_EBCASE
-#define KDL_EBWCASE(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw)                                                      \
+#define KDL_EBWCASE(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp)                                                  \
   case id:                                                                                            \
-    hipLaunchKernelGGL((entry_block_ws_kernel<c0_, c1_, pc_, nw, nc, pt, r_, (id >= 100), cdw>), dim3(a.grid),  \
+    hipLaunchKernelGGL((entry_block_ws_kernel<c0_, c1_, pc_, nw, nc, pt, r_, (id >= 100), cdw, rp>), dim3(a.grid), \
                        dim3(64 * nw), 0, s, a);   /* static LDS */                                   \
     break;
     KDL_EBW_CONFIGS(KDL_EBWCASE)

@@ -1,7 +1,7 @@
 """Fused entry block vs the unfused lowering, per-op device times at batch B (one MI355X);
 ``--stamps``: per-phase s_memtime profile of the fused kernel (stamping build, config 100 + id).
 
-    python tools/ebbench.py [--batch 32] [--iters 20] [--blocks 2,3] [--stamps]
+    python tools/ebbench.py [--batch 32] [--iters 20] [--blocks 2,3] [--stamps [--cfgs 15,19]]
 """
 import argparse
 import os
@@ -13,7 +13,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def stamps(p, blocks, B):
+def stamps(p, blocks, B, only=None):
     import torch
     from kdl.engine.xception import XceptionEngine as XE
     from kdl.models import xception as X
@@ -23,7 +23,8 @@ def stamps(p, blocks, B):
         b = X.SPEC[blk - 1]
         s1, s2, r = XE._sep(p, b.main[0], "cuda"), XE._sep(p, b.main[1], "cuda"), XE._pw(p, b.res_conv, "cuda")
         H, C0 = geom[blk]
-        cfgs = [2, 13, 15] if blk == 2 else [1]
+        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1]      # 17 / 19: 13 / 15 with the row-pair depthwise
+        cfgs = [c for c in cfgs if only is None or c in only]
         for cfg in [c for b in cfgs for c in (b, 100 + b)]:
             eb = EntryBlock(f"block{blk}", s1, s2, r, cfg=cfg)
             x = torch.randn(B, H, H, C0, device="cuda").to(torch.bfloat16)
@@ -45,7 +46,7 @@ def stamps(p, blocks, B):
             if cfg < 100:
                 continue
             v = st.view(8, 64, 5).cpu().tolist()
-            if cfg in (113, 115):      # warp-specialized: [consumer start, consumer end, producer start, producer end]
+            if cfg in (113, 115, 117, 119):      # warp-specialized: [consumer start, consumer end, producer start, producer end]
                 ph = {n: [] for n in ("iteration", "consumers busy", "producers busy")}
                 for wg in range(8):
                     for k in range(3, 62):
@@ -85,6 +86,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--blocks", default="2,3")
     ap.add_argument("--stamps", action="store_true")
+    ap.add_argument("--cfgs", default=None, help="--stamps: only these kernel configs")
     a = ap.parse_args()
     import torch
     from kdl.engine.tuning import tuning_path
@@ -92,7 +94,7 @@ def main():
     from kdl.models import xception as X
     p = X.init_params(seed=0)
     if a.stamps:
-        stamps(p, [int(b) for b in a.blocks.split(",")], a.batch)
+        stamps(p, [int(b) for b in a.blocks.split(",")], a.batch, [int(c) for c in a.cfgs.split(",")] if a.cfgs else None)
         return
     for fused in ("0", a.blocks):
         os.environ["KDL_ENTRY_BLOCK"] = fused
