@@ -30,12 +30,17 @@
 // every wave waits for ITS OWN outstanding loads with a counted vmcnt (consumer: band
 // DMA + B register loads in issue order; producer: weight DMA), then the barrier
 // publishes the stage. Producers write A[(t+1)&1] while consumers read A[t&1].
-// The loop runs an even number of steps; a padding step multiplies a zero A.
+// The loop runs an even number of steps; a padding step multiplies a zero A, and the
+// branch-free loop keeps loading (the last stage again) past the last real one. TAIL
+// builds do neither: their loop ends with the last step whose loads are all real, and
+// the remaining STAGES - 1 steps follow it peeled, each with the loads that still exist
+// and its own wait count (see ws_tile).
 #include "common.h"
 #include "launch.h"
 #include "epilogue.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace kdl {
 
@@ -46,10 +51,25 @@ __device__ __attribute__((aligned(16))) uint8_t sepw_zeros[16384];
 // knows at most N loads are outstanding after it and does not add its own conservative
 // vmcnt(0) before the first use of the register-resident B fragments
 template <int N>
-__device__ __forceinline__ void ws_wait_barrier() {
+__device__ __forceinline__ void ws_wait() {
   static_assert(N < 64, "vmcnt is 6 bits");
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
+}
+template <int N>
+__device__ __forceinline__ void ws_wait_barrier() {
+  ws_wait<N>();
   __builtin_amdgcn_s_barrier();
+}
+
+template <int V> using ws_int = std::integral_constant<int, V>;
+
+// f(ws_int<I>{}) for I = LO .. HI - 1, unrolled at compile time (TAIL's peeled steps)
+template <int LO, int HI, class F>
+__device__ __forceinline__ void ws_static_for(F&& f) {
+  if constexpr (LO < HI) {
+    f(ws_int<LO>{});
+    ws_static_for<LO + 1, HI>(f);
+  }
 }
 
 // LDS bytes of one workgroup of the configuration (the tile body's layout). ZF: every stage
@@ -73,7 +93,15 @@ struct WsSmem {
 // at the 16-byte slot of the same bank as the in-map address would have, instead of one
 // shared zero slot: that slot's bank collided with a live lane of the same ds_read_b128 lane
 // group (2-way conflicts on most dx != 0 taps).
-template <int FM, int FN, int STAGES, int XB, bool STAMP, bool KROT, bool RELU, int ABL = 0, bool ZF = false>
+// TAIL: no padding step and no load of a stage >= KT. With r = KT - t steps left, step t issues
+// band(t + STAGES - 1) only while r >= STAGES and B(t + 2) only while r >= 3, so the loop covers
+// r >= STAGES and the steps r = STAGES - 1 .. 1 are peeled behind it (no branch inside the loop
+// body: see the producers' issue). The two waves' wait counts, by the same rule as the loop's
+// (everything but the previous step's loads has landed):
+//   consumer  LCB * [r >= STAGES - 1] + FN * [r >= 2]      producer  clamp(r - 3, 0, STAGES - 4)
+// KT < STAGES has no step of the loop's kind: a prologue of KT stages, then one step at a time.
+template <int FM, int FN, int STAGES, int XB, bool STAMP, bool KROT, bool RELU, int ABL = 0, bool ZF = false,
+          bool TAIL = false>
 __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, uint8_t* smem) {
   constexpr int NT = 512;
   constexpr int BM = 16 * FM, BN = 64 * FN;
@@ -118,7 +146,11 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
     krot = (mi * (a.krot > 0 ? a.krot : 7)) % KT;
   }
   auto kc = [&](int t) {
-    t = min(t, KT - 1) + krot;
+    // TAIL without KROT: the step index stays a scalar the addresses are computed from, as in the KROT
+    // builds (as an induction variable hipcc kept one running pointer per load of the peeled steps too,
+    // and spilled seven of them inside the loop)
+    if constexpr (TAIL && !KROT) asm("" : "+s"(t));
+    t = (TAIL ? t : min(t, KT - 1)) + krot;
     return t >= KT ? t - KT : t;
   };
   const int NS = min(m0 + BM, a.M) - m0 + 2 * W + 2;
@@ -179,32 +211,36 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
 #pragma unroll
       for (int j = 0; j < FN; ++j) gload(b[j], bsrc + j * bstride + (long)kc(t) * 1024);
     };
-    auto step = [&](int t, s16x8 (&b)[FN]) {
-      ws_wait_barrier<WC>();
+    // nwait: loads that may still be in flight at the barrier; band / bload: the step issues
+    // band(t + STAGES - 1) / B(t + 2) (always, except in TAIL's peeled steps)
+    auto step = [&](int t, s16x8 (&b)[FN], auto nwait, auto band, auto bload) {
+      constexpr bool BAND = decltype(band)::value, BLOAD = decltype(bload)::value;
+      ws_wait_barrier<decltype(nwait)::value>();
       stamp(st0, t);
       const uint8_t* As = smem + RING + (t & 1) * ABUF + lane * 16;
       s16x8 af[FM];
 #pragma unroll
       for (int i = 0; i < FM; ++i) af[i] = *(const s16x8*)(As + i * 1024);
-      issue_band(t + STAGES - 1, (t + STAGES - 1) % STAGES);
+      if constexpr (BAND) issue_band(t + STAGES - 1, (t + STAGES - 1) % STAGES);
       // B(t) is consumed fragment by fragment; each register set is refilled with B(t+2)
       // right behind its last MFMA
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
 #pragma unroll
         for (int i = 0; i < FM; ++i) acc[i][j] = mfma16(b[j], af[i], acc[i][j]);
-        gload(b[j], bsrc + j * bstride + (long)kc(t + 2) * 1024);
+        if constexpr (BLOAD) gload(b[j], bsrc + j * bstride + (long)kc(t + 2) * 1024);
       }
+      constexpr int NBJ = BAND ? LCB : 0;
       __builtin_amdgcn_sched_group_barrier(0x100, FM, 0);      // A fragment reads
 #pragma unroll
-      for (int j = 0; j < LCB; ++j) {
+      for (int j = 0; j < NBJ; ++j) {
         __builtin_amdgcn_sched_group_barrier(0x008, FM, 0);    // MFMAs of fragment j
-        __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);     // band DMA + B(t+2)_j
+        __builtin_amdgcn_sched_group_barrier(0x010, 1 + BLOAD, 0);   // band DMA + B(t+2)_j
       }
 #pragma unroll
-      for (int j = LCB; j < FN; ++j) {
+      for (int j = NBJ; j < FN; ++j) {
         __builtin_amdgcn_sched_group_barrier(0x008, FM, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);     // B(t+2)_j
+        if constexpr (BLOAD) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);     // B(t+2)_j
       }
       if constexpr (STAMP) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -214,17 +250,63 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
     // prologue in need order: band(0..2), B(0), B(1), band(3..STAGES-2); the producers'
     // prologue reads band(0), band(1), step 0 needs band(2) and B(0) (covered by WC)
     s16x8 b0[FN], b1[FN];
-    issue_band(0, 0);
-    issue_band(1, 1);
-    issue_band(2, 2);
-    load_b(0, b0);
-    load_b(1, b1);
+    const std::true_type yes;
+    auto steady = [&](int t, s16x8 (&b)[FN]) { step(t, b, ws_int<WC>{}, yes, yes); };
+    if constexpr (!TAIL) {
+      issue_band(0, 0);
+      issue_band(1, 1);
+      issue_band(2, 2);
+      load_b(0, b0);
+      load_b(1, b1);
 #pragma unroll
-    for (int p = 3; p < STAGES - 1; ++p) issue_band(p, p);
-    ws_wait_barrier<(STAGES - 3) * LCB + 2 * FN>();   // band(0), band(1) landed
-    for (int t = 0; t < KTE; t += 2) {
-      step(t, b0);
-      step(t + 1, b1);
+      for (int p = 3; p < STAGES - 1; ++p) issue_band(p, p);
+      ws_wait_barrier<(STAGES - 3) * LCB + 2 * FN>();   // band(0), band(1) landed
+      for (int t = 0; t < KTE; t += 2) {
+        steady(t, b0);
+        steady(t + 1, b1);
+      }
+    } else if (KT >= STAGES) {
+      // [front step, where nfull is even] [loop of step pairs b0, b1] [step nfull - 1 on b0] [peeled
+      // steps r = STAGES - 1 .. 1 on b1, b0, b1, ..., step r being t = KT - r]. Counted back from the
+      // peeled steps, step 0 takes b0 where nfull is odd (K = 736) and b1 where it is even: then B(0)
+      // is loaded into b1, behind B(1), and the front step waits for both. One path of loads up to the
+      // prologue barrier: tools/vmcnt_check.py follows every path, also mixes of two arms
+      const int nfull = KT - (STAGES - 1);       // steps whose band(t + STAGES - 1) exists
+      const int sw = (nfull & 1) ^ 1;
+      issue_band(0, 0);
+      issue_band(1, 1);
+      issue_band(2, 2);
+      load_b(sw, b0);
+      load_b(sw ^ 1, b1);
+      ws_static_for<3, STAGES - 1>([&](auto p) { issue_band(decltype(p)::value, decltype(p)::value); });
+      ws_wait_barrier<(STAGES - 3) * LCB + 2 * FN>();   // band(0), band(1) landed
+      int t = 0;
+      if (sw) {
+        step(0, b1, ws_int<(STAGES - 4) * LCB>{}, yes, yes);
+        t = 1;
+      }
+      for (; t + 1 < nfull; t += 2) {
+        steady(t, b0);
+        steady(t + 1, b1);
+      }
+      steady(nfull - 1, b0);
+      ws_static_for<0, STAGES - 1>([&](auto ic) {
+        constexpr int i = decltype(ic)::value, r = STAGES - 1 - i;
+        constexpr int N = (r >= STAGES - 1 ? LCB : 0) + (r >= 2 ? FN : 0);
+        if constexpr (i % 2 == 0) step(KT - r, b1, ws_int<N>{}, std::false_type{}, std::bool_constant<(r >= 3)>{});
+        else step(KT - r, b0, ws_int<N>{}, std::false_type{}, std::bool_constant<(r >= 3)>{});
+      });
+    } else {
+      // KT < STAGES (no layer of the models): the stages that exist, then one step at a time behind
+      // all loads. B comes through plain loads here, which hipcc counts itself: an asm load under a
+      // condition has paths on which hipcc sees its destination dead, and re-uses it
+      ws_static_for<0, STAGES - 1>([&](auto p) { if (decltype(p)::value < KT) issue_band(decltype(p)::value, decltype(p)::value); });
+      ws_wait_barrier<0>();
+      for (int t = 0; t < KT; ++t) {
+#pragma unroll
+        for (int j = 0; j < FN; ++j) b0[j] = *(const s16x8*)(bsrc + j * bstride + (long)kc(t) * 1024);
+        step(t, b0, ws_int<0>{}, std::false_type{}, std::false_type{});
+      }
     }
   } else {
     // ================= producer: dw weights LDS-DMA, depthwise on MFMA
@@ -246,7 +328,8 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
     // setup (until round 6), the prologue ran 8,760 instead of 6,892 cycles (stamped ZF build,
     // mid_sep_nr) and the bench read 0.6 % lower in 3 of 3 pairs (profiles/middle_flow_r6.txt)
 #pragma unroll
-    for (int p = 0; p < STAGES - 1; ++p) issue(p, p);
+    for (int p = 0; p < STAGES - 1; ++p)
+      if (!TAIL || p < KT) issue(p, p);
     pstamp(1);
 
     const int g = pw & 1;                        // channel group of all this wave's units
@@ -339,7 +422,7 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
         }
     };
     auto write_a = [&](int s, const f32x4 (&dacc)[UPW], int abuf) {
-      const bool live = s < KT;
+      const bool live = TAIL || s < KT;
       if constexpr (!(ABL & 8)) {
 #pragma unroll
         for (int i = 0; i < UPW; ++i) {
@@ -365,26 +448,43 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
       if (z < STAGES * 16) *(u32x4*)(smem + (z >> 4) * STAGE + ZOFF + (z & 15) * 16) = (u32x4){0u, 0u, 0u, 0u};
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    ws_wait_barrier<STAGES - 3>();             // weights of stages 0, 1 (consumers: bands)
-    pstamp(2);
     u32x4 xv[UPW][5], we;
-    dw_load(0, xv, we);
-    dw_mfma(0, xv, we, 0);
-    dw_load(1, xv, we);
-    if constexpr (STAMP) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      pstamp(3);                               // A(0) written, band(1) read
-    }
-    for (int t = 0; t < KTE; ++t) {
-      ws_wait_barrier<STAGES - 4>();           // stage t+2 landed and published
+    // nwait: weight DMAs that may still be in flight at the barrier; mf / ld / is: the step runs
+    // dw_mfma(t + 1) / dw_load(t + 2) / issue(t + STAGES - 1) (always, except in TAIL's peeled steps)
+    auto pstep = [&](int t, auto nwait, auto mf, auto ld, auto is) {
+      ws_wait_barrier<decltype(nwait)::value>();     // stage t+2 landed and published
       stamp(st0, t);
-      dw_mfma(t + 1, xv, we, (t + 1) & 1);     // inputs read during the previous step
-      dw_load(t + 2, xv, we);                  // consumed next step
-      issue(t + STAGES - 1, (t + STAGES - 1) % STAGES);
+      if constexpr (decltype(mf)::value) dw_mfma(t + 1, xv, we, (t + 1) & 1);   // inputs read during the previous step
+      if constexpr (decltype(ld)::value) dw_load(t + 2, xv, we);                // consumed next step
+      if constexpr (decltype(is)::value) issue(t + STAGES - 1, (t + STAGES - 1) % STAGES);
       if constexpr (STAMP) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         stamp(st1, t);
       }
+    };
+    const std::true_type yes;
+    const int nfull = KT - (STAGES - 1);         // steps whose issue(t + STAGES - 1) is a real stage
+    if (!TAIL || nfull >= 0) ws_wait<STAGES - 3>();   // weights of stages 0, 1 (consumers: bands)
+    else ws_wait<0>();                           // fewer stages than the prologue issues: all of them
+    __builtin_amdgcn_s_barrier();
+    pstamp(2);
+    dw_load(0, xv, we);
+    dw_mfma(0, xv, we, 0);
+    if (!TAIL || KT >= 2) dw_load(1, xv, we);
+    if constexpr (STAMP) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      pstamp(3);                                 // A(0) written, band(1) read
+    }
+    if constexpr (!TAIL) {
+      for (int t = 0; t < KTE; ++t) pstep(t, ws_int<STAGES - 4>{}, yes, yes, yes);
+    } else {
+      for (int t = 0; t < nfull; ++t) pstep(t, ws_int<STAGES - 4>{}, yes, yes, yes);
+      ws_static_for<0, STAGES - 1>([&](auto ic) {   // the peeled steps r = STAGES - 1 .. 1
+        constexpr int r = STAGES - 1 - decltype(ic)::value;
+        constexpr int N = r < 3 ? 0 : r - 3;
+        if (r <= KT)
+          pstep(KT - r, ws_int<N>{}, std::bool_constant<(r >= 2)>{}, std::bool_constant<(r >= 3)>{}, std::false_type{});
+      });
     }
     if constexpr (STAMP) {
       if (a.stamps && blockIdx.x < 64 && lane == 0) {
@@ -449,14 +549,15 @@ __device__ __forceinline__ void ws_tile(const ConvGemmArgs& a, int mi, int ni, u
   }
 }
 
-template <int FM, int FN, int STAGES, int XB, bool STAMP, bool KROT, bool RELU, int ABL = 0, bool ZF = false>
+template <int FM, int FN, int STAGES, int XB, bool STAMP, bool KROT, bool RELU, int ABL = 0, bool ZF = false,
+          bool TAIL = false>
 __global__ __launch_bounds__(512) void sepconv_ws_kernel(ConvGemmArgs a) {
   __shared__ __attribute__((aligned(256))) uint8_t smem[WsSmem<FM, FN, STAGES, XB, ZF>::BYTES];
   constexpr int BM = 16 * FM, BN = 64 * FN;
   const int nN = (a.NF * 16) / BN;
   const int nM = (a.M + BM - 1) / BM;
   const int wg = xcd_remap(blockIdx.x, nM * nN);
-  ws_tile<FM, FN, STAGES, XB, STAMP, KROT, RELU, ABL, ZF>(a, wg / nN, wg % nN, smem);
+  ws_tile<FM, FN, STAGES, XB, STAMP, KROT, RELU, ABL, ZF, TAIL>(a, wg / nN, wg % nN, smem);
 }
 
 // (FM, FN, STAGES, XB = band KiB): tile BM = 16*FM, BN = 64*FN; LDS = STAGES*(XB+1) KiB + 2FM KiB
@@ -495,7 +596,14 @@ __global__ __launch_bounds__(512) void sepconv_ws_kernel(ConvGemmArgs a) {
   X(29, 6, 6, 5, 11)         \
   X(36, 6, 6, 5, 16)         \
   X(37, 4, 6, 5, 8)          \
-  X(38, 6, 6, 5, 9)
+  X(38, 6, 6, 5, 9)          \
+  X(30, 6, 6, 5, 9)          \
+  X(31, 6, 6, 5, 11)         \
+  X(32, 6, 6, 5, 16)         \
+  X(33, 4, 6, 5, 8)          \
+  X(34, 6, 6, 5, 9)          \
+  X(35, 4, 6, 5, 8)          \
+  X(39, 6, 6, 5, 9)
 
 // id 7: s_memtime stamping variant (tools/stamps.py; never tuned); ids 23-26 = 0, 2, 3, 5
 // walking K from a per-M-tile rotated start. Round 6: ids 8-11 = stamped producer ablations
@@ -503,12 +611,19 @@ __global__ __launch_bounds__(512) void sepconv_ws_kernel(ConvGemmArgs a) {
 // ids 28, 29, 36, 37 = 23-26 with ZF; 38 = 0 with ZF. (Round 6 also measured a producer read-ahead
 // by three k-steps over a 6-stage ring, ids 30-34: slower isolated and in the pipelined bench,
 // hipcc hoisting the next step's MFMAs across the barrier; removed.)
-constexpr bool sepw_stamp(int id) { return id == 7 || (id >= 8 && id <= 13); }
-constexpr bool sepw_krot(int id) { return (id >= 8 && id <= 13) || (id >= 23 && id <= 29) || (id >= 36 && id <= 37); }
+// TAIL (peeled tail: no padding step, no load past the last stage): ids 30-34 = 28, 29, 36, 37, 38
+// with it, 35 = 5 with it, 39 = 12 with it (stamped).
+constexpr bool sepw_tail(int id) { return (id >= 30 && id <= 35) || id == 39; }
+constexpr bool sepw_stamp(int id) { return id == 7 || (id >= 8 && id <= 13) || id == 39; }
+constexpr bool sepw_krot(int id) {
+  return (id >= 8 && id <= 13) || (id >= 23 && id <= 29) || (id >= 30 && id <= 33) || (id >= 36 && id <= 37) || id == 39;
+}
 constexpr int sepw_abl(int id) {
   return id == 27 ? 1 : id == 8 ? 2 : id == 9 ? 4 : id == 10 ? 8 : id == 11 ? 14 : 0;
 }
-constexpr bool sepw_zf(int id) { return id == 12 || id == 28 || id == 29 || (id >= 36 && id <= 38); }
+constexpr bool sepw_zf(int id) {
+  return id == 12 || id == 28 || id == 29 || (id >= 30 && id <= 34) || (id >= 36 && id <= 39);
+}
 
 static int sepw_fits_xb(int BM, int W, int xb) { return BM + 2 * W + 3 <= 16 * xb; }
 
@@ -536,7 +651,7 @@ hipError_t sepconv_ws(int cfg, const ConvGemmArgs& args, hipStream_t s) {
   const ConvGemmArgs& a = args;
   int bm, bn, th;
   if (sepconv_ws_config(cfg, &bm, &bn, &th) != 0 || !sepconv_ws_fits(cfg, a.W) || a.K % 32 != 0 ||
-      a.K > 8192 || (a.NF * 16) % bn != 0 || a.OH != a.H || a.OW != a.W || a.M <= 0 || a.dwk == nullptr)
+      a.K < 32 || a.K > 8192 || (a.NF * 16) % bn != 0 || a.OH != a.H || a.OW != a.W || a.M <= 0 || a.dwk == nullptr)
     return hipErrorInvalidValue;
   const int grid = ((a.M + bm - 1) / bm) * ((a.NF * 16) / bn);
   switch (cfg) {
@@ -544,10 +659,10 @@ hipError_t sepconv_ws(int cfg, const ConvGemmArgs& args, hipStream_t s) {
   case id:                                                                                          \
     if (a.relu_in)                                                                                  \
       hipLaunchKernelGGL((sepconv_ws_kernel<fm, fn, st, xb, sepw_stamp(id), sepw_krot(id), true, sepw_abl(id), \
-                                            sepw_zf(id)>), dim3(grid), dim3(th), 0, s, a);           \
+                                            sepw_zf(id), sepw_tail(id)>), dim3(grid), dim3(th), 0, s, a);           \
     else                                                                                            \
       hipLaunchKernelGGL((sepconv_ws_kernel<fm, fn, st, xb, sepw_stamp(id), sepw_krot(id), false, sepw_abl(id), \
-                                            sepw_zf(id)>), dim3(grid), dim3(th), 0, s, a);           \
+                                            sepw_zf(id), sepw_tail(id)>), dim3(grid), dim3(th), 0, s, a);           \
     break;
     KDL_SEPW_CONFIGS(KDL_SWCASE)
 #undef KDL_SWCASE

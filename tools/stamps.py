@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """Per-wave phase timing of the warp-specialized fused separable conv from in-kernel
-s_memtime stamps (config 127 = 121 + stamping; sepconv_ws.hip STAMP).
+s_memtime stamps (sepconv_ws.hip STAMP). Stamped builds: 127 = 121; 133 = 143; 132 = 148 (the
+shipped 96x384 tile with per-stage zero blocks); 159 = 150 (132 with the peeled tail; its peeled
+steps hold three register spills that 150 does not have); 128-131 = producer ablations of 143.
 
 For the first 64 blocks, every wave records, per k-step t, the time right after the
 barrier (st0) and after its work for the step (st1). Printed: per role, the median
 over waves/blocks of the k-step period, the work part and the barrier wait part, plus
-prologue / epilogue spans. Clock: s_memtime counts shader-core cycles.
+prologue / epilogue spans, and the tail: the cycles from the barrier of step KT - 4 to the
+release of the barrier before the epilogue, beside the five steps before it.
+Clock: s_memtime counts shader-core cycles.
 
   python tools/stamps.py --shape mid_sep
+  python tools/stamps.py --shape mid_sep_nr --no-relu --cfg 132     (and --cfg 159)
 """
 from __future__ import annotations
 
@@ -57,7 +62,7 @@ def main():
     starts = s[:, 0, 0].tolist()
     print(f"block start spread (cycles): {max(starts) - min(starts)}")
     for role, waves in (("consumer", range(0, 4)), ("producer", range(4, 8))):
-        per, work, wait, pro, epi, tot = [], [], [], [], [], []
+        per, work, wait, pro, epi, tot, tail, five = [], [], [], [], [], [], [], []
         for b in range(64):
             for w in waves:
                 r = s[b, w]
@@ -66,6 +71,9 @@ def main():
                 tot.append(r[1].item())
                 pro.append(st0[0])
                 epi.append(r[1].item() - st1[kt - 1])
+                if kt >= 10:     # the last four steps, the padding step (if the build has one) and the final drain
+                    tail.append(r[1].item() - st0[kt - 4])
+                    five.append(st0[kt - 4] - st0[kt - 9])
                 for t in range(2, kt - 2):
                     per.append(st0[t + 1] - st0[t])
                     work.append(st1[t] - st0[t])
@@ -73,6 +81,9 @@ def main():
         med = statistics.median
         print(f"  {role}: step {med(per):7.0f}  work {med(work):7.0f}  wait {med(wait):7.0f}  "
               f"prologue {med(pro):7.0f}  loop-end->end {med(epi):7.0f}  total {med(tot):8.0f} cycles")
+        if tail:
+            print(f"    tail: barrier of step {kt - 4} -> final barrier released {med(tail):7.0f}  "
+                  f"the five steps before it {med(five):7.0f}  (difference {med(tail) - med(five):7.0f})")
         # prologue milestones (cycles after kernel entry): setup done, loads issued, prologue barrier,
         # (producers) A(0) written
         ms = [[s[b, w, 120 + i].item() for b in range(64) for w in waves] for i in range(4)]
