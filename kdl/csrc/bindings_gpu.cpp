@@ -201,6 +201,12 @@ HeadArgs head_args(const py::dict& d) {
   a.NC = I(d, "NC");
   return a;
 }
+TopkArgs topk_args(const py::dict& d) {
+  TopkArgs a{};
+  a.x = P<const float>(d, "x"); a.out = P<int32_t>(d, "out");
+  a.B = I(d, "B"); a.NC = I(d, "NC"); a.K = I(d, "K"); a.ldx = I(d, "ldx");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -308,6 +314,13 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(head_dense(a, S(s)), "head_dense");
   });
+  m.def("softmax_topk", [](py::dict d, uintptr_t s) {
+    const auto a = topk_args(d);
+    py::gil_scoped_release nogil;
+    chk(softmax_topk(a, S(s)), "softmax_topk");
+  });
+  m.attr("TOPK_MAX_NC") = int(kTopkMaxNC);
+  m.attr("TOPK_MAX_K") = int(kTopkMaxK);
   m.def("gap", [](py::dict d, uintptr_t s) {
     const auto a = gap_args(d);
     py::gil_scoped_release nogil;
@@ -621,6 +634,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_head", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_HEAD; op.name = name; op.hd = head_args(d); p.add(op);
+      })
+      .def("add_softmax_topk", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_SOFTMAX_TOPK; op.name = name; op.tk = topk_args(d); p.add(op);
       })
       .def("add_gap", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GAP; op.name = name; op.gp = gap_args(d); p.add(op);

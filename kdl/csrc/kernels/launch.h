@@ -328,6 +328,22 @@ struct HeadArgs {
 };
 hipError_t head_dense(const HeadArgs& a, hipStream_t s);
 
+// Classification outputs (kernels/classify.hip): per image, the K largest of its NC fp32
+// logits and their softmax scores. Classes order by descending logit, equal logits by
+// ascending index (TF top_k's rule); score_i = exp(x_i - max) / sum_j exp(x_j - max) over all
+// NC logits, summed in a fixed order (replays are bit-identical). Output row: 2K 32-bit words,
+// K int32 indices then K fp32 scores. 1 <= K <= min(NC, 32), 1 <= NC <= 1024 (kTopkMaxNC: 16
+// logits per lane of a wave), ldx >= NC; anything else is hipErrorInvalidValue. NaN logits and
+// a row that is entirely -inf give unspecified rows.
+constexpr int kTopkMaxNC = 1024;
+constexpr int kTopkMaxK = 32;
+struct TopkArgs {
+  const float* x;         // [B][ldx] fp32 logits, NC used per row
+  int32_t* out;           // [B][2K]
+  int B, NC, K, ldx;
+};
+hipError_t softmax_topk(const TopkArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

@@ -33,10 +33,20 @@ class Step:
     extra: dict = field(default_factory=dict)
 
 
+def unpack_topk(rows) -> tuple:
+    """Packed top-k rows [n, 2K] (a torch tensor or numpy array of 32-bit words) ->
+    (classes int32 [n, K], scores fp32 [n, K]) as numpy arrays."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    k = a.shape[-1] // 2
+    return a[..., :k].view(np.int32).copy(), a[..., k:].view(np.float32).copy()
+
+
 class EngineBase:
     model_name = "model"
 
-    def __init__(self, device, max_batch: int, buckets=None):
+    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0):
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -48,6 +58,12 @@ class EngineBase:
         self.outputs: list[torch.Tensor] = []  # per-slot logits (self.logits is slot 0)
         self._slot = 0
         self._remap: dict[str, str] = {}      # buffer-name overrides while emitting (stages.py)
+        # classification outputs: 0 = the output is the fp32 logits; K = one more step packs the
+        # top-K classes and softmax scores of the logits into the output rows (_enable_topk)
+        if topk < 0:
+            raise ValueError(f"topk must be >= 0, got {topk}")
+        self.topk = int(topk)
+        self.logit_slots: list[torch.Tensor] = []   # topk only: per-slot fp32 logits the head writes
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -56,10 +72,48 @@ class EngineBase:
 
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
+        if self.topk:
+            return _lib.ptr(self._logit_slot(self._slot))
         return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
 
     def slot_logits(self, slot: int) -> torch.Tensor:
+        """Output buffer of a slot: fp32 logits, or the packed top-k rows of a ``topk`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
+
+    # ---------------------------------------------------------------- classification outputs
+    def _enable_topk(self) -> None:
+        """Called by a family's constructor once ``self.logits`` [max_batch, classes] exists. With
+        ``topk = K`` (clipped to the class count) the head keeps writing that buffer, a last
+        step of kind "topk" (kernels/classify.hip) reads it, and ``self.logits`` -- the output
+        the executor copies to the host and ``forward`` returns -- becomes [max_batch, 2K]
+        32-bit words per row: K int32 class indices, then K fp32 scores (``unpack_topk``)."""
+        if not self.topk:
+            return
+        assert not self.inputs, "topk is set at construction, before input slots exist"
+        classes = self.logits.shape[1]
+        if classes > _lib.lib().TOPK_MAX_NC:
+            raise ValueError(f"topk: {classes} classes exceed the kernel's {_lib.lib().TOPK_MAX_NC}")
+        self.topk = min(self.topk, classes)
+        if self.topk > _lib.lib().TOPK_MAX_K:
+            raise ValueError(f"topk must be <= {_lib.lib().TOPK_MAX_K}, got {self.topk}")
+        self.logit_slots = [self.logits]
+        self.logits = torch.zeros((self.max_batch, 2 * self.topk), dtype=torch.float32, device=self.device)
+        self.steps.append(Step("topk", "topk", src="logits"))
+
+    def _logit_slot(self, slot: int) -> torch.Tensor:
+        while len(self.logit_slots) <= slot:      # one per input slot, whoever added the slots
+            self.logit_slots.append(torch.zeros_like(self.logit_slots[0]))
+        return self.logit_slots[slot]
+
+    def _emit_topk(self, prog, step: Step, b: int) -> None:
+        lg = self._logit_slot(self._slot)
+        out = self.outputs[self._slot] if self.outputs else self.logits
+        prog.add_softmax_topk(step.name, dict(x=_lib.ptr(lg), out=_lib.ptr(out), B=b, NC=lg.shape[1],
+                                              K=self.topk, ldx=lg.shape[1]))
+
+    def last_logits(self, slot: int = 0) -> torch.Tensor:
+        """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without ``topk``."""
+        return self._logit_slot(slot) if self.topk else self.slot_logits(slot)
 
     def add_input_slots(self, n: int) -> list[torch.Tensor]:
         """Extra static input AND logits buffers, each slot with its own captured
@@ -144,7 +198,10 @@ class EngineBase:
         with ctx:
             for st, m in zip(steps, maps):
                 self._remap = m
-                self._emit(prog, st, b)
+                if st.kind == "topk":
+                    self._emit_topk(prog, st, b)
+                else:
+                    self._emit(prog, st, b)
 
     def invalidate(self) -> None:
         self.programs.clear()
@@ -163,7 +220,8 @@ class EngineBase:
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, capture: bool = True) -> torch.Tensor:
-        """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]."""
+        """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
+        (a ``topk`` engine: the packed rows [n, 2K], see ``unpack_topk``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

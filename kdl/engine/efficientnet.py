@@ -52,14 +52,16 @@ class EfficientNetEngine(EngineBase):
     model_name = "efficientnet_b7"
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
-                 buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE):
-        super().__init__(device, max_batch, buckets)
+                 buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
+                 topk: int = 0):
+        super().__init__(device, max_batch, buckets, topk)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()
         self.bufsz: dict[str, int] = {}            # buffer -> elements per image (max over uses)
         self._build(params)
         self._alloc()
+        self._enable_topk()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

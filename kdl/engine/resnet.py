@@ -46,10 +46,10 @@ class ResNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
-                 dtype: str = "fp16"):
+                 dtype: str = "fp16", topk: int = 0):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
-        super().__init__(device, max_batch, buckets)
+        super().__init__(device, max_batch, buckets, topk)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind
@@ -60,6 +60,7 @@ class ResNetEngine(EngineBase):
         self.shapes: dict[str, tuple[int, int, int, int]] = {}   # buffer -> (H, W, C, border)
         self._build(params)
         self._alloc()
+        self._enable_topk()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

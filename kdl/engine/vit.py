@@ -44,8 +44,9 @@ class ViTEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
-                 calib: torch.Tensor | None = None, calib_margin: float = 1.25):
-        super().__init__(device, max_batch, buckets)
+                 calib: torch.Tensor | None = None, calib_margin: float = 1.25,
+                 topk: int = 0):
+        super().__init__(device, max_batch, buckets, topk)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"
@@ -60,6 +61,7 @@ class ViTEngine(EngineBase):
         self.classes = params["heads.head.bias"].numel()
         self._build(params)
         self._alloc()
+        self._enable_topk()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

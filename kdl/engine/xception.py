@@ -44,8 +44,8 @@ class XceptionEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
-                 tune_file: str | Path | None = None):
-        super().__init__(device, max_batch, buckets)
+                 tune_file: str | Path | None = None, topk: int = 0):
+        super().__init__(device, max_batch, buckets, topk)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
@@ -66,6 +66,7 @@ class XceptionEngine(EngineBase):
         self.shapes: dict[str, tuple[int, int, int]] = {}  # buffer -> (H, W, C) per image
         self._build(params)
         self._alloc()
+        self._enable_topk()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

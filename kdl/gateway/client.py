@@ -62,3 +62,13 @@ def process_batch_response(pb_result, labels, output_key="dense_7") -> list[dict
     t = pb_result.outputs[output_key]
     vals = np.asarray(t.float_val, dtype=np.float32).reshape([d.size for d in t.tensor_shape.dim])
     return [{c: float(p) for c, p in zip(labels, row)} for row in vals]
+
+
+def process_classify_response(pb_result) -> list[list[dict]]:
+    """A classify signature's PredictResponse (``classes`` DT_STRING [n, K], ``scores`` DT_FLOAT
+    [n, K]) -> per image, K ``{"label", "score"}`` entries in the server's order."""
+    cl, sc = pb_result.outputs["classes"], pb_result.outputs["scores"]
+    n, k = [d.size for d in sc.tensor_shape.dim]
+    labels = [v.decode() for v in cl.string_val]
+    return [[{"label": labels[i * k + j], "score": float(sc.float_val[i * k + j])} for j in range(k)]
+            for i in range(n)]

@@ -18,7 +18,9 @@ Backends:
 Families: ``xception`` (the reference's clothing model; SavedModel ingest,
 ``serving_default`` = f32 ``input_8`` like TF-Serving, plus ``serving_uint8`` and
 ``serving_image`` = uint8 images of any size, resized on the GPU: resize.py, and
-``serving_bytes`` = encoded image files, decoded and resized on the GPU: jpeg.py),
+``serving_bytes`` = encoded image files, decoded and resized on the GPU: jpeg.py;
+beside these three, ``classify`` / ``classify_image`` / ``classify_bytes`` = the same inputs,
+answered with the top-K labels and softmax scores computed on the device: classify.py),
 and ``resnet50`` / ``vit_b16`` / ``efficientnet_b7`` (BASELINE.json configs;
 torchvision-layout safetensors or synthetic weights, uint8 ``images`` input).
 """
@@ -68,6 +70,13 @@ class SignatureInfo:
     method_name: str = "tensorflow/serving/predict"
     input_shape: tuple = (-1, IMG, IMG, 3)
     output_shape: tuple = (-1, 10)
+    # classify signatures (serving/classify.py): every output as (key, dtype, shape), and K;
+    # empty / 0 for the signatures whose single output is the fp32 logits
+    outputs: tuple = ()
+    top_k: int = 0
+
+    def output_specs(self) -> tuple:
+        return self.outputs or ((self.output_key, P.DT_FLOAT, self.output_shape),)
 
 
 @dataclass
@@ -82,6 +91,10 @@ class ModelSource:
     classes: int = 10
     # how serving_image / serving_bytes resize to input_size (gateway.preprocess.ResizeSpec)
     preprocess: ResizeSpec = NEAREST_SPEC
+    # classification outputs (serving/classify.py): label per class, K, the tf.Example feature key
+    labels: list = field(default_factory=list)
+    classify_k: int = 0
+    classify_feature: str = "image/encoded"
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -100,10 +113,12 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
                        input_size=S, classes=n)
 
 
-def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "") -> ModelSource:
+def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
+                     classify_top_k: int | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
-    "preprocess" string of its kdl_model.json / synthetic.json, else nearest."""
+    "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
+    (the server's --classify_top_k) overrides the version's classify K (serving/classify.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -115,6 +130,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "") 
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
+    from .classify import add_signatures
+    add_signatures(src, path, classify_top_k)
     return src
 
 
@@ -372,12 +389,13 @@ class GPUExecutor(_Executor):
         cap = bool(self.engine_kwargs.get("graph", True))      # --graph off: eager launches
         in_kind = "u8" if r.sig.input_dtype == P.DT_UINT8 else "f32"
         dev = f"cuda:{self.device}"
+        tk = dict(topk=r.topk) if r.topk else {}               # the classify runner: rows of 2K words
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
                 return XceptionEngine(src.params, max_batch=b, device=dev, in_kind=in_kind,
-                                      head=src.head, buckets=buckets)
-            return registry.get(fam).engine(src.params, b, dev, buckets=buckets)
+                                      head=src.head, buckets=buckets, **tk)
+            return registry.get(fam).engine(src.params, b, dev, buckets=buckets, **tk)
         self.engine = make(bs[-1], bs)
         info = registry.get(fam)
         tp = tuning_path(info.tuning or fam, bs[-1])
@@ -429,7 +447,7 @@ class GPUExecutor(_Executor):
         want_native = os.environ.get("KDL_NATIVE_EXEC", "1") != "0" and self.lanes is None
         if not want_native:
             self.staging = [torch.zeros((bs[-1], S, S, 3), dtype=dt).pin_memory() for _ in range(self.depth)]
-            self.out = [torch.zeros((bs[-1], src.classes), dtype=torch.float32).pin_memory()
+            self.out = [torch.zeros((bs[-1], r.out_cols), dtype=torch.float32).pin_memory()
                         for _ in range(self.depth)]
         self.h2d_done = [torch.cuda.Event() for _ in range(self.depth)]
         self.done = [torch.cuda.Event() for _ in range(self.depth)]
@@ -445,15 +463,15 @@ class GPUExecutor(_Executor):
                         big.launch(bs[-1], capture=cap, slot=slot)
             torch.cuda.synchronize(self.device)
         if want_native:
-            self._build_native(S * S * 3 * (1 if in_kind == "u8" else 4), src.classes)
+            self._build_native(S * S * 3 * (1 if in_kind == "u8" else 4), r.out_cols)
 
-    def _build_native(self, item_bytes: int, classes: int) -> None:
+    def _build_native(self, item_bytes: int, out_cols: int) -> None:
         """Hand every bucket's captured graphs to the native executor: a kdl._C.HipExecBackend
         (pinned staging, H2D -> graphs -> D2H per slot, HIP-event stage times) driven by a
         kdl._rt.Executor C++ thread that pulls from the signature's batcher."""
         r, rt = self.runner, _lib.rt()
         bs = self.engine_buckets()
-        be = self._rt.HipExecBackend(self.device, self.depth, item_bytes, self.staging_rows(), classes,
+        be = self._rt.HipExecBackend(self.device, self.depth, item_bytes, self.staging_rows(), out_cols,
                                      copy_stream=self.copy_stream.cuda_stream, timing=True)
         keep = []
         for bk in bs:
@@ -618,6 +636,13 @@ class NullExecutor(_Executor):
 class SignatureRunner:
     """One C++ batcher + the executors serving one signature of one version."""
 
+    topk = 0            # K: the GPU engines end in the top-k step and rows are 2K words (ClassifyRunner)
+
+    @property
+    def out_cols(self) -> int:
+        """32-bit words per result row, from the executor to the waiting handler."""
+        return 2 * self.topk if self.topk else self.source.classes
+
     def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
         self.sig, self.source, self.cfg = sig, source, cfg
         bp = cfg.batching
@@ -632,7 +657,7 @@ class SignatureRunner:
         self.batcher = _lib.rt().DynamicBatcher(max_batch_size=self.max_batch, batch_timeout_us=timeout,
                                                 max_enqueued_batches=bp.max_enqueued_batches,
                                                 allowed_batch_sizes=self.buckets, item_bytes=item_bytes,
-                                                out_cols=source.classes,
+                                                out_cols=self.out_cols,
                                                 # threads for a batch's payload copy into pinned staging
                                                 copy_threads=int(os.environ.get("KDL_COPY_THREADS", "4")))
         self.executors: list[_Executor] = []
@@ -684,7 +709,7 @@ class SignatureRunner:
         rt = _lib.rt()
         if not self.healthy():
             raise ServingError("UNAVAILABLE", f"no healthy device left for signature {self.sig.name}")
-        ncls = self.source.classes
+        ncls = self.out_cols
         out = np.empty((n, ncls), dtype=np.float32)
         tickets = []
         for s in range(0, n, self.max_batch):
@@ -722,6 +747,23 @@ class SignatureRunner:
             ex.join(timeout=5)
 
 
+class ClassifyRunner(SignatureRunner):
+    """The ``classify`` signature: like ``serving_uint8``'s runner, but a result row is the packed
+    top-K (K int32 class indices, K fp32 softmax scores: classify.unpack_rows). GPU executors build
+    their engines with ``topk=K``, so the rows come out of the captured program; the CPU and null
+    executors return logits as ever and the rule is applied here in numpy."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.k = sig.top_k
+        self.topk = self.k if devices else 0
+        super().__init__(sig, source, cfg, devices)
+
+    def _run(self, n: int, submit) -> np.ndarray:
+        from .classify import pack_rows, topk_rule
+        rows = super()._run(n, submit)
+        return rows if self.topk else pack_rows(*topk_rule(rows, self.k))
+
+
 class Servable:
     """One loaded model version (all its signatures)."""
 
@@ -750,7 +792,16 @@ class Servable:
                 if sig_name not in self.signatures:
                     raise ServingError("INVALID_ARGUMENT", f"Serving signature name: \"{sig_name}\" not found "
                                        "in signature def")
-                if sig_name == IMAGE_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
+                from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
+                if sig_name == CLASSIFY_SIGNATURE:
+                    r = ClassifyRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == CLASSIFY_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(CLASSIFY_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == CLASSIFY_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(CLASSIFY_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == IMAGE_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
                     r = ImageRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
                                     self.source.preprocess)
                 elif sig_name == BYTES_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
@@ -772,9 +823,11 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # serving_image / serving_bytes feed the serving_uint8 runner's batcher and have none of
-        # their own: that runner is in the list already and speaks for them
-        used = [r for r in runners if hasattr(r, "batcher") and r.batcher.stats()["submitted"] > 0]
+        # a wrapper (serving_image / serving_bytes / classify_image / classify_bytes) has no batcher
+        # of its own: it feeds its inner runner's, so that is where its work shows
+        def batcher(r):
+            return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)
+        used = [r for r in runners if batcher(r) is not None and batcher(r).stats()["submitted"] > 0]
         return not used or any(r.healthy() for r in used)
 
     def close(self):

@@ -89,6 +89,9 @@ class ServerConfig:
     # "gpu_rst": gpu, and files with restart intervals are decoded on the device too, one workgroup per
     # group of intervals (a file whose RSTm markers are out of order or number still goes to the host)
     jpeg_entropy: str = "host"
+    # K of the classify signatures (serving/classify.py); None = the model version's own
+    # "classify": {"top_k": K}, else 5. 1..32, clipped to the class count
+    classify_top_k: int | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -185,6 +188,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "as gpu, and files with restart intervals (DRI) are decoded on the GPU too, their "
                          "intervals in parallel workgroups, instead of going to the host; env "
                          "KDL_JPEG_ENTROPY (default host)")
+    ap.add_argument("--classify_top_k", type=int, default=None,
+                    help="classes and scores per image of the classify / classify_image / classify_bytes signatures "
+                         "and the Classify RPC (1..32, clipped to the class count); overrides the model version's "
+                         "\"classify\": {\"top_k\": K} (env KDL_CLASSIFY_TOP_K, default: the version's, else 5)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -243,6 +250,8 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         warm_signatures=[s for s in a.warm_signatures.split(",") if s],
                         preprocess=a.preprocess if a.preprocess is not None else env.get("KDL_PREPROCESS", ""),
                         jpeg_entropy=a.jpeg_entropy or env.get("KDL_JPEG_ENTROPY", "") or "host",
+                        classify_top_k=(a.classify_top_k if a.classify_top_k is not None
+                                        else int(env["KDL_CLASSIFY_TOP_K"]) if env.get("KDL_CLASSIFY_TOP_K") else None),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

@@ -20,6 +20,7 @@ import numpy as np
 from ..ops import _lib
 from . import protos as P
 from .backend import NATIVE_SIGNATURE, ServingError
+from .classify import CLASSIFY_BYTES_SIGNATURE, examples_to_images, labels_of, unpack_rows
 from .metrics import METRICS
 from .model_repo import ModelManager
 
@@ -167,8 +168,9 @@ class Servicer:
                                    f"{{{sig.input_key}}}.")
             if len(inputs) != 1:
                 raise ServingError("INVALID_ARGUMENT", f"expected exactly one input ({sig.input_key})")
+            out_keys = [k for k, _, _ in sig.output_specs()]
             for f in req["output_filter"]:
-                if f != sig.output_key:
+                if f not in out_keys:
                     raise ServingError("INVALID_ARGUMENT", f"output tensor alias not found in signature: {f}")
             buf, n = _payload(raw, inputs[sig.input_key], sig)
             if self.f32_exact_u8:
@@ -176,7 +178,10 @@ class Servicer:
             t1 = time.perf_counter()
             logits = runner.predict(buf, n, _deadline_us(context))
             t2 = time.perf_counter()
-            out = rt.build_predict_response([(sig.output_key, logits)], s.name, s.version, sig_name)
+            if sig.top_k:               # classify signatures: label strings + scores from the packed rows
+                out = classify_response(s, sig, logits, req["output_filter"])
+            else:
+                out = rt.build_predict_response([(sig.output_key, logits)], s.name, s.version, sig_name)
             # per-request stage trace (SURVEY.md §5 tracing): parse+validate, batcher wait+run, respond
             METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
             METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")
@@ -234,9 +239,43 @@ class Servicer:
             resp.status.error_message = str(e)
             return resp.SerializeToString()
 
+    # ---------------------------------------------------------------- Classify
+    def classify(self, raw: bytes, context) -> bytes:
+        """TF-Serving's Classify over tf.Examples: one encoded image per example (feature
+        ``image/encoded``), served by the ``classify_bytes`` signature."""
+        t0 = time.perf_counter()
+        try:
+            try:
+                req = P.ClassificationRequest.FromString(raw)
+            except Exception as e:  # noqa: BLE001 - protobuf's DecodeError
+                raise ServingError("INVALID_ARGUMENT", f"malformed ClassificationRequest: {e}") from e
+            spec = req.model_spec
+            if not spec.name and not req.HasField("input"):
+                raise ServingError("INVALID_ARGUMENT", "malformed ClassificationRequest: no model_spec and no input")
+            ver = spec.version.value if spec.HasField("version") else None
+            s = self.m.get(spec.name, ver, spec.version_label or None)
+            labels, scores = classify_examples(s, spec.signature_name, req.input.WhichOneof("kind"),
+                                               req.input.example_list.examples, _deadline_us(context))
+            resp = P.ClassificationResponse()
+            resp.model_spec.name = s.name
+            resp.model_spec.version.value = s.version
+            resp.model_spec.signature_name = spec.signature_name or CLASSIFY_BYTES_SIGNATURE
+            for lab, sc in zip(labels, scores):
+                c = resp.result.classifications.add()
+                for name, v in zip(lab, sc):
+                    c.classes.add(label=name, score=float(v))
+            out = resp.SerializeToString()
+        except ServingError as e:
+            METRICS.inc("kdl_requests_total", code=e.code, method="Classify")
+            _abort(context, e)
+            return b""
+        METRICS.inc("kdl_requests_total", code="OK", method="Classify")
+        METRICS.observe("kdl_request_latency_ms", (time.perf_counter() - t0) * 1e3, method="Classify")
+        return out
+
     def unimplemented(self, raw: bytes, context) -> bytes:
         context.abort(grpc.StatusCode.UNIMPLEMENTED,
-                      "only Predict is supported for tensorflow/serving/predict signatures")
+                      "only Predict and Classify are supported for tensorflow/serving/predict signatures")
         return b""
 
     # ---------------------------------------------------------------- grpc.health.v1
@@ -246,6 +285,52 @@ class Servicer:
         if context is not None:
             context.send_initial_metadata((("kdl-pid", str(os.getpid())),))
         return b"\x08\x01" if self.m.ready() else b"\x08\x02"
+
+
+def classify_outputs(s, sig, rows) -> tuple[list[list[str]], np.ndarray]:
+    """Packed top-K rows of a classify signature -> (labels [n][K], scores fp32 [n, K])."""
+    classes, scores = unpack_rows(rows)
+    METRICS.inc("kdl_classify_total", signature=sig.name)
+    return labels_of(s.source, classes), scores
+
+
+def classify_response(s, sig, rows, output_filter) -> bytes:
+    """PredictResponse of a classify signature: ``classes`` DT_STRING [n, K] and ``scores``
+    DT_FLOAT [n, K] (float_val), or the subset ``output_filter`` names."""
+    labels, scores = classify_outputs(s, sig, rows)
+    n, k = scores.shape
+    resp = P.PredictResponse()
+    resp.model_spec.name = s.name
+    resp.model_spec.version.value = s.version
+    resp.model_spec.signature_name = sig.name
+    want = list(output_filter) or ["classes", "scores"]
+    if "classes" in want:
+        t = resp.outputs["classes"]
+        t.dtype = P.DT_STRING
+        t.string_val.extend(name.encode() for row in labels for name in row)
+    if "scores" in want:
+        t = resp.outputs["scores"]
+        t.dtype = P.DT_FLOAT
+        t.float_val.extend(scores.reshape(-1).tolist())
+    for key in resp.outputs:
+        for d in (n, k):
+            resp.outputs[key].tensor_shape.dim.add(size=d)
+    return resp.SerializeToString()
+
+
+def classify_examples(s, signature_name: str, kind, examples, deadline_us: int):
+    """The Classify RPC / REST :classify core, after the model lookup: (labels, scores) of the
+    examples' images through the ``classify_bytes`` runner."""
+    if signature_name not in ("", CLASSIFY_BYTES_SIGNATURE):
+        raise ServingError("INVALID_ARGUMENT", f"Classify is served by signature \"{CLASSIFY_BYTES_SIGNATURE}\", "
+                           f"not \"{signature_name}\"")
+    if kind == "example_list_with_context":
+        raise ServingError("INVALID_ARGUMENT", "example_list_with_context is not supported: send an example_list")
+    if len(examples) == 0:
+        raise ServingError("INVALID_ARGUMENT", "the example list is empty: expected at least example 0")
+    images = examples_to_images(examples, s.source.classify_feature)
+    runner = s.runner(CLASSIFY_BYTES_SIGNATURE)
+    return classify_outputs(s, runner.sig, runner.predict(images, len(images), deadline_us))
 
 
 def signature_def_map(s) -> "P.SignatureDefMap":
@@ -258,11 +343,12 @@ def signature_def_map(s) -> "P.SignatureDefMap":
         ti.dtype = sig.input_dtype
         for d in sig.input_shape:
             ti.tensor_shape.dim.add(size=d)
-        to = sd.outputs[sig.output_key]
-        to.name = "StatefulPartitionedCall:0"
-        to.dtype = P.DT_FLOAT
-        for d in sig.output_shape:
-            to.tensor_shape.dim.add(size=d)
+        for i, (key, dtype, shape) in enumerate(sig.output_specs()):
+            to = sd.outputs[key]
+            to.name = f"StatefulPartitionedCall:{i}"
+            to.dtype = dtype
+            for d in shape:
+                to.tensor_shape.dim.add(size=d)
     return m
 
 
@@ -273,7 +359,7 @@ def build_grpc_server(manager: ModelManager, host: str, port: int, max_workers: 
     pred = grpc.method_handlers_generic_handler("tensorflow.serving.PredictionService", {
         "Predict": grpc.unary_unary_rpc_method_handler(sv.predict, **raw),
         "GetModelMetadata": grpc.unary_unary_rpc_method_handler(sv.get_model_metadata, **raw),
-        "Classify": grpc.unary_unary_rpc_method_handler(sv.unimplemented, **raw),
+        "Classify": grpc.unary_unary_rpc_method_handler(sv.classify, **raw),
         "Regress": grpc.unary_unary_rpc_method_handler(sv.unimplemented, **raw),
         "MultiInference": grpc.unary_unary_rpc_method_handler(sv.unimplemented, **raw),
     })

@@ -37,7 +37,8 @@ def latest_version_source(cfg: ServerConfig):
     versions = list_versions(base) or ([1] if cfg.synthetic else [])
     if not versions:
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
-    return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess)
+    return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess,
+                            classify_top_k=cfg.classify_top_k)
 
 
 class ModelManager:
@@ -73,7 +74,8 @@ class ModelManager:
             self.states[v] = (LOADING, "")
         t0 = time.perf_counter()
         try:
-            src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess)
+            src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess,
+                                   classify_top_k=self.cfg.classify_top_k)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

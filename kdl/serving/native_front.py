@@ -73,7 +73,7 @@ class NativeFront:
         self.methods = {
             PREDICT: servicer.predict,
             sp + "GetModelMetadata": servicer.get_model_metadata,
-            sp + "Classify": servicer.unimplemented,
+            sp + "Classify": servicer.classify,
             sp + "Regress": servicer.unimplemented,
             sp + "MultiInference": servicer.unimplemented,
             ms + "GetModelStatus": servicer.get_model_status,
@@ -126,8 +126,8 @@ class NativeFront:
             gen = self._gen
         runner = s.runner(sig_name)
         sig = runner.sig
-        if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or not runner.healthy():
-            return                                             # serving_image / serving_bytes: slow path
+        if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or sig.top_k or not runner.healthy():
+            return                              # serving_image / serving_bytes / classify*: slow path
         u8 = None
         if self.f32_exact_u8 and sig.input_dtype == P.DT_FLOAT and NATIVE_SIGNATURE in s.signatures:
             u8 = s.runner(NATIVE_SIGNATURE).batcher

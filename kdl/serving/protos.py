@@ -13,7 +13,9 @@ SignatureDef, MetaGraphDef, SavedModel, SavedObjectGraph, TrackableObjectGraph,
 BundleHeaderProto, BundleEntryProto, VersionDef}; tensorflow.serving.{ModelSpec,
 PredictRequest/Response, GetModelMetadataRequest/Response, SignatureDefMap,
 GetModelStatusRequest/Response, ModelVersionStatus, StatusProto,
-ReloadConfigRequest/Response}; services PredictionService and ModelService.
+ReloadConfigRequest/Response}; tf.Example (BytesList, FloatList, Int64List, Feature,
+Features, Example) and tensorflow.serving.{Input, ExampleList, ExampleListWithContext,
+Class, Classifications, ClassificationResult, ClassificationRequest/Response}; services PredictionService and ModelService.
 """
 from __future__ import annotations
 
@@ -162,6 +164,24 @@ def _build_pool() -> descriptor_pool.DescriptorPool:
     _field(be, "offset", 4, F.TYPE_INT64)
     _field(be, "size", 5, F.TYPE_INT64)
     _field(be, "crc32c", 6, F.TYPE_FIXED32)
+
+    # tf.Example (tensorflow/core/example/feature.proto, example.proto) [ext]: field numbers from
+    # the published protos, not checked against a copy of the package
+    bl = tf.message_type.add(name="BytesList")
+    _field(bl, "value", 1, F.TYPE_BYTES, REP)
+    fl = tf.message_type.add(name="FloatList")
+    _field(fl, "value", 1, F.TYPE_FLOAT, REP, packed=True)
+    il = tf.message_type.add(name="Int64List")
+    _field(il, "value", 1, F.TYPE_INT64, REP, packed=True)
+    ft = tf.message_type.add(name="Feature")
+    ft.oneof_decl.add(name="kind")
+    _field(ft, "bytes_list", 1, F.TYPE_MESSAGE, type_name=".tensorflow.BytesList", oneof=0)
+    _field(ft, "float_list", 2, F.TYPE_MESSAGE, type_name=".tensorflow.FloatList", oneof=0)
+    _field(ft, "int64_list", 3, F.TYPE_MESSAGE, type_name=".tensorflow.Int64List", oneof=0)
+    fts = tf.message_type.add(name="Features")
+    _map(tf, fts, "feature", 1, F.TYPE_STRING, F.TYPE_MESSAGE, ".tensorflow.Feature")
+    ex = tf.message_type.add(name="Example")
+    _field(ex, "features", 1, F.TYPE_MESSAGE, type_name=".tensorflow.Features")
     pool.Add(tf)
 
     # ---------------------------------------------------------------- tensorflow.serving
@@ -214,8 +234,34 @@ def _build_pool() -> descriptor_pool.DescriptorPool:
     rcp = sv.message_type.add(name="ReloadConfigResponse")
     _field(rcp, "status", 1, F.TYPE_MESSAGE, type_name=".tensorflow.serving.StatusProto")
 
+    # Classify (tensorflow_serving/apis/input.proto, classification.proto) [ext]
+    exl = sv.message_type.add(name="ExampleList")
+    _field(exl, "examples", 1, F.TYPE_MESSAGE, REP, ".tensorflow.Example")
+    exc = sv.message_type.add(name="ExampleListWithContext")
+    _field(exc, "examples", 1, F.TYPE_MESSAGE, REP, ".tensorflow.Example")
+    _field(exc, "context", 2, F.TYPE_MESSAGE, type_name=".tensorflow.Example")
+    inp = sv.message_type.add(name="Input")
+    inp.oneof_decl.add(name="kind")
+    _field(inp, "example_list", 1, F.TYPE_MESSAGE, type_name=".tensorflow.serving.ExampleList", oneof=0)
+    _field(inp, "example_list_with_context", 2, F.TYPE_MESSAGE,
+           type_name=".tensorflow.serving.ExampleListWithContext", oneof=0)
+    kl = sv.message_type.add(name="Class")
+    _field(kl, "label", 1, F.TYPE_STRING)
+    _field(kl, "score", 2, F.TYPE_FLOAT)
+    kls = sv.message_type.add(name="Classifications")
+    _field(kls, "classes", 1, F.TYPE_MESSAGE, REP, ".tensorflow.serving.Class")
+    clr = sv.message_type.add(name="ClassificationResult")
+    _field(clr, "classifications", 1, F.TYPE_MESSAGE, REP, ".tensorflow.serving.Classifications")
+    clq = sv.message_type.add(name="ClassificationRequest")
+    _field(clq, "model_spec", 1, F.TYPE_MESSAGE, type_name=".tensorflow.serving.ModelSpec")
+    _field(clq, "input", 2, F.TYPE_MESSAGE, type_name=".tensorflow.serving.Input")
+    clp = sv.message_type.add(name="ClassificationResponse")
+    _field(clp, "result", 1, F.TYPE_MESSAGE, type_name=".tensorflow.serving.ClassificationResult")
+    _field(clp, "model_spec", 2, F.TYPE_MESSAGE, type_name=".tensorflow.serving.ModelSpec")
+
     svc = sv.service.add(name="PredictionService")
     for mname, i, o in (("Predict", "PredictRequest", "PredictResponse"),
+                        ("Classify", "ClassificationRequest", "ClassificationResponse"),
                         ("GetModelMetadata", "GetModelMetadataRequest", "GetModelMetadataResponse")):
         svc.method.add(name=mname, input_type=f".tensorflow.serving.{i}", output_type=f".tensorflow.serving.{o}")
     msvc = sv.service.add(name="ModelService")
@@ -255,8 +301,14 @@ GetModelStatusResponse = _cls("tensorflow.serving.GetModelStatusResponse")
 ModelVersionStatus = _cls("tensorflow.serving.ModelVersionStatus")
 ReloadConfigRequest = _cls("tensorflow.serving.ReloadConfigRequest")
 ReloadConfigResponse = _cls("tensorflow.serving.ReloadConfigResponse")
+Feature = _cls("tensorflow.Feature")
+Example = _cls("tensorflow.Example")
+Input = _cls("tensorflow.serving.Input")
+ClassificationRequest = _cls("tensorflow.serving.ClassificationRequest")
+ClassificationResponse = _cls("tensorflow.serving.ClassificationResponse")
 
 PREDICT_METHOD = "/tensorflow.serving.PredictionService/Predict"
+CLASSIFY_METHOD = "/tensorflow.serving.PredictionService/Classify"
 METADATA_METHOD = "/tensorflow.serving.PredictionService/GetModelMetadata"
 STATUS_METHOD = "/tensorflow.serving.ModelService/GetModelStatus"
 

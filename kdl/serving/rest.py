@@ -7,6 +7,10 @@ Routes (TF-Serving REST semantics):
        {"signature_name"?, "instances": [...]}  -> {"predictions": [...]}
        {"signature_name"?, "inputs": ...}       -> {"outputs": ...}
        (serving_bytes: every value is {"b64": "<base64 of the image file>"})
+       (classify signatures: {"classes": [...], "scores": [...]} per instance, or by column)
+  POST /v1/models/<name>[/versions/<v>|/labels/<l>]:classify
+       {"signature_name"?, "examples": [{"image/encoded": {"b64": ...}}, ...]}
+                                                -> {"results": [[["label", score], ...], ...]}
   GET  /monitoring/prometheus/metrics, /healthz (liveness), /readyz (readiness)
 """
 from __future__ import annotations
@@ -24,12 +28,13 @@ from google.protobuf import json_format
 from ..ops import _lib
 from . import protos as P
 from .backend import ServingError
-from .grpc_server import route_exact_u8, signature_def_map
+from .classify import CLASSIFY_BYTES_SIGNATURE
+from .grpc_server import classify_examples, classify_outputs, route_exact_u8, signature_def_map
 from .metrics import METRICS
 from .model_repo import STATE_NAMES, ModelManager
 
 _ROUTE = re.compile(r"^/v1/models/(?P<name>[^/:]+)(?:/versions/(?P<ver>\d+)|/labels/(?P<label>[^/:]+))?"
-                    r"(?P<tail>:predict|/metadata)?/?$")
+                    r"(?P<tail>:predict|:classify|/metadata)?/?$")
 _HTTP = {"INVALID_ARGUMENT": 400, "NOT_FOUND": 404, "DEADLINE_EXCEEDED": 504, "UNAVAILABLE": 503,
          "RESOURCE_EXHAUSTED": 429, "UNIMPLEMENTED": 501, "INTERNAL": 500}
 
@@ -61,7 +66,7 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 ok = manager.ready()
                 return self._send(200 if ok else 503, {"ready": ok})
             m = _ROUTE.match(self.path)
-            if not m or m.group("tail") == ":predict":
+            if not m or m.group("tail") in (":predict", ":classify"):
                 return self._send(404, {"error": "not found"})
             try:
                 ver = int(m.group("ver")) if m.group("ver") else None
@@ -82,6 +87,8 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
 
         def do_POST(self):  # noqa: N802
             m = _ROUTE.match(self.path)
+            if m and m.group("tail") == ":classify":
+                return self._classify(m)
             if not m or m.group("tail") != ":predict":
                 return self._send(404, {"error": "not found"})
             t0 = time.perf_counter()
@@ -94,7 +101,7 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 sig = runner.sig
                 dt = np.uint8 if sig.input_dtype == P.DT_UINT8 else np.float32
                 if sig.input_dtype == P.DT_STRING:      # serving_bytes: {"b64": ...} per encoded image
-                    return self._predict_bytes(body, runner, t0)
+                    return self._predict_bytes(body, s, runner, t0)
                 if "instances" in body:
                     inst = body["instances"]
                     if inst and isinstance(inst[0], dict):
@@ -120,9 +127,9 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 if f32_exact_u8:     # same routing as gRPC (--scatter rccl serves serving_uint8 over the node)
                     runner, x = route_exact_u8(s, runner, x, n_img)
                 t1 = time.perf_counter()
-                out = runner.predict(x, n_img, deadline).tolist()
+                out = self._body(s, sig, runner.predict(x, n_img, deadline), rows)
                 t2 = time.perf_counter()
-                r = self._send(200, {"predictions": out} if rows else {"outputs": out})
+                r = self._send(200, out)
                 # same per-request stage trace as the gRPC path (SURVEY.md §5 tracing)
                 METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
                 METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")
@@ -136,7 +143,72 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
             except (ValueError, KeyError, TypeError) as e:
                 return self._err(ServingError("INVALID_ARGUMENT", str(e)))
 
-        def _predict_bytes(self, body, runner, t0):
+        @staticmethod
+        def _body(s, sig, out, rows: bool) -> dict:
+            """The :predict answer: logits, or a classify signature's two named outputs."""
+            if not sig.top_k:
+                return {"predictions": out.tolist()} if rows else {"outputs": out.tolist()}
+            labels, scores = classify_outputs(s, sig, out)
+            if rows:
+                return {"predictions": [{"classes": c, "scores": v} for c, v in zip(labels, scores.tolist())]}
+            return {"outputs": {"classes": labels, "scores": scores.tolist()}}
+
+        def _classify(self, m):
+            t0 = time.perf_counter()
+            try:
+                n = int(self.headers.get("Content-Length", "0"))
+                try:
+                    body = json.loads(self.rfile.read(n) or b"{}")
+                except ValueError as e:
+                    raise ServingError("INVALID_ARGUMENT", f"malformed JSON body: {e}") from e
+                if not isinstance(body, dict):
+                    raise ServingError("INVALID_ARGUMENT", "the body must be a JSON object with \"examples\"")
+                ver = int(m.group("ver")) if m.group("ver") else None
+                s = manager.get(m.group("name"), ver, m.group("label"))
+                if "context" in body:
+                    raise ServingError("INVALID_ARGUMENT", "\"context\" is not supported: send \"examples\" only")
+                items = body.get("examples")
+                if not isinstance(items, list):
+                    raise ServingError("INVALID_ARGUMENT", "request must contain a list \"examples\"")
+                examples = []
+                for i, it in enumerate(items):
+                    ex = P.Example()
+                    if not isinstance(it, dict):
+                        raise ServingError("INVALID_ARGUMENT", f"example {i}: expected an object of features")
+                    for key, v in it.items():
+                        f = ex.features.feature[key]
+                        for one in v if isinstance(v, list) else [v]:
+                            if isinstance(one, dict) and isinstance(one.get("b64"), str):
+                                try:
+                                    f.bytes_list.value.append(base64.b64decode(one["b64"], validate=True))
+                                except ValueError as e:
+                                    raise ServingError("INVALID_ARGUMENT",
+                                                       f"example {i}: feature '{key}': bad base64: {e}") from e
+                            elif isinstance(one, str):
+                                f.bytes_list.value.append(one.encode())
+                            elif isinstance(one, bool) or not isinstance(one, (int, float)):
+                                raise ServingError("INVALID_ARGUMENT", f"example {i}: feature '{key}': unsupported value")
+                            elif isinstance(one, int):
+                                f.int64_list.value.append(one)
+                            else:
+                                f.float_list.value.append(one)
+                    examples.append(ex)
+                dl = self.headers.get("X-Deadline-Ms")
+                deadline = int(_lib.rt().now_us() + float(dl) * 1e3) if dl else 0
+                labels, scores = classify_examples(s, body.get("signature_name") or "", "example_list", examples,
+                                                   deadline)
+                r = self._send(200, {"results": [[[name, v] for name, v in zip(lab, sc)]
+                                                 for lab, sc in zip(labels, scores.tolist())]})
+                METRICS.inc("kdl_requests_total", code="OK", method="RestClassify")
+                METRICS.observe("kdl_request_latency_ms", (time.perf_counter() - t0) * 1e3, method="RestClassify")
+                return r
+            except ServingError as e:
+                METRICS.inc("kdl_requests_total", code=e.code, method="RestClassify")
+                return self._err(e)
+            except (ValueError, KeyError, TypeError) as e:
+                return self._err(ServingError("INVALID_ARGUMENT", str(e)))
+
+        def _predict_bytes(self, body, s, runner, t0):
             sig = runner.sig
             rows = "instances" in body
             if not rows and "inputs" not in body:
@@ -161,9 +233,9 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
             dl = self.headers.get("X-Deadline-Ms")
             deadline = int(_lib.rt().now_us() + float(dl) * 1e3) if dl else 0
             t1 = time.perf_counter()
-            out = runner.predict(images, len(images), deadline).tolist()
+            out = self._body(s, sig, runner.predict(images, len(images), deadline), rows)
             t2 = time.perf_counter()
-            r = self._send(200, {"predictions": out} if rows else {"outputs": out})
+            r = self._send(200, out)
             METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
             METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")
             METRICS.observe("kdl_stage_ms", (time.perf_counter() - t2) * 1e3, stage="respond")

@@ -264,7 +264,11 @@ def _watch_devices(srv: "ModelServer", done: threading.Event, rc: list, grace_s:
     alone does not recycle the child: its other signatures keep serving."""
     served, bad_since = False, None
     while not done.wait(0.2):
-        ok = srv.manager.device_alive()
+        try:
+            ok = srv.manager.device_alive()
+        except Exception:  # noqa: BLE001 - a failed poll is logged; the watch thread must not die
+            log.exception("device watch: poll failed")
+            continue
         served = served or ok
         if not served or ok:
             bad_since = None

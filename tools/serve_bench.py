@@ -77,12 +77,14 @@ def _build_request(a) -> bytes:
             restart = {f"restart_marker_{kind}": int(num)}
         im.save(buf, "JPEG", quality=90, subsampling=2, **restart)
         data = buf.getvalue()
-        if a.signature == "serving_bytes":
+        if a.signature in ("serving_bytes", "classify_bytes"):
             return make_request([data] * a.images, signature=a.signature, input_key="image_bytes").SerializeToString()
         px = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), np.uint8)
         return make_request(np.stack([px] * a.images), signature=a.signature, input_key="images").SerializeToString()
     rng = np.random.default_rng(0)
-    H, W = (299, 299) if a.signature != "serving_image" else map(int, a.image_size.split("x"))
+    from kdl.engine import registry
+    S = registry.get(a.model).input_size
+    H, W = (S, S) if a.signature not in ("serving_image", "classify_image") else map(int, a.image_size.split("x"))
     u8 = rng.integers(0, 256, (a.images, H, W, 3), dtype=np.uint8)
     if a.signature != "serving_default":
         return make_request(u8, signature=a.signature, input_key="images").SerializeToString()
@@ -96,7 +98,7 @@ def _launch_procs(a):
     import tempfile
     base = os.path.join(tempfile.mkdtemp(), "clothing-model")
     os.makedirs(os.path.join(base, "1"))
-    open(os.path.join(base, "1", "synthetic.json"), "w").write('{"seed": 0}')
+    open(os.path.join(base, "1", "synthetic.json"), "w").write(json.dumps({"seed": 0, "model": a.model}))
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -137,7 +139,12 @@ def main(argv=None) -> int:
     ap.add_argument("--clients", type=int, default=32)
     ap.add_argument("--images", type=int, default=1)
     ap.add_argument("--seconds", type=float, default=15)
-    ap.add_argument("--signature", default="serving_uint8", choices=["serving_uint8", "serving_default", "serving_image", "serving_bytes"])
+    ap.add_argument("--signature", default="serving_uint8",
+                    choices=["serving_uint8", "serving_default", "serving_image", "serving_bytes",
+                             "classify", "classify_image", "classify_bytes"],
+                    help="classify*: the top-k classes and scores instead of the logits (serving/classify.py)")
+    ap.add_argument("--model", default="xception",
+                    help="family of the synthetic model served (kdl.engine.registry: xception, resnet50, ...)")
     ap.add_argument("--payload", choices=["random", "jpeg"], default="random",
                     help="jpeg: a quality-90 4:2:0 JPEG of tests/data/pants.png at --image-size -- the file for "
                          "serving_bytes, its decoded pixels for serving_image (random: seeded uniform pixels)")
@@ -180,7 +187,8 @@ def main(argv=None) -> int:
                     help="run the clients in this many spawned processes (0: threads of the server "
                          "process, which then share its GIL with the server's handlers)")
     a = ap.parse_args(argv)
-    if (a.signature == "serving_bytes") != (a.payload == "jpeg") and a.signature != "serving_image":
+    if ((a.signature in ("serving_bytes", "classify_bytes")) != (a.payload == "jpeg")
+            and a.signature not in ("serving_image", "classify_image")):
         ap.error("--signature serving_bytes goes with --payload jpeg (which serving_image also takes)")
     procs = []
     if a.client_procs and a.client == "python":
@@ -207,7 +215,7 @@ def main(argv=None) -> int:
         from kdl.serving.server import ModelServer
         base = os.path.join(tempfile.mkdtemp(), "clothing-model")
         os.makedirs(os.path.join(base, "1"))
-        open(os.path.join(base, "1", "synthetic.json"), "w").write('{"seed": 0}')
+        open(os.path.join(base, "1", "synthetic.json"), "w").write(json.dumps({"seed": 0, "model": a.model}))
         sizes = [b for b in (1, 2, 4, 8, 16, 32, 64) if b <= a.max_batch]
         cfg = ServerConfig(port=0, rest_api_port=0, model_base_path=base, device=a.device, gpus=a.gpus,
                            executors_per_gpu=a.executors_per_gpu,
@@ -220,6 +228,8 @@ def main(argv=None) -> int:
             srv.manager.get("clothing-model").runner(a.signature)
         target = f"127.0.0.1:{srv.grpc_port}"
     req = _build_request(a)
+    with grpc.insecure_channel(target, options=[("grpc.max_send_message_length", -1)]) as ch0:
+        response_bytes = len(ch0.unary_unary("/tensorflow.serving.PredictionService/Predict")(req, timeout=120))
     lat, lock = [], threading.Lock()
     native_load = None
     if a.client == "native":
@@ -263,7 +273,8 @@ def main(argv=None) -> int:
            "client": a.client, "frontend": a.frontend,
            "client_procs": a.client_procs, **({"conns": a.conns} if native_load is not None else {}),
            "images_per_request": a.images,
-           "signature": a.signature, "requests": len(lat), "images_per_s": round(len(lat) * a.images / span, 1),
+           "signature": a.signature, "model": a.model, "request_bytes": len(req), "response_bytes": response_bytes,
+           "requests": len(lat), "images_per_s": round(len(lat) * a.images / span, 1),
            "p50_ms": round(statistics.median(lat) * 1e3, 2),
            "p99_ms": round(sorted(lat)[int(0.99 * (len(lat) - 1))] * 1e3, 2)}
     if srv is not None:
