@@ -207,6 +207,13 @@ TopkArgs topk_args(const py::dict& d) {
   a.B = I(d, "B"); a.NC = I(d, "NC"); a.K = I(d, "K"); a.ldx = I(d, "ldx");
   return a;
 }
+EmbedRowsArgs embed_rows_args(const py::dict& d) {
+  EmbedRowsArgs a{};
+  a.x = P<const uint16_t>(d, "x"); a.out = P<float>(d, "out");
+  a.B = I(d, "B"); a.HW = I(d, "HW"); a.F = I(d, "F"); a.ldx = I(d, "ldx"); a.ldo = I(d, "ldo");
+  a.dt = I(d, "dt"); a.norm = I(d, "norm");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -319,6 +326,12 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(softmax_topk(a, S(s)), "softmax_topk");
   });
+  m.def("embed_rows", [](py::dict d, uintptr_t s) {
+    const auto a = embed_rows_args(d);
+    py::gil_scoped_release nogil;
+    chk(embed_rows(a, S(s)), "embed_rows");
+  });
+  m.attr("EMBED_MAX_F") = int(kEmbedMaxF);
   m.attr("TOPK_MAX_NC") = int(kTopkMaxNC);
   m.attr("TOPK_MAX_K") = int(kTopkMaxK);
   m.def("gap", [](py::dict d, uintptr_t s) {
@@ -637,6 +650,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_softmax_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_SOFTMAX_TOPK; op.name = name; op.tk = topk_args(d); p.add(op);
+      })
+      .def("add_embed_rows", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_EMBED_ROWS; op.name = name; op.er = embed_rows_args(d); p.add(op);
       })
       .def("add_gap", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GAP; op.name = name; op.gp = gap_args(d); p.add(op);

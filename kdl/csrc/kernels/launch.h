@@ -344,6 +344,24 @@ struct TopkArgs {
 };
 hipError_t softmax_topk(const TopkArgs& a, hipStream_t s);
 
+// Pooled-feature embeddings (kernels/embed.hip): out[b][c] = (1/HW) sum_p x[b][p][c] for the F
+// channels of each image, accumulated in fp32 in a fixed order (replays are bit-identical).
+// norm = 1: each row is then divided by max(||row||_2, 1e-12), torch.nn.functional.normalize's
+// rule: an all-zero row stays zero. HW = 1 is a cast of one row (the ViT class token).
+// F % 8 == 0, 8 <= F <= 4096 (kEmbedMaxF: 16 values per thread of the norm's workgroup),
+// ldx % 8 == 0, ldx >= F, ldo >= F, x 16-byte aligned, 1 <= B <= 65535, HW >= 1, dt and norm
+// 0 or 1; anything else is hipErrorInvalidValue and nothing is launched. Columns F..ldo of
+// out are not written. One launch, two with norm. (EmbedArgs is the ViT token embedding's.)
+constexpr int kEmbedMaxF = 4096;
+struct EmbedRowsArgs {
+  const uint16_t* x;      // [B][HW][ldx] bf16 / fp16, F used per pixel
+  float* out;             // [B][ldo] fp32, F written per row
+  int B, HW, F, ldx, ldo;
+  int dt;                 // element type of x: 0 bf16, 1 fp16
+  int norm;               // 0 raw mean, 1 L2-normalised
+};
+hipError_t embed_rows(const EmbedRowsArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

@@ -43,10 +43,13 @@ def unpack_topk(rows) -> tuple:
     return a[..., :k].view(np.int32).copy(), a[..., k:].view(np.float32).copy()
 
 
+EMBED_MODES = ("", "raw", "l2")
+
+
 class EngineBase:
     model_name = "model"
 
-    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0):
+    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = ""):
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -63,7 +66,15 @@ class EngineBase:
         if topk < 0:
             raise ValueError(f"topk must be >= 0, got {topk}")
         self.topk = int(topk)
-        self.logit_slots: list[torch.Tensor] = []   # topk only: per-slot fp32 logits the head writes
+        self.logit_slots: list[torch.Tensor] = []   # topk / embed only: per-slot fp32 logits the head writes
+        # embedding outputs: "" = the output is the fp32 logits; "raw" / "l2" = one more step writes
+        # the pooled features in front of the head into the output rows (_enable_embed)
+        if embed not in EMBED_MODES:
+            raise ValueError(f"embed must be one of {EMBED_MODES}, got {embed!r}")
+        if embed and topk:
+            raise ValueError("embed and topk both replace the output rows: set one of them")
+        self.embed = embed
+        self._embed_step: Step | None = None
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -72,12 +83,13 @@ class EngineBase:
 
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
-        if self.topk:
+        if self.topk or self.embed:
             return _lib.ptr(self._logit_slot(self._slot))
         return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
 
     def slot_logits(self, slot: int) -> torch.Tensor:
-        """Output buffer of a slot: fp32 logits, or the packed top-k rows of a ``topk`` engine."""
+        """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, or the
+        feature rows of an ``embed`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
 
     # ---------------------------------------------------------------- classification outputs
@@ -112,8 +124,46 @@ class EngineBase:
                                               K=self.topk, ldx=lg.shape[1]))
 
     def last_logits(self, slot: int = 0) -> torch.Tensor:
-        """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without ``topk``."""
-        return self._logit_slot(slot) if self.topk else self.slot_logits(slot)
+        """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without
+        ``topk`` / ``embed``."""
+        return self._logit_slot(slot) if (self.topk or self.embed) else self.slot_logits(slot)
+
+    # ---------------------------------------------------------------- embedding outputs
+    def embed_source(self) -> tuple:
+        """A family's pooled-feature source: (buffer name, HW, row stride in elements, F, element
+        type: 0 bf16 / 1 fp16). The embedding of an image is the mean over the buffer's HW pixels
+        of its first F channels: what the head pools before its dense layers."""
+        raise NotImplementedError
+
+    @property
+    def embed_dim(self) -> int:
+        """F: floats per embedding row (whether or not this engine was built with ``embed``)."""
+        return self.embed_source()[3]
+
+    def _enable_embed(self) -> None:
+        """Called by a family's constructor next to ``_enable_topk``. With ``embed`` "raw" or "l2"
+        the head keeps writing the per-slot logits, a last step of kind "embed" (kernels/embed.hip)
+        pools ``embed_source()`` and ``self.logits`` -- the output the executor copies to the host
+        and ``forward`` returns -- becomes [max_batch, F] fp32: the mean over the pixels, for "l2"
+        divided by max(its L2 norm, 1e-12). The step is named "embed_rows" (ViT's token
+        embedding is the step "embed") and names its source in ``src``, so the stage pipeline's
+        buffer renaming reaches it through ``_ptr``."""
+        if not self.embed:
+            return
+        assert not self.inputs, "embed is set at construction, before input slots exist"
+        src, _, _, F, _ = self.embed_source()
+        if F % 8 or F > _lib.lib().EMBED_MAX_F:
+            raise ValueError(f"embed: {F} features; the kernel takes a multiple of 8 up to {_lib.lib().EMBED_MAX_F}")
+        self.logit_slots = [self.logits]
+        self.logits = torch.zeros((self.max_batch, F), dtype=torch.float32, device=self.device)
+        self._embed_step = Step("embed", "embed_rows", src=src)
+        self.steps.append(self._embed_step)
+
+    def _emit_embed(self, prog, step: Step, b: int) -> None:
+        _, hw, ldx, F, dt = self.embed_source()
+        out = self.outputs[self._slot] if self.outputs else self.logits
+        prog.add_embed_rows(step.name, dict(x=self._ptr(step.src), out=_lib.ptr(out), B=b, HW=hw, F=F, ldx=ldx,
+                                            ldo=out.shape[1], dt=dt, norm=int(self.embed == "l2")))
 
     def add_input_slots(self, n: int) -> list[torch.Tensor]:
         """Extra static input AND logits buffers, each slot with its own captured
@@ -200,6 +250,8 @@ class EngineBase:
                 self._remap = m
                 if st.kind == "topk":
                     self._emit_topk(prog, st, b)
+                elif st is self._embed_step:
+                    self._emit_embed(prog, st, b)
                 else:
                     self._emit(prog, st, b)
 
@@ -221,7 +273,8 @@ class EngineBase:
     @torch.no_grad()
     def forward(self, x: torch.Tensor, capture: bool = True) -> torch.Tensor:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
-        (a ``topk`` engine: the packed rows [n, 2K], see ``unpack_topk``)."""
+        (a ``topk`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed`` engine: the
+        fp32 feature rows [n, F])."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

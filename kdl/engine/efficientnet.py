@@ -53,8 +53,8 @@ class EfficientNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
-                 topk: int = 0):
-        super().__init__(device, max_batch, buckets, topk)
+                 topk: int = 0, embed: str = ""):
+        super().__init__(device, max_batch, buckets, topk, embed)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()
@@ -62,6 +62,7 @@ class EfficientNetEngine(EngineBase):
         self._build(params)
         self._alloc()
         self._enable_topk()
+        self._enable_embed()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -166,6 +167,11 @@ class EfficientNetEngine(EngineBase):
         if name == "logits":
             return self.output_ptr()
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
+
+    def embed_source(self) -> tuple:
+        """features.8's output, the input of the avgpool step: 19 x 19 pixels of 2560 bf16."""
+        gap = next(s for s in self.steps if s.kind == "gap")
+        return "E", gap.geom[0] * gap.geom[1], E.HEAD, E.HEAD, 0
 
     def scratch_buffers(self) -> list[str]:
         """SE partial pools (written by the dw kernel, not a step dst) and scales: used

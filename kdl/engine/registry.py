@@ -21,6 +21,15 @@ class ModelInfo:
     dtype: str = "bf16"       # compute dtype of the engine (bench.py's "dtype" field)
     tuning: str = ""          # tuning-table family name when it differs from ``name``
     stage_cut: str = ""       # default stage-pipeline cut (stages.py) for bench / serving; "" = lanes
+    features: int = 0         # F: floats of the pooled feature vector in front of the head
+    feature_oracle: Callable = None   # (params, uint8 NHWC) -> fp32 [n, F], what engines pool with embed=
+
+
+def _no_grad_mean(base, p, x_nchw):
+    """Spatial mean of a family's fp32 feature map [n, F, H, W]: Keras ``pooling="avg"``."""
+    import torch
+    with torch.no_grad():
+        return base(p, x_nchw).mean(dim=(2, 3))
 
 
 def _xception():
@@ -32,7 +41,9 @@ def _xception():
                      lambda p, max_batch, device, **kw: XceptionEngine(p, max_batch=max_batch, device=device,
                                                                        in_kind="u8", **kw),
                      lambda p, x: X.xception_forward(p, x.float() / 127.5 - 1.0),
-                     stage_cut="block8_sepconv3")
+                     stage_cut="block8_sepconv3", features=X.DEFAULT_HEAD.features,
+                     feature_oracle=lambda p, x: _no_grad_mean(X.base_forward, p, (x.float() / 127.5 - 1.0)
+                                                               .permute(0, 3, 1, 2).contiguous()))
 
 
 def _resnet50(dtype: str = "fp16"):
@@ -47,7 +58,8 @@ def _resnet50(dtype: str = "fp16"):
                                                                      dtype=dtype, **kw),
                      # three stages (3 compute streams): +1.3-1.9 % over the round-2 cut after layer3.1
                      # (profiles/stages3_ab_r3.txt)
-                     R.resnet_forward, dtype=dtype, tuning="resnet50", stage_cut="layer2.1.conv3,layer3.3.conv3")
+                     R.resnet_forward, dtype=dtype, tuning="resnet50", stage_cut="layer2.1.conv3,layer3.3.conv3",
+                     features=2048, feature_oracle=lambda p, x: _no_grad_mean(R.features, p, R.preprocess(x)))
 
 
 def _vit_b16():
@@ -57,7 +69,8 @@ def _vit_b16():
                      "ViT-B/16 224x224 (torchvision layout, 86,567,656 params)",
                      lambda seed=0: V.init_params(seed=seed),
                      lambda p, max_batch, device, **kw: ViTEngine(p, max_batch=max_batch, device=device, **kw),
-                     V.vit_forward, stage_cut="encoder.layers.encoder_layer_5.mlp.3")
+                     V.vit_forward, stage_cut="encoder.layers.encoder_layer_5.mlp.3",
+                     features=V.DIM, feature_oracle=V.vit_features)
 
 
 def _efficientnet_b7():
@@ -68,7 +81,8 @@ def _efficientnet_b7():
                      lambda seed=0: E.init_params(seed=seed),
                      lambda p, max_batch, device, **kw: EfficientNetEngine(p, max_batch=max_batch, device=device,
                                                                            **kw),
-                     E.efficientnet_forward, stage_cut="features.4.9.block.3")
+                     E.efficientnet_forward, stage_cut="features.4.9.block.3",
+                     features=E.HEAD, feature_oracle=lambda p, x: _no_grad_mean(E.features, p, E.preprocess(x)))
 
 
 def _vit_b16_fp8():
@@ -80,7 +94,8 @@ def _vit_b16_fp8():
                      lambda p, max_batch, device, **kw: ViTEngine(p, max_batch=max_batch, device=device, fp8=True,
                                                                   **kw),
                      V.vit_forward, dtype="fp8-e4m3 linears / bf16 rest",
-                     stage_cut="encoder.layers.encoder_layer_5.mlp.3")
+                     stage_cut="encoder.layers.encoder_layer_5.mlp.3",
+                     features=V.DIM, feature_oracle=V.vit_features)
 
 
 _FACTORIES = {"xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),

@@ -46,10 +46,10 @@ class ResNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
-                 dtype: str = "fp16", topk: int = 0):
+                 dtype: str = "fp16", topk: int = 0, embed: str = ""):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
-        super().__init__(device, max_batch, buckets, topk)
+        super().__init__(device, max_batch, buckets, topk, embed)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind
@@ -61,6 +61,7 @@ class ResNetEngine(EngineBase):
         self._build(params)
         self._alloc()
         self._enable_topk()
+        self._enable_embed()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -152,6 +153,13 @@ class ResNetEngine(EngineBase):
         if name == "logits":
             return self.output_ptr()
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
+
+    def embed_source(self) -> tuple:
+        """The input of the avgpool step: layer4's output, 7 x 7 pixels of 2048 fp16 / bf16."""
+        gap = next(s for s in self.steps if s.kind == "gap")
+        h, w, c, border = self.shapes[gap.src]
+        assert border == 0
+        return gap.src, h * w, c, gap.extra["F"], self.dt
 
     def scratch_buffers(self) -> list[str]:
         return []

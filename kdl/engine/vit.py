@@ -45,8 +45,8 @@ class ViTEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
-                 topk: int = 0):
-        super().__init__(device, max_batch, buckets, topk)
+                 topk: int = 0, embed: str = ""):
+        super().__init__(device, max_batch, buckets, topk, embed)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"
@@ -62,6 +62,7 @@ class ViTEngine(EngineBase):
         self._build(params)
         self._alloc()
         self._enable_topk()
+        self._enable_embed()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -153,6 +154,10 @@ class ViTEngine(EngineBase):
 
     def _ptr(self, name: str) -> int:
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
+
+    def embed_source(self) -> tuple:
+        """The normalised class token in front of heads.head: one row of 768 bf16 per image."""
+        return "CLS", 1, self.ld["CLS"], V.DIM, 0
 
     def scratch_buffers(self) -> list[str]:
         return []

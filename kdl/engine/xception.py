@@ -44,8 +44,8 @@ class XceptionEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
-                 tune_file: str | Path | None = None, topk: int = 0):
-        super().__init__(device, max_batch, buckets, topk)
+                 tune_file: str | Path | None = None, topk: int = 0, embed: str = ""):
+        super().__init__(device, max_batch, buckets, topk, embed)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
@@ -67,6 +67,7 @@ class XceptionEngine(EngineBase):
         self._build(params)
         self._alloc()
         self._enable_topk()
+        self._enable_embed()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -245,6 +246,10 @@ class XceptionEngine(EngineBase):
             return self.output_ptr()
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
 
+    def embed_source(self) -> tuple:
+        """block14's output, the map the head's fused pool reads: 10 x 10 pixels of 2048 bf16."""
+        h, w, ld = self.shapes[self.feat_buf]
+        return self.feat_buf, h * w, ld, self.head.features, 0
 
     def apply_tuning(self, d: dict) -> None:
         """The conv layers' table plus the optional fused-stem entry (an int: stem_conv3x3 config)."""

@@ -1,6 +1,8 @@
 """Serving gateway: ``POST /predict {"url": ...}`` -> ``{label: logit}``;
 ``POST /classify {"url": ...}`` -> ``[{"label": ..., "score": ...}, ...]`` (the model server's
-top-K classes and softmax scores, its label strings: the classify signature of the mode).
+top-K classes and softmax scores, its label strings: the classify signature of the mode);
+``POST /embed {"url": ...}`` -> ``{"embedding": [...]}`` (the pooled feature vector in front of the
+model's head: the embed signature of the mode).
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -34,7 +36,7 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_response)
+                     process_embed_response, process_response)
 
 
 class GatewayConfig:
@@ -124,10 +126,21 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             return grpc_fail(e)
         return jsonify(process_response(pb_result, cfg.labels, cfg.output_key))
 
-    # the classify signature of each mode; compat and uint8 resize here, as for /predict, and
-    # both send uint8 pixels (the classify signatures take no f32 input)
+    # the classify / embed signature of each mode; compat and uint8 resize here, as for /predict,
+    # and both send uint8 pixels (these signatures take no f32 input)
     classify_sig = {"bytes": ("classify_bytes", "image_bytes"), "raw": ("classify_image", "images")}.get(
         cfg.mode, ("classify", "images"))
+    embed_sig = {"bytes": ("embed_bytes", "image_bytes"), "raw": ("embed_image", "images")}.get(
+        cfg.mode, ("embed", "images"))
+
+    def uint8_input(img):
+        if cfg.mode == "bytes":
+            return [img]
+        if cfg.mode == "raw":
+            return np.asarray(img, dtype=np.uint8)[None]
+        if cfg.preprocess != pp.NEAREST_SPEC:
+            return pp.apply_spec_pil(img, cfg.preprocess, pp.TARGET[0])[None]
+        return pp.to_uint8(img)[None]
 
     @app.route("/classify", methods=["POST"])
     def classify():
@@ -138,20 +151,28 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             img = load(body["url"])
         except LookupError as e:
             return fail(502, str(e))
-        if cfg.mode == "bytes":
-            X = [img]
-        elif cfg.mode == "raw":
-            X = np.asarray(img, dtype=np.uint8)[None]
-        elif cfg.preprocess != pp.NEAREST_SPEC:
-            X = pp.apply_spec_pil(img, cfg.preprocess, pp.TARGET[0])[None]
-        else:
-            X = pp.to_uint8(img)[None]
         try:
-            req = make_request(X, cfg.model_name, classify_sig[0], classify_sig[1])
+            req = make_request(uint8_input(img), cfg.model_name, classify_sig[0], classify_sig[1])
             pb_result = next_stub().Predict(req, timeout=cfg.timeout)
         except grpc.RpcError as e:
             return grpc_fail(e)
         return jsonify(process_classify_response(pb_result)[0])
+
+    @app.route("/embed", methods=["POST"])
+    def embed():
+        body = request.get_json(silent=True)
+        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
+            return fail(400, 'request body must be JSON {"url": "<image url>"}')
+        try:
+            img = load(body["url"])
+        except LookupError as e:
+            return fail(502, str(e))
+        try:
+            req = make_request(uint8_input(img), cfg.model_name, embed_sig[0], embed_sig[1])
+            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
+        except grpc.RpcError as e:
+            return grpc_fail(e)
+        return jsonify({"embedding": process_embed_response(pb_result)[0]})
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

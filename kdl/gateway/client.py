@@ -72,3 +72,11 @@ def process_classify_response(pb_result) -> list[list[dict]]:
     labels = [v.decode() for v in cl.string_val]
     return [[{"label": labels[i * k + j], "score": float(sc.float_val[i * k + j])} for j in range(k)]
             for i in range(n)]
+
+
+def process_embed_response(pb_result) -> list[list[float]]:
+    """An embed signature's PredictResponse (``embedding`` DT_FLOAT [n, F]) -> per image, its F floats."""
+    t = pb_result.outputs["embedding"]
+    n, f = [d.size for d in t.tensor_shape.dim]
+    vals = np.asarray(t.float_val, dtype=np.float32).reshape(n, f)
+    return [[float(v) for v in row] for row in vals]

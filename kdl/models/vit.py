@@ -111,13 +111,18 @@ def encoder_layer(p, i, x):
 
 
 @torch.no_grad()
-def vit_forward(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
-    """fp32 oracle: uint8 NHWC [B,224,224,3] -> logits [B,1000]."""
+def vit_features(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
+    """fp32 oracle: uint8 NHWC [B,224,224,3] -> the normalised class token [B,768] in front of heads.head."""
     x = embed(p, preprocess(x_u8_nhwc))
     for i in range(DEPTH):
         x = encoder_layer(p, i, x)
-    c = F.layer_norm(x[:, 0], (DIM,), p["encoder.ln.weight"], p["encoder.ln.bias"], LN_EPS)
-    return c @ p["heads.head.weight"].t() + p["heads.head.bias"]
+    return F.layer_norm(x[:, 0], (DIM,), p["encoder.ln.weight"], p["encoder.ln.bias"], LN_EPS)
+
+
+@torch.no_grad()
+def vit_forward(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
+    """fp32 oracle: uint8 NHWC [B,224,224,3] -> logits [B,1000]."""
+    return vit_features(p, x_u8_nhwc) @ p["heads.head.weight"].t() + p["heads.head.bias"]
 
 
 @torch.no_grad()

@@ -74,6 +74,9 @@ class SignatureInfo:
     # empty / 0 for the signatures whose single output is the fp32 logits
     outputs: tuple = ()
     top_k: int = 0
+    # embed signatures (serving/embed.py): "raw" / "l2" = the single output is the pooled feature
+    # vector in front of the head, [-1, F] fp32; "" for every other signature
+    embed: str = ""
 
     def output_specs(self) -> tuple:
         return self.outputs or ((self.output_key, P.DT_FLOAT, self.output_shape),)
@@ -95,6 +98,9 @@ class ModelSource:
     labels: list = field(default_factory=list)
     classify_k: int = 0
     classify_feature: str = "image/encoded"
+    # embedding outputs (serving/embed.py): "none" | "l2", and F
+    embed_normalize: str = "none"
+    embed_dim: int = 0
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -114,11 +120,12 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 
 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
-                     classify_top_k: int | None = None) -> ModelSource:
+                     classify_top_k: int | None = None, embedding_normalize: str | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
-    (the server's --classify_top_k) overrides the version's classify K (serving/classify.py)."""
+    (the server's --classify_top_k) overrides the version's classify K (serving/classify.py),
+    ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -132,6 +139,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         raise ValueError(f"{path}: {e}") from e
     from .classify import add_signatures
     add_signatures(src, path, classify_top_k)
+    from .embed import add_signatures as add_embed_signatures
+    add_embed_signatures(src, path, embedding_normalize)
     return src
 
 
@@ -390,6 +399,8 @@ class GPUExecutor(_Executor):
         in_kind = "u8" if r.sig.input_dtype == P.DT_UINT8 else "f32"
         dev = f"cuda:{self.device}"
         tk = dict(topk=r.topk) if r.topk else {}               # the classify runner: rows of 2K words
+        if r.embed:
+            tk = dict(embed=r.embed)                           # the embed runner: rows of F floats
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -579,11 +590,12 @@ class CPUExecutor(_Executor):
         u8 = self.runner.sig.input_dtype == P.DT_UINT8
         S = src.input_size
         self.staging = torch.zeros((bs, S, S, 3), dtype=torch.uint8 if u8 else torch.float32)
-        self.out = torch.zeros((bs, src.classes), dtype=torch.float32)
+        self.out = torch.zeros((bs, self.runner.out_cols), dtype=torch.float32)
         self.u8 = u8
-        if src.family != "xception":
+        if src.family != "xception" or self.runner.embed:
             from ..engine import registry
-            self.oracle = registry.get(src.family).oracle
+            info = registry.get(src.family)
+            self.oracle = info.feature_oracle if self.runner.embed else info.oracle
 
     def staging_ptr(self, slot: int = 0) -> int:
         return self.staging.data_ptr()
@@ -591,6 +603,13 @@ class CPUExecutor(_Executor):
     def execute(self, bucket: int, n_real: int) -> int:
         x = self.staging[:n_real]
         src = self.runner.source
+        if self.runner.embed:              # the embed runner: fp32 feature rows, normalised by the same rule
+            rows = self.oracle(src.params, x)
+            if self.runner.embed == "l2":
+                from .embed import l2_rule
+                rows = torch.from_numpy(l2_rule(rows.numpy()))
+            self.out[:n_real] = rows
+            return self.out.data_ptr()
         if src.family != "xception":
             self.out[:n_real] = self.oracle(src.params, x)
             return self.out.data_ptr()
@@ -620,7 +639,7 @@ class NullExecutor(_Executor):
         r, rt = self.runner, _lib.rt()
         S = r.source.input_size
         item = S * S * 3 * (1 if r.sig.input_dtype == P.DT_UINT8 else 4)
-        self.fake = rt.FakeBackend(nslots=2, item_bytes=item, max_batch=r.buckets[-1], out_cols=r.source.classes)
+        self.fake = rt.FakeBackend(nslots=2, item_bytes=item, max_batch=r.buckets[-1], out_cols=r.out_cols)
         fail, delay_us = self.faults.native_args(self.name)
         self.native = rt.Executor(r.batcher, self.fake, r.exec_group, name=self.name, eager=self.eager,
                                   max_failures=self.max_failures, fail_batches=fail, delay_us=delay_us)
@@ -637,10 +656,14 @@ class SignatureRunner:
     """One C++ batcher + the executors serving one signature of one version."""
 
     topk = 0            # K: the GPU engines end in the top-k step and rows are 2K words (ClassifyRunner)
+    embed = ""          # "raw" / "l2": the engines end in the embed step and rows are F floats (EmbedRunner)
+    embed_dim = 0
 
     @property
     def out_cols(self) -> int:
         """32-bit words per result row, from the executor to the waiting handler."""
+        if self.embed:
+            return self.embed_dim
         return 2 * self.topk if self.topk else self.source.classes
 
     def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
@@ -764,6 +787,19 @@ class ClassifyRunner(SignatureRunner):
         return rows if self.topk else pack_rows(*topk_rule(rows, self.k))
 
 
+class EmbedRunner(SignatureRunner):
+    """The ``embed`` signature: like ``serving_uint8``'s runner, but a result row is the pooled
+    feature vector in front of the head, F fp32 (serving/embed.py). GPU executors build their
+    engines with ``embed="raw"`` or ``"l2"``, so the rows come out of the captured program; the CPU
+    executor returns the family's ``feature_oracle`` rows, normalised in numpy for "l2"; the null
+    executor's rows are F wide."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.embed = sig.embed
+        self.embed_dim = sig.output_shape[1]
+        super().__init__(sig, source, cfg, devices)
+
+
 class Servable:
     """One loaded model version (all its signatures)."""
 
@@ -793,7 +829,16 @@ class Servable:
                     raise ServingError("INVALID_ARGUMENT", f"Serving signature name: \"{sig_name}\" not found "
                                        "in signature def")
                 from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
-                if sig_name == CLASSIFY_SIGNATURE:
+                from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
+                if sig_name == EMBED_SIGNATURE:
+                    r = EmbedRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == EMBED_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(EMBED_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == EMBED_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(EMBED_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == CLASSIFY_SIGNATURE:
                     r = ClassifyRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 elif sig_name == CLASSIFY_IMAGE_SIGNATURE:
                     r = ImageRunner(self.signatures[sig_name], self.runner(CLASSIFY_SIGNATURE), self._devices,
@@ -823,7 +868,7 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # a wrapper (serving_image / serving_bytes / classify_image / classify_bytes) has no batcher
+        # a wrapper (serving_image / serving_bytes, the classify_* and embed_* pairs) has no batcher
         # of its own: it feeds its inner runner's, so that is where its work shows
         def batcher(r):
             return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)

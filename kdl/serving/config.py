@@ -92,6 +92,9 @@ class ServerConfig:
     # K of the classify signatures (serving/classify.py); None = the model version's own
     # "classify": {"top_k": K}, else 5. 1..32, clipped to the class count
     classify_top_k: int | None = None
+    # normalisation of the embed signatures (serving/embed.py): "none" | "l2"; None = the model
+    # version's own "embedding": {"normalize": ...}, else none
+    embedding_normalize: str | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -192,6 +195,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="classes and scores per image of the classify / classify_image / classify_bytes signatures "
                          "and the Classify RPC (1..32, clipped to the class count); overrides the model version's "
                          "\"classify\": {\"top_k\": K} (env KDL_CLASSIFY_TOP_K, default: the version's, else 5)")
+    ap.add_argument("--embedding_normalize", choices=["none", "l2"], default=None,
+                    help="rows of the embed / embed_image / embed_bytes signatures: none = the pooled features as they "
+                         "are (Keras pooling=\"avg\"), l2 = each divided by its L2 norm; overrides the model version's "
+                         "\"embedding\": {\"normalize\": ...} (env KDL_EMBEDDING_NORMALIZE, default: the version's, "
+                         "else none)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -252,6 +260,7 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         jpeg_entropy=a.jpeg_entropy or env.get("KDL_JPEG_ENTROPY", "") or "host",
                         classify_top_k=(a.classify_top_k if a.classify_top_k is not None
                                         else int(env["KDL_CLASSIFY_TOP_K"]) if env.get("KDL_CLASSIFY_TOP_K") else None),
+                        embedding_normalize=a.embedding_normalize or env.get("KDL_EMBEDDING_NORMALIZE") or None,
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

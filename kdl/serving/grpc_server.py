@@ -182,6 +182,8 @@ class Servicer:
                 out = classify_response(s, sig, logits, req["output_filter"])
             else:
                 out = rt.build_predict_response([(sig.output_key, logits)], s.name, s.version, sig_name)
+            if sig.embed:               # answers built here; the native front-end's learned route counts
+                METRICS.inc("kdl_embed_total", signature=sig.name)      # its own in kdl_requests_total only
             # per-request stage trace (SURVEY.md §5 tracing): parse+validate, batcher wait+run, respond
             METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
             METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")

@@ -38,7 +38,7 @@ def latest_version_source(cfg: ServerConfig):
     if not versions:
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
     return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess,
-                            classify_top_k=cfg.classify_top_k)
+                            classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize)
 
 
 class ModelManager:
@@ -75,7 +75,8 @@ class ModelManager:
         t0 = time.perf_counter()
         try:
             src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess,
-                                   classify_top_k=self.cfg.classify_top_k)
+                                   classify_top_k=self.cfg.classify_top_k,
+                                   embedding_normalize=self.cfg.embedding_normalize)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

@@ -138,7 +138,7 @@ class NativeFront:
                 return
             self.front.set_route(model=s.name, signature=sig_name, version=s.version, input_key=sig.input_key,
                                  output_key=sig.output_key, dtype=sig.input_dtype, image=sig.input_shape[1],
-                                 out_cols=s.source.classes, batcher=runner.batcher, u8=u8)
+                                 out_cols=runner.out_cols, batcher=runner.batcher, u8=u8)
             self._learned.add(key)
 
     def _changed(self) -> None:

@@ -8,6 +8,7 @@ Routes (TF-Serving REST semantics):
        {"signature_name"?, "inputs": ...}       -> {"outputs": ...}
        (serving_bytes: every value is {"b64": "<base64 of the image file>"})
        (classify signatures: {"classes": [...], "scores": [...]} per instance, or by column)
+       (embed signatures: the feature rows, as "predictions" or "outputs")
   POST /v1/models/<name>[/versions/<v>|/labels/<l>]:classify
        {"signature_name"?, "examples": [{"image/encoded": {"b64": ...}}, ...]}
                                                 -> {"results": [[["label", score], ...], ...]}
@@ -146,6 +147,8 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
         @staticmethod
         def _body(s, sig, out, rows: bool) -> dict:
             """The :predict answer: logits, or a classify signature's two named outputs."""
+            if sig.embed:
+                METRICS.inc("kdl_embed_total", signature=sig.name)
             if not sig.top_k:
                 return {"predictions": out.tolist()} if rows else {"outputs": out.tolist()}
             labels, scores = classify_outputs(s, sig, out)
