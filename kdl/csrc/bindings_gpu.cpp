@@ -123,7 +123,7 @@ AttnArgs attn_args(const py::dict& d) {
   a.qkv = P<const uint16_t>(d, "qkv"); a.out = P<uint16_t>(d, "out");
   a.out8 = P<uint8_t>(d, "out8"); a.inv_scale = F(d, "inv_scale", 1.f);
   a.B = I(d, "B"); a.T = I(d, "T"); a.H = I(d, "H"); a.dh = I(d, "dh", 64);
-  a.scale = F(d, "scale", 0.125f);
+  a.scale = F(d, "scale", 0.125f); a.algo = I(d, "algo", 0);
   return a;
 }
 DwkArgs dwk_args(const py::dict& d) {

@@ -321,8 +321,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 
 hipError_t attention(const AttnArgs& a, hipStream_t s) {
   if (a.dh != AT_DH || a.T <= 0 || a.H <= 0 || a.B <= 0) return hipErrorInvalidValue;
+  if (a.algo < 0 || a.algo > 2 || (a.algo == 1 && a.T > AW_TK)) return hipErrorInvalidValue;
   static const bool tiled = [] { const char* e = getenv("KDL_ATTN_TILED"); return e && atoi(e) != 0; }();
-  if (a.T <= AW_TK && !tiled) {
+  if (a.algo == 1 || (a.algo == 0 && a.T <= AW_TK && !tiled)) {
     const int waves = (a.T + 15) / 16;
     const size_t smem = (size_t)(AW_TK * AT_ROW + AT_DH * AW_VROW) * sizeof(uint16_t);
     hipLaunchKernelGGL(attn_head_kernel, dim3((unsigned)(a.B * a.H)), dim3(64 * waves), smem, s, a);

@@ -249,6 +249,10 @@ hipError_t layernorm(const LnArgs& a, hipStream_t s);
 
 // Multi-head self-attention (flash-style, online softmax) over a packed QKV buffer:
 // qkv [B*T][3*H*dh] bf16 (q | k | v, head-major inside each), out [B*T][H*dh] bf16.
+// Two kernels compute the same values: the whole-head one (one workgroup per (image, head),
+// all keys in LDS, T <= 256) and the query-tiled one (64 queries per workgroup, any T).
+// dh != 64, T <= 0, H <= 0, B <= 0, an algo outside 0..2 and algo 1 with T > 256 are
+// hipErrorInvalidValue, and nothing is launched.
 struct AttnArgs {
   const uint16_t* qkv;
   uint16_t* out;
@@ -256,6 +260,8 @@ struct AttnArgs {
   float inv_scale;
   int B, T, H, dh;        // dh = 64
   float scale;            // 1/sqrt(dh)
+  int algo;               // 0 = auto (whole-head if T <= 256, unless env KDL_ATTN_TILED forces the
+                          // query-tiled kernel), 1 = whole-head, 2 = query-tiled
 };
 hipError_t attention(const AttnArgs& a, hipStream_t s);
 

@@ -141,8 +141,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a) {
 
 // Two rows per wave (32 lanes per row, up to 4 chunks of 8 per lane: D <= 1024): every lane
 // is busy at D = 768 (the kernel above leaves half its lanes idle for a row's second chunk),
-// and sum / sum of squares reduce together in one 5-step butterfly instead of two dependent
-// 6-step ones (the row's statistics were a chain of 12 ds_bpermute latencies).
+// and a row reduces in 5-step butterflies instead of 6-step ones.
+//
+// Variance. Both kernels take it in two passes over the row in registers: the mean first, then
+// the sum of squared deviations from it. This kernel used to reduce sum and sum of squares in
+// one butterfly and form E[x^2] - mean^2, which cancels to nothing in fp32 once |mean| / std
+// reaches a few hundred (mean 300, std 1: both terms are 9e4 with an ulp of 8e-3, against a
+// variance of 1) and put rstd off by 0.4-0.9 % on such rows. The second butterfly costs no
+// time (profiles/layernorm_var.txt: it measured cheaper than one-pass sums about a pivot
+// element, the other exact form). The registers keep x - mean for the output pass, and the
+// mean is s / D by division, so a constant row has deviation 0 and gives beta exactly.
 __global__ __launch_bounds__(256) void layernorm2_kernel(LnArgs a) {
   const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
   const long r = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + half;
@@ -150,7 +158,7 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(LnArgs a) {
   const uint16_t* xr = a.x + (live ? r : 0) * a.ldx;
   const int C8 = a.D / 8;
   float v[LN_CH][8];
-  float s = 0.f, ss = 0.f;
+  float s = 0.f;
 #pragma unroll
   for (int j = 0; j < LN_CH; ++j) {
     const int c8 = hl + 32 * j;
@@ -162,20 +170,24 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(LnArgs a) {
       v[j][2 * d + 1] = bf_hi(u[d]);
     }
 #pragma unroll
+    for (int d = 0; d < 8; ++d) s += v[j][d];
+  }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  const float mu = s / (float)a.D;
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_CH; ++j) {
+    const float mj = live && hl + 32 * j < C8 ? mu : 0.f;   // an absent chunk is zeros about 0: it adds nothing
+#pragma unroll
     for (int d = 0; d < 8; ++d) {
-      s += v[j][d];
-      ss += v[j][d] * v[j][d];
+      v[j][d] -= mj;
+      sq += v[j][d] * v[j][d];
     }
   }
 #pragma unroll
-  for (int off = 16; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off);
-    ss += __shfl_xor(ss, off);
-  }
-  const float inv_d = 1.f / (float)a.D;
-  const float mean = s * inv_d;
-  const float var = fmaxf(ss * inv_d - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + a.eps);
+  for (int off = 16; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+  const float rstd = rsqrtf(sq / (float)a.D + a.eps);
   if (!live) return;
   uint16_t* yr = a.y + r * a.ldy;
 #pragma unroll
@@ -188,7 +200,7 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(LnArgs a) {
       const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
       float o8[8];
 #pragma unroll
-      for (int d = 0; d < 8; ++d) o8[d] = (v[j][d] - mean) * rstd * g[d] + bb[d];
+      for (int d = 0; d < 8; ++d) o8[d] = v[j][d] * rstd * g[d] + bb[d];   // v holds x - mean
       if (a.y8) {
         const float q = a.inv_scale;
         *(u32x2*)(a.y8 + r * a.ldy + c8 * 8) = (u32x2){pack_fp8x4(o8[0] * q, o8[1] * q, o8[2] * q, o8[3] * q),
