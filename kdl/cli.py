@@ -8,6 +8,11 @@
   make-synthetic <repo>/<version> [--seed] [--model xception|resnet50|vit_b16|efficientnet_b7]
                                              random-init weights of the exact architecture (Xception:
                                              a SavedModel; other families: torchvision-layout safetensors)
+  build-gallery <version_dir> <images_dir> [--device cpu|gpu]
+                                             the gallery of the similar signatures (serving/similar.py): every
+                                             image file of <images_dir>, in sorted order, through the
+                                             version's embed_bytes path with raw rows -> gallery.npy (fp32
+                                             [N, F]) + gallery_ids.txt (the file names) in <version_dir>
   serve [server flags...]                    same as python -m kdl.serving
 """
 from __future__ import annotations
@@ -32,6 +37,11 @@ def main(argv=None) -> int:
     m.add_argument("--seed", type=int, default=0)
     m.add_argument("--residual-offset", type=int, default=0)
     m.add_argument("--model", default="xception")
+    g = sub.add_parser("build-gallery")
+    g.add_argument("version_dir")
+    g.add_argument("images_dir")
+    g.add_argument("--device", choices=["cpu", "gpu"], default="cpu")
+    g.add_argument("--batch", type=int, default=8, help="images per forward")
     sv = sub.add_parser("serve")
     sv.add_argument("rest", nargs=argparse.REMAINDER)
     a = ap.parse_args(argv)
@@ -76,9 +86,42 @@ def main(argv=None) -> int:
         from .models import xception as X
         write_savedmodel(a.dst, to_keras_variables(X.init_params(seed=a.seed), residual_offset=a.residual_offset))
         print(f"wrote synthetic SavedModel to {a.dst}")
+    elif a.cmd == "build-gallery":
+        return build_gallery(Path(a.version_dir), Path(a.images_dir), a.device, a.batch)
     elif a.cmd == "serve":
         from .serving.server import main as serve_main
         return serve_main(a.rest)
+    return 0
+
+
+def build_gallery(version_dir: Path, images_dir: Path, device: str = "cpu", batch: int = 8) -> int:
+    import numpy as np
+
+    from .serving.backend import Servable, load_version_dir, pick_devices
+    from .serving.config import BatchingParams, ServerConfig
+    from .serving.similar import DEFAULT_GALLERY, IDS_FILE
+    names = sorted(p.name for p in images_dir.iterdir() if p.is_file())
+    if not names:
+        print(f"no image files in {images_dir}", file=sys.stderr)
+        return 1
+    cfg = ServerConfig(model_base_path=str(version_dir.parent), device=device, gpus=1,
+                       batching=BatchingParams(max_batch_size=batch, batch_timeout_micros=0,
+                                               allowed_batch_sizes=[batch]))
+    src = load_version_dir(version_dir, embedding_normalize="none", gallery=False)
+    s = Servable(version_dir.parent.name, int(version_dir.name) if version_dir.name.isdigit() else 1, src, cfg,
+                 pick_devices(cfg))
+    try:
+        runner = s.runner("embed_bytes")
+        rows = []
+        for i in range(0, len(names), batch):
+            files = [(images_dir / n).read_bytes() for n in names[i:i + batch]]
+            rows.append(np.asarray(runner.predict(files, len(files), 0), dtype=np.float32))
+    finally:
+        s.close()
+    gal = np.ascontiguousarray(np.concatenate(rows), dtype=np.float32)
+    np.save(version_dir / DEFAULT_GALLERY, gal, allow_pickle=False)
+    (version_dir / IDS_FILE).write_text("".join(n + "\n" for n in names))
+    print(f"wrote {version_dir / DEFAULT_GALLERY} {list(gal.shape)} and {version_dir / IDS_FILE}")
     return 0
 
 

@@ -214,6 +214,13 @@ EmbedRowsArgs embed_rows_args(const py::dict& d) {
   a.dt = I(d, "dt"); a.norm = I(d, "norm");
   return a;
 }
+GalleryTopkArgs gallery_topk_args(const py::dict& d) {
+  GalleryTopkArgs a{};
+  a.q = P<const float>(d, "q"); a.g = P<const uint16_t>(d, "g"); a.out = P<int32_t>(d, "out");
+  a.work = P<void>(d, "work");
+  a.B = I(d, "B"); a.N = I(d, "N"); a.F = I(d, "F"); a.K = I(d, "K"); a.ldq = I(d, "ldq"); a.ldg = I(d, "ldg");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -331,6 +338,14 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(embed_rows(a, S(s)), "embed_rows");
   });
+  m.def("gallery_topk", [](py::dict d, uintptr_t s) {
+    const auto a = gallery_topk_args(d);
+    py::gil_scoped_release nogil;
+    chk(gallery_topk(a, S(s)), "gallery_topk");
+  });
+  m.def("gallery_topk_workspace", [](int B, int N, int K) { return gallery_topk_workspace(B, N, K); });
+  m.attr("GALLERY_MAX_N") = int(kGalleryMaxN);
+  m.attr("GALLERY_CHUNK") = int(kGalleryChunk);
   m.attr("EMBED_MAX_F") = int(kEmbedMaxF);
   m.attr("TOPK_MAX_NC") = int(kTopkMaxNC);
   m.attr("TOPK_MAX_K") = int(kTopkMaxK);
@@ -653,6 +668,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_embed_rows", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_EMBED_ROWS; op.name = name; op.er = embed_rows_args(d); p.add(op);
+      })
+      .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);
       })
       .def("add_gap", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GAP; op.name = name; op.gp = gap_args(d); p.add(op);

@@ -14,20 +14,6 @@
 
 namespace kdl {
 
-// a ranks before b: larger logit, equal logits by smaller index (idx INT_MAX = no candidate)
-__device__ __forceinline__ bool topk_before(float av, int ai, float bv, int bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
-__device__ __forceinline__ void topk_wave_best(float& v, int& i) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ov = __shfl_xor(v, m, 64);
-    const int oi = __shfl_xor(i, m, 64);
-    if (topk_before(ov, oi, v, i)) { v = ov; i = oi; }
-  }
-}
-
 template <int R>
 __global__ __launch_bounds__(256) void softmax_topk_kernel(TopkArgs a) {
   const int lane = threadIdx.x & 63;

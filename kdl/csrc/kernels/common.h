@@ -115,6 +115,21 @@ struct Elt<1> {
   static __device__ __forceinline__ uint16_t from_f32(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
 };
 
+// Top-k ranking shared by classify.hip and similar.hip. a ranks before b: larger value, equal
+// values by smaller index (idx INT_MAX = no candidate)
+__device__ __forceinline__ bool topk_before(float av, int ai, float bv, int bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+__device__ __forceinline__ void topk_wave_best(float& v, int& i) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ov = __shfl_xor(v, m, 64);
+    const int oi = __shfl_xor(i, m, 64);
+    if (topk_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+}
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be
 // bijective"): blocks b, b+8, ... are dispatched to one XCD, so give each XCD a
 // contiguous run of logical tiles; neighbouring tiles then share an L2.

@@ -368,6 +368,33 @@ struct EmbedRowsArgs {
 };
 hipError_t embed_rows(const EmbedRowsArgs& a, hipStream_t s);
 
+// Gallery search (kernels/similar.hip): score[b][j] = sum_i q[b][i] * g[j][i] of B fp32 query
+// rows (an embed_rows output) against N stored bf16 rows, and per query the K best rows: by
+// descending computed score, equal scores by ascending row index (softmax_topk's rule). Output
+// row: 2K 32-bit words, K int32 row indices then K fp32 scores (TopkArgs' layout). The bf16
+// values are taken as they stand and the query as fp32 (three bf16 terms per value on the
+// matrix cores, fp32 accumulation): |score - exact| <= (F + 16) * 2^-23 * sum_i |q_i| * |g_ji|.
+// Every row's sum runs in the same order, so equal rows give bit-equal scores and replays are
+// bit-identical. Three launches: a small one splits the queries into their bf16 terms in `work`,
+// a scan in which each workgroup keeps the K best of its kGalleryChunk rows in `work`, then a
+// merge with one wave per query. The gallery is read once
+// for B <= 32 and once per further 32 queries. Nothing is loaded past row N - 1 or column F - 1;
+// pad columns of q and g are not read and out is written 2K words per row.
+// F % 8 == 0, 8 <= F <= kEmbedMaxF, ldg % 8 == 0, ldg >= F, ldq >= F, 1 <= K <= min(N, kTopkMaxK),
+// 1 <= N <= kGalleryMaxN, 1 <= B <= 1024, g and work 16-byte aligned; anything else is
+// hipErrorInvalidValue and nothing is launched. NaN in q gives unspecified rows.
+constexpr int kGalleryMaxN = 1 << 24;
+constexpr int kGalleryChunk = 256;   // gallery rows per workgroup of the scan
+struct GalleryTopkArgs {
+  const float* q;         // [B][ldq] fp32 query rows, F used per row
+  const uint16_t* g;      // [N][ldg] bf16 gallery rows, F used per row, 16-byte aligned
+  int32_t* out;           // [B][2K]
+  void* work;             // split queries + partial candidates: gallery_topk_workspace(B, N, K) bytes, 16-byte aligned
+  int B, N, F, K, ldq, ldg;
+};
+size_t gallery_topk_workspace(int B, int N, int K);
+hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

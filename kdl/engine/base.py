@@ -44,12 +44,25 @@ def unpack_topk(rows) -> tuple:
 
 
 EMBED_MODES = ("", "raw", "l2")
+SIMILAR_METRICS = ("cosine", "dot")
+
+
+@dataclass
+class Similar:
+    """Gallery search outputs of an engine (``EngineBase(similar=...)``). ``gallery`` is the device
+    tensor [N, ldg] of stored bf16 rows (``kdl.serving.similar.load_gallery``'s values), ldg a
+    multiple of 8 and at least the family's F. It is shared: every engine on that device built
+    from this object reads the same copy. ``k`` neighbours per image (clipped to N); ``metric``
+    "cosine" normalises the query rows (the stored rows are already unit length), "dot" does not."""
+    gallery: torch.Tensor
+    k: int = 5
+    metric: str = "cosine"
 
 
 class EngineBase:
     model_name = "model"
 
-    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = ""):
+    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None):
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -75,6 +88,13 @@ class EngineBase:
             raise ValueError("embed and topk both replace the output rows: set one of them")
         self.embed = embed
         self._embed_step: Step | None = None
+        # gallery search outputs: None = the output is the fp32 logits; a ``Similar`` = two more
+        # steps write the K nearest gallery rows of each image's features (_enable_similar)
+        if similar is not None and (topk or embed):
+            raise ValueError("similar, embed and topk all replace the output rows: set one of them")
+        self.similar: Similar | None = similar
+        self.feature_slots: list[torch.Tensor] = []   # similar only: per-slot fp32 features [max_batch, F]
+        self._similar_work: list[torch.Tensor] = []   # similar only: per-slot gallery_topk workspace
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -83,13 +103,13 @@ class EngineBase:
 
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
-        if self.topk or self.embed:
+        if self.topk or self.embed or self.similar:
             return _lib.ptr(self._logit_slot(self._slot))
         return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
 
     def slot_logits(self, slot: int) -> torch.Tensor:
-        """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, or the
-        feature rows of an ``embed`` engine."""
+        """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, the
+        feature rows of an ``embed`` engine, or the packed neighbour rows of a ``similar`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
 
     # ---------------------------------------------------------------- classification outputs
@@ -125,8 +145,8 @@ class EngineBase:
 
     def last_logits(self, slot: int = 0) -> torch.Tensor:
         """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without
-        ``topk`` / ``embed``."""
-        return self._logit_slot(slot) if (self.topk or self.embed) else self.slot_logits(slot)
+        ``topk`` / ``embed`` / ``similar``."""
+        return self._logit_slot(slot) if (self.topk or self.embed or self.similar) else self.slot_logits(slot)
 
     # ---------------------------------------------------------------- embedding outputs
     def embed_source(self) -> tuple:
@@ -161,9 +181,73 @@ class EngineBase:
 
     def _emit_embed(self, prog, step: Step, b: int) -> None:
         _, hw, ldx, F, dt = self.embed_source()
-        out = self.outputs[self._slot] if self.outputs else self.logits
+        if self.similar is not None:       # the query rows of the "similar" step
+            out, norm = self.feature_slot(self._slot), int(self.similar.metric == "cosine")
+        else:
+            out, norm = (self.outputs[self._slot] if self.outputs else self.logits), int(self.embed == "l2")
         prog.add_embed_rows(step.name, dict(x=self._ptr(step.src), out=_lib.ptr(out), B=b, HW=hw, F=F, ldx=ldx,
-                                            ldo=out.shape[1], dt=dt, norm=int(self.embed == "l2")))
+                                            ldo=out.shape[1], dt=dt, norm=norm))
+
+    # ---------------------------------------------------------------- gallery search outputs
+    def _enable_similar(self) -> None:
+        """Called by a family's constructor next to ``_enable_embed``. With ``similar`` the head keeps
+        writing the per-slot logits, a step "embed_rows" pools ``embed_source()`` into a per-slot
+        fp32 feature buffer [max_batch, F] (L2-normalised for "cosine"), and a last step of kind
+        "similar" (kernels/similar.hip) scores those rows against the gallery. ``self.logits`` --
+        the output the executor copies to the host and ``forward`` returns -- becomes
+        [max_batch, 2K] 32-bit words per row: K int32 gallery row indices, then K fp32 scores
+        (``unpack_topk``). Feature buffers and workspaces are per slot, like the logits."""
+        sim = self.similar
+        if sim is None:
+            return
+        assert not self.inputs, "similar is set at construction, before input slots exist"
+        lib = _lib.lib()
+        src, _, _, F, _ = self.embed_source()
+        g = sim.gallery
+        if sim.metric not in SIMILAR_METRICS:
+            raise ValueError(f"similar: metric must be one of {SIMILAR_METRICS}, got {sim.metric!r}")
+        if F % 8 or F > lib.EMBED_MAX_F:
+            raise ValueError(f"similar: {F} features; the kernel takes a multiple of 8 up to {lib.EMBED_MAX_F}")
+        if (g.dim() != 2 or g.dtype != torch.bfloat16 or not self._on_device(g) or not g.is_contiguous()
+                or g.shape[1] < F or g.shape[1] % 8 or not 1 <= g.shape[0] <= lib.GALLERY_MAX_N):
+            raise ValueError(f"similar: the gallery must be a contiguous bf16 [N, >= {F}] tensor on {self.device} "
+                             f"with 1 <= N <= {lib.GALLERY_MAX_N} and a row stride that is a multiple of 8, got "
+                             f"{tuple(g.shape)} {g.dtype} on {g.device}")
+        if sim.k < 1:
+            raise ValueError(f"similar: k must be >= 1, got {sim.k}")
+        self.similar_k = min(int(sim.k), g.shape[0])
+        if self.similar_k > lib.TOPK_MAX_K:
+            raise ValueError(f"similar: k must be <= {lib.TOPK_MAX_K}, got {self.similar_k}")
+        self.logit_slots = [self.logits]
+        self.feature_slots = [torch.zeros((self.max_batch, F), dtype=torch.float32, device=self.device)]
+        self.logits = torch.zeros((self.max_batch, 2 * self.similar_k), dtype=torch.float32, device=self.device)
+        self._embed_step = Step("embed", "embed_rows", src=src)
+        self.steps.append(self._embed_step)
+        self.steps.append(Step("similar", "similar", src="features"))
+
+    def _on_device(self, t: torch.Tensor) -> bool:
+        d = self.device
+        return t.device.type == d.type and (d.index is None or t.device.index == d.index)
+
+    def feature_slot(self, slot: int = 0) -> torch.Tensor:
+        """fp32 query rows [max_batch, F] of the last forward of a ``similar`` engine in ``slot``."""
+        while len(self.feature_slots) <= slot:
+            self.feature_slots.append(torch.zeros_like(self.feature_slots[0]))
+        return self.feature_slots[slot]
+
+    def _similar_workspace(self, slot: int) -> torch.Tensor:
+        while len(self._similar_work) <= slot:
+            n = _lib.lib().gallery_topk_workspace(self.max_batch, self.similar.gallery.shape[0], self.similar_k)
+            self._similar_work.append(torch.zeros(n, dtype=torch.uint8, device=self.device))
+        return self._similar_work[slot]
+
+    def _emit_similar(self, prog, step: Step, b: int) -> None:
+        g, feat = self.similar.gallery, self.feature_slot(self._slot)
+        out = self.outputs[self._slot] if self.outputs else self.logits
+        prog.add_gallery_topk(step.name, dict(q=_lib.ptr(feat), g=_lib.ptr(g), out=_lib.ptr(out),
+                                              work=_lib.ptr(self._similar_workspace(self._slot)), B=b,
+                                              N=g.shape[0], F=feat.shape[1], K=self.similar_k,
+                                              ldq=feat.shape[1], ldg=g.shape[1]))
 
     def add_input_slots(self, n: int) -> list[torch.Tensor]:
         """Extra static input AND logits buffers, each slot with its own captured
@@ -252,6 +336,8 @@ class EngineBase:
                     self._emit_topk(prog, st, b)
                 elif st is self._embed_step:
                     self._emit_embed(prog, st, b)
+                elif st.kind == "similar":
+                    self._emit_similar(prog, st, b)
                 else:
                     self._emit(prog, st, b)
 
@@ -273,8 +359,8 @@ class EngineBase:
     @torch.no_grad()
     def forward(self, x: torch.Tensor, capture: bool = True) -> torch.Tensor:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
-        (a ``topk`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed`` engine: the
-        fp32 feature rows [n, F])."""
+        (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
+        engine: the fp32 feature rows [n, F])."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

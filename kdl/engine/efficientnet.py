@@ -53,8 +53,8 @@ class EfficientNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
-                 topk: int = 0, embed: str = ""):
-        super().__init__(device, max_batch, buckets, topk, embed)
+                 topk: int = 0, embed: str = "", similar=None):
+        super().__init__(device, max_batch, buckets, topk, embed, similar)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()
@@ -63,6 +63,7 @@ class EfficientNetEngine(EngineBase):
         self._alloc()
         self._enable_topk()
         self._enable_embed()
+        self._enable_similar()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

@@ -46,10 +46,10 @@ class ResNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
-                 dtype: str = "fp16", topk: int = 0, embed: str = ""):
+                 dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
-        super().__init__(device, max_batch, buckets, topk, embed)
+        super().__init__(device, max_batch, buckets, topk, embed, similar)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind
@@ -62,6 +62,7 @@ class ResNetEngine(EngineBase):
         self._alloc()
         self._enable_topk()
         self._enable_embed()
+        self._enable_similar()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

@@ -45,8 +45,8 @@ class ViTEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
-                 topk: int = 0, embed: str = ""):
-        super().__init__(device, max_batch, buckets, topk, embed)
+                 topk: int = 0, embed: str = "", similar=None):
+        super().__init__(device, max_batch, buckets, topk, embed, similar)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"
@@ -63,6 +63,7 @@ class ViTEngine(EngineBase):
         self._alloc()
         self._enable_topk()
         self._enable_embed()
+        self._enable_similar()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

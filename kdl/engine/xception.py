@@ -44,8 +44,8 @@ class XceptionEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
-                 tune_file: str | Path | None = None, topk: int = 0, embed: str = ""):
-        super().__init__(device, max_batch, buckets, topk, embed)
+                 tune_file: str | Path | None = None, topk: int = 0, embed: str = "", similar=None):
+        super().__init__(device, max_batch, buckets, topk, embed, similar)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
@@ -68,6 +68,7 @@ class XceptionEngine(EngineBase):
         self._alloc()
         self._enable_topk()
         self._enable_embed()
+        self._enable_similar()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

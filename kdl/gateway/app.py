@@ -3,6 +3,8 @@
 top-K classes and softmax scores, its label strings: the classify signature of the mode);
 ``POST /embed {"url": ...}`` -> ``{"embedding": [...]}`` (the pooled feature vector in front of the
 model's head: the embed signature of the mode).
+``POST /similar {"url": ...}`` -> ``{"neighbors": [{"id": ..., "score": ...}, ...]}`` (the nearest items
+of the model version's gallery, nearest first: the similar signature of the mode).
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -36,7 +38,7 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_embed_response, process_response)
+                     process_embed_response, process_response, process_similar_response)
 
 
 class GatewayConfig:
@@ -132,6 +134,8 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         cfg.mode, ("classify", "images"))
     embed_sig = {"bytes": ("embed_bytes", "image_bytes"), "raw": ("embed_image", "images")}.get(
         cfg.mode, ("embed", "images"))
+    similar_sig = {"bytes": ("similar_bytes", "image_bytes"), "raw": ("similar_image", "images")}.get(
+        cfg.mode, ("similar", "images"))
 
     def uint8_input(img):
         if cfg.mode == "bytes":
@@ -173,6 +177,22 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except grpc.RpcError as e:
             return grpc_fail(e)
         return jsonify({"embedding": process_embed_response(pb_result)[0]})
+
+    @app.route("/similar", methods=["POST"])
+    def similar():
+        body = request.get_json(silent=True)
+        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
+            return fail(400, 'request body must be JSON {"url": "<image url>"}')
+        try:
+            img = load(body["url"])
+        except LookupError as e:
+            return fail(502, str(e))
+        try:
+            req = make_request(uint8_input(img), cfg.model_name, similar_sig[0], similar_sig[1])
+            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
+        except grpc.RpcError as e:
+            return grpc_fail(e)
+        return jsonify({"neighbors": process_similar_response(pb_result)[0]})
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

@@ -74,6 +74,16 @@ def process_classify_response(pb_result) -> list[list[dict]]:
             for i in range(n)]
 
 
+def process_similar_response(pb_result) -> list[list[dict]]:
+    """A similar signature's PredictResponse (``ids`` DT_STRING [n, K], ``scores`` DT_FLOAT [n, K])
+    -> per image, K ``{"id", "score"}`` entries, nearest first."""
+    ids, sc = pb_result.outputs["ids"], pb_result.outputs["scores"]
+    n, k = [d.size for d in sc.tensor_shape.dim]
+    names = [v.decode() for v in ids.string_val]
+    return [[{"id": names[i * k + j], "score": float(sc.float_val[i * k + j])} for j in range(k)]
+            for i in range(n)]
+
+
 def process_embed_response(pb_result) -> list[list[float]]:
     """An embed signature's PredictResponse (``embedding`` DT_FLOAT [n, F]) -> per image, its F floats."""
     t = pb_result.outputs["embedding"]

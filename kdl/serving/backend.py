@@ -70,10 +70,12 @@ class SignatureInfo:
     method_name: str = "tensorflow/serving/predict"
     input_shape: tuple = (-1, IMG, IMG, 3)
     output_shape: tuple = (-1, 10)
-    # classify signatures (serving/classify.py): every output as (key, dtype, shape), and K;
-    # empty / 0 for the signatures whose single output is the fp32 logits
+    # classify and similar signatures (serving/classify.py, serving/similar.py): every output as
+    # (key, dtype, shape), and K; empty / 0 for the signatures whose single output is the fp32 logits
     outputs: tuple = ()
     top_k: int = 0
+    # similar signatures: the K packed indices are gallery rows (ids), the scores their dot products
+    similar: bool = False
     # embed signatures (serving/embed.py): "raw" / "l2" = the single output is the pooled feature
     # vector in front of the head, [-1, F] fp32; "" for every other signature
     embed: str = ""
@@ -101,6 +103,14 @@ class ModelSource:
     # embedding outputs (serving/embed.py): "none" | "l2", and F
     embed_normalize: str = "none"
     embed_dim: int = 0
+    # gallery search (serving/similar.py): the stored bf16 patterns [N, F] (None = no gallery and no
+    # similar signatures), an id per row, K, the metric, and the device copies (one per device)
+    gallery: np.ndarray | None = None
+    gallery_ids: list = field(default_factory=list)
+    similar_k: int = 0
+    similar_metric: str = "cosine"
+    gallery_device: dict = field(default_factory=dict)
+    gallery_lock: object = field(default_factory=threading.Lock)
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -120,12 +130,15 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 
 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
-                     classify_top_k: int | None = None, embedding_normalize: str | None = None) -> ModelSource:
+                     classify_top_k: int | None = None, embedding_normalize: str | None = None,
+                     similar_top_k: int | None = None, gallery: bool = True) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
     (the server's --classify_top_k) overrides the version's classify K (serving/classify.py),
-    ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py)."""
+    ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py),
+    ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py);
+    ``gallery=False`` leaves the version's gallery files alone (the tool that writes them)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -141,6 +154,9 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     add_signatures(src, path, classify_top_k)
     from .embed import add_signatures as add_embed_signatures
     add_embed_signatures(src, path, embedding_normalize)
+    if gallery:
+        from .similar import add_signatures as add_similar_signatures
+        add_similar_signatures(src, path, similar_top_k)
     return src
 
 
@@ -401,6 +417,10 @@ class GPUExecutor(_Executor):
         tk = dict(topk=r.topk) if r.topk else {}               # the classify runner: rows of 2K words
         if r.embed:
             tk = dict(embed=r.embed)                           # the embed runner: rows of F floats
+        if r.similar:                                          # the similar runner: rows of 2K words
+            from ..engine.base import Similar
+            from .similar import device_gallery
+            tk = dict(similar=Similar(device_gallery(src, dev), r.similar_k, src.similar_metric))
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -658,10 +678,14 @@ class SignatureRunner:
     topk = 0            # K: the GPU engines end in the top-k step and rows are 2K words (ClassifyRunner)
     embed = ""          # "raw" / "l2": the engines end in the embed step and rows are F floats (EmbedRunner)
     embed_dim = 0
+    similar = False     # the engines end in the similar step and rows are 2K words (SimilarRunner)
+    similar_k = 0
 
     @property
     def out_cols(self) -> int:
         """32-bit words per result row, from the executor to the waiting handler."""
+        if self.similar:
+            return 2 * self.similar_k
         if self.embed:
             return self.embed_dim
         return 2 * self.topk if self.topk else self.source.classes
@@ -800,6 +824,30 @@ class EmbedRunner(SignatureRunner):
         super().__init__(sig, source, cfg, devices)
 
 
+class SimilarRunner(SignatureRunner):
+    """The ``similar`` signature: like ``serving_uint8``'s runner, but a result row is the packed
+    K nearest gallery rows (K int32 row indices, K fp32 scores: classify.unpack_rows). GPU executors
+    build their engines with ``similar=`` over the version's one device gallery, so the rows come
+    out of the captured program; the CPU and null executors return feature rows as an embed
+    runner's do, and ``similar_rule`` is applied here in numpy."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.k = sig.top_k
+        if devices:
+            self.similar, self.similar_k = True, self.k
+        else:
+            self.embed, self.embed_dim = "raw", source.gallery.shape[1]
+        super().__init__(sig, source, cfg, devices)
+
+    def _run(self, n: int, submit) -> np.ndarray:
+        from .classify import pack_rows
+        from .similar import similar_rule
+        rows = super()._run(n, submit)
+        if self.similar:
+            return rows
+        return pack_rows(*similar_rule(rows, self.source.gallery, self.k, self.source.similar_metric))
+
+
 class Servable:
     """One loaded model version (all its signatures)."""
 
@@ -830,7 +878,16 @@ class Servable:
                                        "in signature def")
                 from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
                 from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
-                if sig_name == EMBED_SIGNATURE:
+                from .similar import SIMILAR_BYTES_SIGNATURE, SIMILAR_IMAGE_SIGNATURE, SIMILAR_SIGNATURE
+                if sig_name == SIMILAR_SIGNATURE:
+                    r = SimilarRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == SIMILAR_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(SIMILAR_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == SIMILAR_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(SIMILAR_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == EMBED_SIGNATURE:
                     r = EmbedRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 elif sig_name == EMBED_IMAGE_SIGNATURE:
                     r = ImageRunner(self.signatures[sig_name], self.runner(EMBED_SIGNATURE), self._devices,
@@ -868,7 +925,7 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # a wrapper (serving_image / serving_bytes, the classify_* and embed_* pairs) has no batcher
+        # a wrapper (serving_image / serving_bytes, the classify_*, embed_* and similar_* pairs) has no batcher
         # of its own: it feeds its inner runner's, so that is where its work shows
         def batcher(r):
             return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)

@@ -95,6 +95,9 @@ class ServerConfig:
     # normalisation of the embed signatures (serving/embed.py): "none" | "l2"; None = the model
     # version's own "embedding": {"normalize": ...}, else none
     embedding_normalize: str | None = None
+    # K of the similar signatures (serving/similar.py); None = the model version's own
+    # "similar": {"top_k": K}, else 5. 1..32, clipped to the gallery's row count
+    similar_top_k: int | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -200,6 +203,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "are (Keras pooling=\"avg\"), l2 = each divided by its L2 norm; overrides the model version's "
                          "\"embedding\": {\"normalize\": ...} (env KDL_EMBEDDING_NORMALIZE, default: the version's, "
                          "else none)")
+    ap.add_argument("--similar_top_k", type=int, default=None,
+                    help="gallery items and scores per image of the similar / similar_image / similar_bytes "
+                         "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
+                         "\"similar\": {\"top_k\": K} (env KDL_SIMILAR_TOP_K, default: the version's, else 5)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -261,6 +268,8 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         classify_top_k=(a.classify_top_k if a.classify_top_k is not None
                                         else int(env["KDL_CLASSIFY_TOP_K"]) if env.get("KDL_CLASSIFY_TOP_K") else None),
                         embedding_normalize=a.embedding_normalize or env.get("KDL_EMBEDDING_NORMALIZE") or None,
+                        similar_top_k=(a.similar_top_k if a.similar_top_k is not None
+                                       else int(env["KDL_SIMILAR_TOP_K"]) if env.get("KDL_SIMILAR_TOP_K") else None),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

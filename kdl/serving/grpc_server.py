@@ -178,7 +178,7 @@ class Servicer:
             t1 = time.perf_counter()
             logits = runner.predict(buf, n, _deadline_us(context))
             t2 = time.perf_counter()
-            if sig.top_k:               # classify signatures: label strings + scores from the packed rows
+            if sig.top_k:               # classify / similar signatures: strings + scores from the packed rows
                 out = classify_response(s, sig, logits, req["output_filter"])
             else:
                 out = rt.build_predict_response([(sig.output_key, logits)], s.name, s.version, sig_name)
@@ -290,24 +290,31 @@ class Servicer:
 
 
 def classify_outputs(s, sig, rows) -> tuple[list[list[str]], np.ndarray]:
-    """Packed top-K rows of a classify signature -> (labels [n][K], scores fp32 [n, K])."""
+    """Packed top-K rows of a classify signature -> (labels [n][K], scores fp32 [n, K]); of a
+    similar signature -> (gallery ids [n][K], scores fp32 [n, K])."""
     classes, scores = unpack_rows(rows)
+    if sig.similar:
+        from .similar import ids_of
+        METRICS.inc("kdl_similar_total", signature=sig.name)
+        return ids_of(s.source, classes), scores
     METRICS.inc("kdl_classify_total", signature=sig.name)
     return labels_of(s.source, classes), scores
 
 
 def classify_response(s, sig, rows, output_filter) -> bytes:
     """PredictResponse of a classify signature: ``classes`` DT_STRING [n, K] and ``scores``
-    DT_FLOAT [n, K] (float_val), or the subset ``output_filter`` names."""
+    DT_FLOAT [n, K] (float_val), or the subset ``output_filter`` names. A similar signature's
+    strings are gallery ids under ``ids``."""
     labels, scores = classify_outputs(s, sig, rows)
+    names = sig.output_key                      # "classes" | "ids"
     n, k = scores.shape
     resp = P.PredictResponse()
     resp.model_spec.name = s.name
     resp.model_spec.version.value = s.version
     resp.model_spec.signature_name = sig.name
-    want = list(output_filter) or ["classes", "scores"]
-    if "classes" in want:
-        t = resp.outputs["classes"]
+    want = list(output_filter) or [names, "scores"]
+    if names in want:
+        t = resp.outputs[names]
         t.dtype = P.DT_STRING
         t.string_val.extend(name.encode() for row in labels for name in row)
     if "scores" in want:

@@ -38,7 +38,8 @@ def latest_version_source(cfg: ServerConfig):
     if not versions:
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
     return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess,
-                            classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize)
+                            classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize,
+                            similar_top_k=cfg.similar_top_k)
 
 
 class ModelManager:
@@ -76,7 +77,8 @@ class ModelManager:
         try:
             src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess,
                                    classify_top_k=self.cfg.classify_top_k,
-                                   embedding_normalize=self.cfg.embedding_normalize)
+                                   embedding_normalize=self.cfg.embedding_normalize,
+                                   similar_top_k=self.cfg.similar_top_k)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

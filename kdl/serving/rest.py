@@ -152,9 +152,10 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
             if not sig.top_k:
                 return {"predictions": out.tolist()} if rows else {"outputs": out.tolist()}
             labels, scores = classify_outputs(s, sig, out)
+            names = sig.output_key              # "classes", or a similar signature's "ids"
             if rows:
-                return {"predictions": [{"classes": c, "scores": v} for c, v in zip(labels, scores.tolist())]}
-            return {"outputs": {"classes": labels, "scores": scores.tolist()}}
+                return {"predictions": [{names: c, "scores": v} for c, v in zip(labels, scores.tolist())]}
+            return {"outputs": {names: labels, "scores": scores.tolist()}}
 
         def _classify(self, m):
             t0 = time.perf_counter()
