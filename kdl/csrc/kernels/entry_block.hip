@@ -24,7 +24,11 @@
 // only activations from LDS. The depthwise convs run on the VALU (v_dot2c_f32_bf16 over tap
 // pairs, fp32 accumulate), each lane producing the 8 channels of one pixel = exactly its MFMA
 // operand fragment, written fragment-linear to an LDS A buffer. Phases per step, separated by
-// workgroup barriers: dw1 -> GEMM1 (+ residual GEMM) -> dw2 -> GEMM2 + pool.
+// workgroup barriers: dw1 -> GEMM1 (+ residual GEMM) -> dw2 -> GEMM2 + pool (five barriers with B0).
+// TWOPH (config 21, block3's default): the same step skewed by one stage, TWO barriers per step --
+// a DW phase (dw2 of step i, dw1 + residual GEMM of step i+1) and a GEMM phase (GEMM2 + pool + output
+// of step i, GEMM1 of step i+1, the x-row DMA of step i+2 in flight); A1 and A2 are separate buffers,
+// the horizontal pool exchanges lanes (ds_bpermute) instead of LDS rows, no register is spilled.
 //
 // LDS activation images are channel-PLANE major (16-byte slot = 8 channels of one pixel, a
 // plane = one 8-channel chunk of a row, pitch PLP px, a multiple of 16): a depthwise / MFMA
@@ -56,7 +60,7 @@ struct EbStepRegs {
 };
 static_assert(EB_MAX_STEPS <= 128, "EbStepRegs holds two words per lane");
 
-template <int C0, int C1, int PC, int NFW, bool DWM = false>
+template <int C0, int C1, int PC, int NFW, bool DWM = false, bool TWOPH = false>
 struct EbGeom {
   static constexpr int Y2C = 2 * PC + 1;            // y2 columns a strip needs
   static constexpr int Y1C = Y2C + 2;               // y1 columns
@@ -71,17 +75,21 @@ struct EbGeom {
   static constexpr int Y2F = 2 * Y2FR;
   static constexpr int NW = C1 / (16 * NFW);        // waves (NFW 16-channel output slices each)
   static constexpr int XDMA = XROW / 1024;          // 1 KiB DMA instructions per x row
-  static constexpr int ABYTES = (KT0 * Y1F > KT1 * Y2F ? KT0 * Y1F : KT1 * Y2F) * 1024;
+  static constexpr int A1BYTES = KT0 * Y1F * 1024, A2BYTES = KT1 * Y2F * 1024;
+  static constexpr int ABYTES = TWOPH ? A1BYTES + A2BYTES : (A1BYTES > A2BYTES ? A1BYTES : A2BYTES);
   static constexpr int PCOLS = 16 * Y2FR;           // pool row columns
   static constexpr int DWQ = DWM ? 1024 : 640;      // LDS depthwise entries per k-step: 4 lane groups x 40 words
                                                     // (VALU), or pack_dw_entries' 1 KiB (MFMA variant)
   // LDS map: the two depthwise A buffers alias (A1 is read before the barrier that precedes
-  // A2's writes, A2 before the next step's first barrier)
+  // A2's writes, A2 before the next step's first barrier). TWOPH: both are live in one barrier
+  // interval (A2 at OFF_A, A1 behind it); the room comes from the pool rows, which that schedule
+  // exchanges between lanes instead (ds_bpermute)
   static constexpr int OFF_X = 0;
   static constexpr int OFF_Y1 = OFF_X + 4 * XROW;
   static constexpr int OFF_A = OFF_Y1 + 4 * Y1ROW;
+  static constexpr int OFF_A1 = OFF_A + A2BYTES;    // TWOPH only
   static constexpr int OFF_P = OFF_A + ABYTES;      // per-wave pool rows [NW][PCOLS][16*NFW] bf16
-  static constexpr int OFF_DW = OFF_P + NW * PCOLS * 16 * NFW * 2;
+  static constexpr int OFF_DW = OFF_P + (TWOPH ? 0 : NW * PCOLS * 16 * NFW * 2);
   static constexpr int OFF_B = OFF_DW + (KT0 + KT1) * DWQ;   // biases [3][C1] fp32
   static constexpr int OFF_S = OFF_B + 3 * C1 * 4;  // this workgroup's step table, one packed word per step
   static constexpr int BYTES = OFF_S + 4 * EB_MAX_STEPS;
@@ -127,6 +135,46 @@ __device__ __forceinline__ s16x8 eb_dw8(Tap tap, const uint32_t* wq) {
 #pragma unroll
   for (int d = 0; d < 4; ++d) o[d] = pack_bf16(acc[2 * d], acc[2 * d + 1]);
   return __builtin_bit_cast(s16x8, o);
+}
+
+// eb_dw8 for N units of one wave that share their weights (same k-step, same lane group): every
+// tap pair's 8 weight words are read once for the N units, not once per unit, and no store sits
+// between the units, so taps that two units share (tap(u, ti) with the same address: the two rows
+// of a row pair share 6 of their 9) are read once as well. Per unit the operands and the order of
+// the fp32 sums are eb_dw8's: bit-identical to it.
+template <bool RELU, int N, class Tap>
+__device__ __forceinline__ void eb_dw8_n(Tap tap, const uint32_t* wq, s16x8 (&out)[N]) {
+  float acc[N][8];
+#pragma unroll
+  for (int u = 0; u < N; ++u)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[u][e] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const u32x4 w0 = *(const u32x4*)(wq + 8 * j), w1 = *(const u32x4*)(wq + 8 * j + 4);
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      u32x4 a = tap(u, 2 * j);
+      u32x4 b = j < 4 ? tap(u, 2 * j + 1) : (u32x4){0u, 0u, 0u, 0u};
+      if constexpr (RELU) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) { a[d] = relu_bf16x2(a[d]); b[d] = relu_bf16x2(b[d]); }
+      }
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const uint32_t wl = d < 2 ? w0[2 * d] : w1[2 * d - 4], wh = d < 2 ? w0[2 * d + 1] : w1[2 * d - 3];
+        acc[u][2 * d] = eb_dot(eb_lo(a[d], b[d]), wl, acc[u][2 * d]);
+        acc[u][2 * d + 1] = eb_dot(eb_hi(a[d], b[d]), wh, acc[u][2 * d + 1]);
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    u32x4 o;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = pack_bf16(acc[u][2 * d], acc[u][2 * d + 1]);
+    out[u] = __builtin_bit_cast(s16x8, o);
+  }
 }
 
 // depthwise 3x3 of a 16-pixel x 32-channel unit on the MATRIX cores (the block-diagonal operand of
@@ -241,9 +289,10 @@ __device__ __forceinline__ s16x8 eb_frag(const uint16_t* wp, int nf, int kt, int
   return *(const s16x8*)(wp + ((long)(nf * kt + t) * 64 + lane) * 8);
 }
 
-template <int C0, int C1, int PC, int NFW, int PT, bool RELU1, bool STAMP = false, bool DWM = false, int OCC = 1>
+template <int C0, int C1, int PC, int NFW, int PT, bool RELU1, bool STAMP = false, bool DWM = false, int OCC = 1,
+          bool TWOPH = false>
 __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void entry_block_kernel(EntryBlockArgs a) {
-  using G = EbGeom<C0, C1, PC, NFW, DWM>;
+  using G = EbGeom<C0, C1, PC, NFW, DWM, TWOPH>;
   constexpr int NW = G::NW, KT0 = G::KT0, KT1 = G::KT1;
   constexpr int PLB = G::PLB, XROW = G::XROW, Y1ROW = G::Y1ROW;
   constexpr int Y1C = G::Y1C, Y2C = G::Y2C, XC = G::XC, PLP = G::PLP;
@@ -393,6 +442,228 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
   __syncthreads();                                   // step table, weights, biases in LDS
   if constexpr (REG_STEPS) str.load(stl, s1 - s0, lane);
   dma_for(s0);
+  if constexpr (TWOPH) {
+    // ---- two-phase schedule (config 21): the step skewed by one stage, two barriers per step.
+    // Iteration `it` runs the second half of step it next to the first half of step it + 1:
+    //   DW phase    dw2(it): y1 ring -> A2         dw1(it + 1): x ring -> A1, + its residual 1x1/2 GEMM
+    //   barrier A   then the x-row DMA of step it + 2 and the deferred output store of step it - 1
+    //   GEMM phase  GEMM2(it) + pool + output      GEMM1(it + 1): A1 -> y1 ring
+    //   barrier B   (= B0: vmcnt(0) for the landed x rows)
+    // The first iteration (it = s0 - 1) has only the (it + 1) half, the last only the (it) half; the
+    // halves are predicated, every wave runs both barriers of every iteration. Operands, dot orders
+    // and rounding points are the four-phase loop's: the output is bit-identical to it.
+    // y1 ring slots are counted by steps: step j writes its rows R+2, R+3 into pair j & 1 and reads
+    // R, R+1 from the other pair (its predecessor's), so the rows of two runs walked back to back
+    // never meet in a slot whatever their row numbers are.
+    static_assert(!DWM && !WIDE && PT == 0 && Y2FR == 2 && U1 % NW == 0 && NW == KT1,
+                  "two-phase schedule: block3's VALU-depthwise, two-slice build (a wave's dw2 units: one k-step)");
+    uint8_t* const A2 = Ab;
+    uint8_t* const A1 = smem + G::OFF_A1;
+    auto word = [&](int q) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)stl[q - s0]); };
+    auto yslot = [](int j, int o) { return 2 * ((j + (o >> 1) + 1) & 1) + (o & 1); };   // row R + o of step j
+    // every part of an iteration derives its per-lane addresses from an opaque copy of the lane index:
+    // as loop invariants they are hoisted out of the loop by the dozen and kept in scratch, and a
+    // scratch reload in the GEMM phase waits, in vmcnt order, for the x-row DMA issued ahead of it
+    auto fresh = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
+    // residual carry: dw1 runs a step early, so the residual of pooled row k + 1 (read with x row
+    // 2k + 2 in the ring) is two iterations ahead of its output. fp32, never rounded.
+    f32x4 res0[NFW], res1[NFW], res2[NFW];           // of the output of step it / it + 1 / it + 2
+#pragma unroll
+    for (int n = 0; n < NFW; ++n) res0[n] = res1[n] = res2[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                 // the first step's x rows landed
+    for (int it = s0 - 1; it < s1; ++it) {
+      const bool hn = it + 1 < s1;                   // uniform (SGPR) predicates of the two halves
+      const uint32_t ec = it >= s0 ? word(it) : 0u, en = hn ? word(it + 1) : 0u;
+      const int mc = (ec >> 23) & 3, mn = (en >> 23) & 3;   // mc 0: nothing to do for step it
+      const int b = ec & 255, pc0 = (int)((ec >> 8) & 63) * PC, k = (int)((ec >> 14) & 511) - 2;
+      const int pcn = (int)((en >> 8) & 63) * PC, Rn = 2 * ((int)((en >> 14) & 511) - 2);
+      const int R = 2 * k;
+      if (it >= s0) stamp(it, 0);
+      // ---- DW phase. dw2(it) -> A2 (y2 rows R+1, R+2: fragments [row][col / 16])
+      if (mc >= 1) {
+        const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
+        // a wave's four units are the two rows of both column fragments at its k-step: per fragment a
+        // row pair (eb_dw8_n: 12 distinct tap reads for the two rows), all four stored after the last read
+        const uint32_t* wq = dwl + ((KT0 + t2) * 4 + q16) * 40;
+        s16x8 o2[Y2FR][2];
+#pragma unroll
+        for (int fc = 0; fc < Y2FR; ++fc) {
+          const uint8_t* base = y1r + (4 * t2 + q16) * PLB + (fc * 16 + p16) * 16;
+          auto tap = [&](int rr, int ti) {           // y2 row R+1+rr reads y1 rows R+rr .. R+rr+2
+            return *(const u32x4*)(base + yslot(it, rr + ti / 3) * Y1ROW + (ti % 3) * 16);
+          };
+          eb_dw8_n<false, 2>(tap, wq, o2[fc]);
+        }
+#pragma unroll
+        for (int fc = 0; fc < Y2FR; ++fc)
+#pragma unroll
+          for (int rr = 0; rr < 2; ++rr) *(s16x8*)(A2 + (t2 * Y2F + rr * Y2FR + fc) * 1024 + lane * 16) = o2[fc][rr];
+      }
+      // dw1(it + 1) -> A1 (y1 rows Rn+2, Rn+3) and the residual of pooled row kn + 1 (x row Rn+2)
+      if (hn) {
+        const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
+        const uint32_t* wq = dwl + (t1 * 4 + q16) * 40;
+        const uint8_t* base[U1W];
+        int row[U1W];
+#pragma unroll
+        for (int i = 0; i < U1W; ++i) {
+          int pi = 16 * ((w + NW * i) / KT0) + p16;
+          pi = pi < 2 * Y1C ? pi : 2 * Y1C - 1;
+          const int rr = pi >= Y1C, col = pi - rr * Y1C;
+          row[i] = Rn + 2 + rr;
+          base[i] = xr + (4 * t1 + q16) * PLB + col * 16;
+        }
+        auto tap = [&](int i, int ti) {
+          return *(const u32x4*)(base[i] + ((row[i] - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
+        };
+        s16x8 o1[U1W];
+        eb_dw8_n<RELU1, U1W>(tap, wq, o1);
+#pragma unroll
+        for (int i = 0; i < U1W; ++i) *(s16x8*)(A1 + (t1 * Y1F + (w + NW * i) / KT0) * 1024 + lane * 16) = o1[i];
+        if (mn >= 1) {
+          // the residual weights are fetched here, every step (8 KiB per wave, L2-resident; nothing else is
+          // in flight: barrier B drained vmcnt), and live only for the eight MFMAs below. As residents (32
+          // VGPRs) they pushed the allocation into scratch, and so did fetching them any earlier in the
+          // phase (the allocator parked them in scratch across the depthwise); a scratch reload in the
+          // GEMM phase waits, in vmcnt order, for the x-row DMA issued ahead of it
+          s16x8 wrs[NFW][KT0];
+#pragma unroll
+          for (int n = 0; n < NFW; ++n)
+#pragma unroll
+            for (int t = 0; t < KT0; ++t) wrs[n][t] = eb_frag(a.wr, NFW * w + n, KT0, t, lane);
+          const int xrow = Rn + 2, xcol = 2 * p16 + 2;
+#pragma unroll
+          for (int n = 0; n < NFW; ++n) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT0; ++t)
+              acc = mfma16(wrs[n][t], *(const s16x8*)(xr + (xrow & 3) * XROW + (4 * t + q16) * PLB + xcol * 16), acc);
+            res2[n] = acc;
+          }
+        }
+      }
+      eb_lds_barrier();                              // A: A1, A2 complete; y1 pair (it + 1) & 1 and the x ring free
+      if (it >= s0) stamp(it, 1);
+      if (it + 2 < s1) dma_for(it + 2);
+      // ---- GEMM phase. GEMM2(it) + bias -> bf16; vertical max with the carried row; horizontal max
+      if (mc >= 1) {
+        const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
+        const bool r0ok = (unsigned)R < (unsigned)H && mc == 2, r1ok = (unsigned)(R + 1) < (unsigned)H;
+        const bool r2ok = (unsigned)(R + 2) < (unsigned)H;
+        float4 bz1[NFW];
+#pragma unroll
+        for (int n = 0; n < NFW; ++n) bz1[n] = bias(1, n);
+        u32x2 pv[NFW][Y2FR];                         // vertical maxima: lane (p16, q16) = column 16 fc + p16
+#pragma unroll
+        for (int fc = 0; fc < Y2FR; ++fc) {
+          const s16x8* a0 = (const s16x8*)(A2 + fc * 1024 + lane * 16);
+          const s16x8* a1 = (const s16x8*)(A2 + (Y2FR + fc) * 1024 + lane * 16);
+          const int col = fc * 16 + p16, gcol = 2 * pc0 + col;
+          const bool cok = col < Y2C && (unsigned)gcol < (unsigned)W;
+#pragma unroll
+          for (int n = 0; n < NFW; ++n) {
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT1; ++t) {
+              acc0 = mfma16(w2[n][t], a0[t * Y2F * 64], acc0);
+              acc1 = mfma16(w2[n][t], a1[t * Y2F * 64], acc1);
+            }
+            float vm[4];
+            const float4 b4 = bz1[n];
+            const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+            // bf16 rounding: the values an unfused separable conv would have stored
+            const u32x2 y2a = {pack_bf16(acc0[0] + bb[0], acc0[1] + bb[1]), pack_bf16(acc0[2] + bb[2], acc0[3] + bb[3])};
+            const u32x2 y2b = {pack_bf16(acc1[0] + bb[0], acc1[1] + bb[1]), pack_bf16(acc1[2] + bb[2], acc1[3] + bb[3])};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const uint32_t dc = carry[n][fc][e >> 1], da = y2a[e >> 1], db = y2b[e >> 1];
+              const float c0 = (e & 1) ? bf_hi(dc) : bf_lo(dc);
+              const float v1 = (e & 1) ? bf_hi(da) : bf_lo(da), v2 = (e & 1) ? bf_hi(db) : bf_lo(db);
+              float m = r0ok ? c0 : -INFINITY;
+              if (r1ok) m = fmaxf(m, v1);
+              if (r2ok) m = fmaxf(m, v2);
+              vm[e] = cok ? m : -INFINITY;
+            }
+            carry[n][fc] = y2b;
+            pv[n][fc] = (u32x2){pack_bf16(vm[0], vm[1]), pack_bf16(vm[2], vm[3])};   // bf16: lossless here
+          }
+        }
+        if (mc == 2) {
+          // horizontal 3/2 max: pooled column j takes y2 local cols 2j .. 2j+2 of this wave's own two
+          // fragments from lanes (col & 15, q16), every lane active (uniform branch): no LDS rows
+          const int j = p16, gj = pc0 + j;
+          u32x2 cc[NFW][3];
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+            const int c = 2 * j + d, src = ((lane & 48) | (c & 15)) * 4;
+#pragma unroll
+            for (int n = 0; n < NFW; ++n)
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)pv[n][0][h]);
+                const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)pv[n][1][h]);
+                cc[n][d][h] = c >= 16 ? hi : lo;
+              }
+          }
+          if (j < PC && gj < a.OW) {
+            // stored at once: GEMM1(it + 1) follows, so the store has the rest of the phase to retire
+            // before barrier B's vmcnt(0) (the four-phase loop defers it past its next barrier)
+            uint16_t* const yp = a.y + (((long)b * a.OH + k) * a.OW + gj) * a.ldy + PCH * w + 4 * q16;
+#pragma unroll
+            for (int n = 0; n < NFW; ++n) {
+              const float4 brv = bias(2, n);
+              const float br4[4] = {brv.x, brv.y, brv.z, brv.w};
+              float o[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const uint32_t d0 = cc[n][0][e >> 1], d1 = cc[n][1][e >> 1], d2 = cc[n][2][e >> 1];
+                const float m = (e & 1) ? fmaxf(fmaxf(bf_hi(d0), bf_hi(d1)), bf_hi(d2))
+                                        : fmaxf(fmaxf(bf_lo(d0), bf_lo(d1)), bf_lo(d2));
+                o[e] = m + bf2f(f2bf(res0[n][e] + br4[e]));
+              }
+              *(u32x2*)(yp + 16 * n) = (u32x2){pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+            }
+          }
+        }
+      }
+      // GEMM1(it + 1) (+ bias, ReLU) -> y1 ring rows Rn+2, Rn+3 (pair (it + 1) & 1)
+      if (hn) {
+        const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
+        float4 bz0[NFW];
+#pragma unroll
+        for (int n = 0; n < NFW; ++n) bz0[n] = bias(0, n);
+#pragma unroll
+        for (int f = 0; f < Y1F; ++f) {
+          const s16x8* af = (const s16x8*)(A1 + f * 1024 + lane * 16);
+          const int pi = 16 * f + p16;
+          const int rr = pi >= Y1C, col = pi - rr * Y1C;
+          const int row = Rn + 2 + rr, gcol = 2 * pcn - 1 + col;
+          const bool ok = (unsigned)row < (unsigned)H && (unsigned)gcol < (unsigned)W;
+#pragma unroll
+          for (int n = 0; n < NFW; ++n) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT0; ++t) acc = mfma16(w1[n][t], af[t * Y1F * 64], acc);
+            if (pi < 2 * Y1C) {
+              const int c = PCH * w + 16 * n + 4 * q16;
+              const float4 bv = bz0[n];
+              const float v0 = fmaxf(acc[0] + bv.x, 0.f), v1 = fmaxf(acc[1] + bv.y, 0.f);
+              const float v2 = fmaxf(acc[2] + bv.z, 0.f), v3 = fmaxf(acc[3] + bv.w, 0.f);
+              const u32x2 o = ok ? (u32x2){pack_bf16(v0, v1), pack_bf16(v2, v3)} : (u32x2){0u, 0u};
+              *(u32x2*)(y1r + yslot(it + 1, 2 + rr) * Y1ROW + (c / 8) * PLB + col * 16 + (c & 7) * 2) = o;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int n = 0; n < NFW; ++n) { res0[n] = res1[n]; res1[n] = res2[n]; }
+      if (it >= s0) stamp(it, 2);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();                               // B: y1 rows written, A1 / A2 free, x rows of step it + 2 landed
+    }
+    return;
+  }
   for (int q = s0; q < s1; ++q) {
     int b, s, k, mode;
     decode(q, b, s, k, mode);
@@ -1161,6 +1432,13 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 // product sits in -- block outputs equal on small maps, bench logits off by 7.6e-3; 8 reads with
 // v_permlane32_swap: bit-identical, iteration 6,472: 24 swaps / selects + 16 copies per item cost more
 // than two reads), and block3 (VALU depthwise) was not changed: see the same file.
+// 21 / 121 (block3's default): config 1 on the two-phase schedule (TWOPH, see the loop's comment). Bit-identical
+// to config 1 (tests/test_entry_block3_twophase_gpu.py; the bench logits equal the parent build's). One lease
+// (profiles/entry_block3_twophase.txt): 185 -> 145 us per launch, step 23.4k -> 18.4k cycles (DW phase 8.0k,
+// GEMM phase 7.8k, barrier B 2.6k), 254 VGPRs and no spill against 256 with 26 spilled; bench +2.6 % in 8 of 8
+// interleaved pairs (A spread 1.4 %). The barriers were the smaller part: the same schedule with config 1's
+// resident residual weights and hoisted lane addresses spilled 37 VGPRs and ran 174 us, with the depthwise
+// reads shared on top 54 spilled and 221 us -- a scratch reload in the GEMM phase waits behind the x-row DMA.
 #define KDL_EBW_CONFIGS(X) \
   X(13, 64, 128, 13, 16, 8, 1, false, 0, false) \
   X(15, 64, 128, 13, 16, 8, 1, false, 1, false) \
@@ -1172,21 +1450,23 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   X(119, 64, 128, 13, 16, 8, 1, false, 1, true)
 
 #define KDL_EB_CONFIGS(X)                          \
-  X(0, 64, 128, 15, 1, 1, false, false, 1)         \
-  X(1, 128, 256, 13, 2, 0, true, false, 1)         \
-  X(2, 64, 128, 15, 1, 1, false, true, 1)          \
-  X(4, 64, 128, 13, 1, 1, false, false, 2)         \
-  X(5, 64, 128, 13, 1, 1, false, true, 2)          \
-  X(100, 64, 128, 15, 1, 1, false, false, 1)       \
-  X(101, 128, 256, 13, 2, 0, true, false, 1)       \
-  X(102, 64, 128, 15, 1, 1, false, true, 1)        \
-  X(104, 64, 128, 13, 1, 1, false, false, 2)       \
-  X(105, 64, 128, 13, 1, 1, false, true, 2)
+  X(0, 64, 128, 15, 1, 1, false, false, 1, false)  \
+  X(1, 128, 256, 13, 2, 0, true, false, 1, false)  \
+  X(2, 64, 128, 15, 1, 1, false, true, 1, false)   \
+  X(4, 64, 128, 13, 1, 1, false, false, 2, false)  \
+  X(5, 64, 128, 13, 1, 1, false, true, 2, false)   \
+  X(21, 128, 256, 13, 2, 0, true, false, 1, true)  \
+  X(100, 64, 128, 15, 1, 1, false, false, 1, false) \
+  X(101, 128, 256, 13, 2, 0, true, false, 1, false) \
+  X(102, 64, 128, 15, 1, 1, false, true, 1, false) \
+  X(104, 64, 128, 13, 1, 1, false, false, 2, false) \
+  X(105, 64, 128, 13, 1, 1, false, true, 2, false) \
+  X(121, 128, 256, 13, 2, 0, true, false, 1, true)
 
 int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds, int* occ) {
   switch (cfg) {
-#define KDL_EBINFO(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_) \
-  case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbGeom<c0_, c1_, pc_, nfw, dwm>::BYTES; *occ = occ_; return 0;
+#define KDL_EBINFO(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp) \
+  case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbGeom<c0_, c1_, pc_, nfw, dwm, tp>::BYTES; *occ = occ_; return 0;
     KDL_EB_CONFIGS(KDL_EBINFO)
 #undef KDL_EBINFO
 #define KDL_EBWINFO(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) \
@@ -1199,7 +1479,7 @@ int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds, int* occ) {
 
 static int eb_pad(int cfg) {
   switch (cfg) {
-#define KDL_EBPAD(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_) case id: return pt;
+#define KDL_EBPAD(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp) case id: return pt;
     KDL_EB_CONFIGS(KDL_EBPAD)
 #undef KDL_EBPAD
 #define KDL_EBWPAD(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) case id: return pt;
@@ -1217,10 +1497,10 @@ hipError_t entry_block(int cfg, const EntryBlockArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
   if (eb_pad(cfg) != (a.H % 2)) return hipErrorInvalidValue;   // TF 'same': leading pad 1 iff odd size
   switch (cfg) {
-#define KDL_EBCASE(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_)                                               \
-  case id:                                                                                                 \
-    hipLaunchKernelGGL((entry_block_kernel<c0_, c1_, pc_, nfw, pt, r_, (id >= 100), dwm, occ_>), dim3(a.grid), \
-                       dim3(64 * EbGeom<c0_, c1_, pc_, nfw, dwm>::NW), lds, s, a);                               \
+#define KDL_EBCASE(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp)                                                \
+  case id:                                                                                                      \
+    hipLaunchKernelGGL((entry_block_kernel<c0_, c1_, pc_, nfw, pt, r_, (id >= 100), dwm, occ_, tp>), dim3(a.grid), \
+                       dim3(64 * EbGeom<c0_, c1_, pc_, nfw, dwm, tp>::NW), lds, s, a);                             \
     break;
     KDL_EB_CONFIGS(KDL_EBCASE)
 #undef KDL_EBCASE

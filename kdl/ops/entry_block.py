@@ -30,6 +30,8 @@ def entry_block_config(cfg: int) -> tuple[int, int, int, int, int]:
 
 
 # kernel config per (block input channels, block output channels): entry_block.hip KDL_EB_CONFIGS
+# (the four-phase builds, any map parity they were built for; the engine's default for block3 is config 21,
+# the two-phase schedule of config 1: kdl/engine/xception.py KDL_ENTRY_BLOCK)
 CONFIGS = {(64, 128): 0, (128, 256): 1}
 
 

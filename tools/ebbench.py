@@ -23,7 +23,7 @@ def stamps(p, blocks, B, only=None):
         b = X.SPEC[blk - 1]
         s1, s2, r = XE._sep(p, b.main[0], "cuda"), XE._sep(p, b.main[1], "cuda"), XE._pw(p, b.res_conv, "cuda")
         H, C0 = geom[blk]
-        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1]      # 17 / 19: 13 / 15 with the row-pair depthwise
+        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1, 21]  # 17 / 19: 13 / 15 with the row-pair depthwise; 21: two-phase
         cfgs = [c for c in cfgs if only is None or c in only]
         for cfg in [c for b in cfgs for c in (b, 100 + b)]:
             eb = EntryBlock(f"block{blk}", s1, s2, r, cfg=cfg)
@@ -56,6 +56,22 @@ def stamps(p, blocks, B, only=None):
                         ph["iteration"].append(a1[0] - a0[0])
                         ph["consumers busy"].append(a0[1] - a0[0])
                         ph["producers busy"].append(a0[3] - a0[2])
+                print("  per iteration (= one step; median shader cycles, 8 workgroups):", flush=True)
+                for n, xs in ph.items():
+                    if xs:
+                        print(f"    {n:20s} {statistics.median(xs):8.0f}", flush=True)
+                continue
+            if cfg == 121:                       # two-phase: [iteration start, barrier A, end of the GEMM phase]
+                ph = {n: [] for n in ("DW phase", "GEMM phase", "vmcnt + barrier B", "iteration")}
+                for wg in range(8):
+                    for k in range(3, 62):
+                        a0, a1 = v[wg][k], v[wg][k + 1]
+                        if 0 in a0[:3] or a1[0] == 0:
+                            continue
+                        ph["DW phase"].append(a0[1] - a0[0])
+                        ph["GEMM phase"].append(a0[2] - a0[1])
+                        ph["vmcnt + barrier B"].append(a1[0] - a0[2])
+                        ph["iteration"].append(a1[0] - a0[0])
                 print("  per iteration (= one step; median shader cycles, 8 workgroups):", flush=True)
                 for n, xs in ph.items():
                     if xs:
