@@ -390,6 +390,15 @@ PYBIND11_MODULE(_C, m) {
     dwk_tiles(a, &cg, &rb, &tw, &nt);
     return py::make_tuple(cg, rb, tw, nt, dwk_seg(a));
   });
+  m.def("dwk_plan", [](py::dict d) {
+    const auto a = dwk_args(d);
+    DwkPlan p{};
+    chk(dwk_plan(a, &p), "dwk_plan");
+    py::dict r;
+    r["algo"] = p.algo; r["cb"] = p.cb; r["rb"] = p.rb; r["tw"] = p.tw; r["seg"] = p.seg; r["pd"] = p.pd;
+    r["ntiles"] = p.ntiles; r["lds"] = p.lds;
+    return r;
+  });
   m.def("squeeze_excite", [](py::dict d, uintptr_t s) {
     const auto a = se_args(d);
     py::gil_scoped_release nogil;

@@ -257,18 +257,26 @@ static int dwt_seg(const DwkArgs& a) {
   return a.S == 1 ? 5 : 3;
 }
 
-static hipError_t dwt(const DwkArgs& a, hipStream_t s) {
+static hipError_t dwt_plan(const DwkArgs& a, DwkPlan* p) {
   int CG, RB, TW, nt;
   dwt_tiles(a, &CG, &RB, &TW, &nt);
   // CG: a power of two <= 8 dividing C/8 (fixed chunk per thread; the pool reduction's
   // CG*8 channel sums fit the 64-float tail of the reduction buffer)
-  if ((CG & (CG - 1)) != 0 || CG > 8 || (a.C / 8) % CG != 0 || RB <= 0 || TW <= 0) return hipErrorInvalidValue;
+  if (CG <= 0 || (CG & (CG - 1)) != 0 || CG > 8 || (a.C / 8) % CG != 0 || RB <= 0 || TW <= 0) return hipErrorInvalidValue;
+  // before the size is computed: an absurd override must not wrap the product
+  if (RB > 4096 || TW > 4096) return hipErrorInvalidValue;
   const size_t smem = dwk_smem(a.K, a.S, CG, RB, TW);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
-  const long nblk = (long)a.B * nt;          // nt counts (row band, column tile, channel group)
-  if (nblk >= (1L << 31)) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)nblk), block(256);
   const int seg = dwt_seg(a);
+  if (seg != 3 && seg != 4 && seg != 5 && seg != 7 && seg != 8) return hipErrorInvalidValue;
+  *p = DwkPlan{1, CG, RB, TW, seg, 0, nt, (long)smem};   // nt counts (row band, column tile, channel group)
+  return hipSuccess;
+}
+
+static hipError_t dwt(const DwkArgs& a, const DwkPlan& p, hipStream_t s) {
+  const int CG = p.cb, RB = p.rb, TW = p.tw, seg = p.seg;
+  const size_t smem = (size_t)p.lds;
+  const dim3 grid((unsigned)((long)a.B * p.ntiles)), block(256);
 #define KDL_DWK(k, st, sg) \
   if (a.K == k && a.S == st && seg == sg) { \
     if (a.act == 2) hipLaunchKernelGGL((dwk_kernel<k, st, sg, true>), grid, block, smem, s, a, CG, RB, TW); \
@@ -514,16 +522,37 @@ int dwk_seg(const DwkArgs& a) {
   return dwt_seg(a);
 }
 
+hipError_t dwk_plan(const DwkArgs& a, DwkPlan* p) {
+  if (a.C <= 0 || a.C % 8 != 0 || a.B <= 0 || (a.K != 3 && a.K != 5) || (a.S != 1 && a.S != 2)) return hipErrorInvalidValue;
+  if (a.algo < 0 || a.algo > 2 || a.H <= 0 || a.W <= 0 || a.OH <= 0 || a.OW <= 0) return hipErrorInvalidValue;
+  // the kernels take the pad as given, so the output size must be the one it implies: a larger
+  // OH / OW would store rows and columns that no input feeds
+  if (a.pad < 0 || a.pad > a.K - 1 || a.H + 2 * a.pad < a.K || a.W + 2 * a.pad < a.K ||
+      a.OH != (a.H + 2 * a.pad - a.K) / a.S + 1 || a.OW != (a.W + 2 * a.pad - a.K) / a.S + 1)
+    return hipErrorInvalidValue;
+  if (a.pool != nullptr && a.Cs <= 0) return hipErrorInvalidValue;
+  if (dwk_algo(a) != 2) {
+    if (hipError_t e = dwt_plan(a, p); e != hipSuccess) return e;
+  } else {
+    int CB, RB, SEG, nt;
+    dwv_plan(a, &CB, &RB, &SEG, &nt);
+    const DwkTile* tb = dwk_lookup(a);
+    const int PDv = a.pd > 0 ? a.pd : (tb != nullptr && tb->algo == 2 && tb->tw > 0) ? tb->tw : 1;
+    bool cbok = false;
+    for (int c : {8, 16, 32, 64, 24, 36, 40, 48}) cbok = cbok || CB == c;
+    if (!cbok || RB <= 0 || (SEG != 2 && SEG != 4) || (PDv != 1 && PDv != 3)) return hipErrorInvalidValue;
+    *p = DwkPlan{2, CB, RB, 0, SEG, PDv, nt, (long)((256 * 4 + CB * 4) * sizeof(float))};
+  }
+  if ((long)a.B * p->ntiles >= (1L << 31)) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+
 hipError_t dwk(const DwkArgs& a, hipStream_t s) {
-  if (a.C % 8 != 0 || a.B <= 0 || (a.K != 3 && a.K != 5) || (a.S != 1 && a.S != 2)) return hipErrorInvalidValue;
-  if (dwk_algo(a) != 2) return dwt(a, s);
-  int CB, RB, SEG, nt;
-  dwv_plan(a, &CB, &RB, &SEG, &nt);
-  const DwkTile* tb = dwk_lookup(a);
-  const int PDv = a.pd > 0 ? a.pd : (tb != nullptr && tb->algo == 2 && tb->tw > 0) ? tb->tw : 1;
-  if (CB == 0 || RB <= 0 || (SEG != 2 && SEG != 4) || (PDv != 1 && PDv != 3)) return hipErrorInvalidValue;
-  const long nblk = (long)a.B * nt;
-  if (nblk >= (1L << 31)) return hipErrorInvalidValue;
+  DwkPlan p;
+  if (hipError_t e = dwk_plan(a, &p); e != hipSuccess) return e;
+  if (p.algo != 2) return dwt(a, p, s);
+  const int CB = p.cb, RB = p.rb, SEG = p.seg, PDv = p.pd;
+  const long nblk = (long)a.B * p.ntiles;
 #define KDL_DWV1(k, st, sg, cb, pd)                                                                     \
   if (a.K == k && a.S == st && SEG == sg && CB == cb && PDv == pd) {                                  \
     if (a.act == 2) hipLaunchKernelGGL((dwv_kernel<k, st, sg, cb, pd, true>), dim3((unsigned)nblk), dim3(256), 0, s, a, RB); \
@@ -591,8 +620,9 @@ __global__ __launch_bounds__(256) void se_kernel(SeArgs a) {
 }
 
 hipError_t squeeze_excite(const SeArgs& a, hipStream_t s) {
-  if (a.B <= 0 || a.Cs <= 0 || a.ntiles <= 0 || a.C <= 0 || a.B > 65535) return hipErrorInvalidValue;
+  if (a.B <= 0 || a.Cs <= 0 || a.ntiles <= 0 || a.C <= 0 || a.B > 65535 || a.HW <= 0) return hipErrorInvalidValue;
   const size_t smem = (size_t)(256 + a.Cs) * sizeof(float);
+  if (smem > 160 * 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(se_kernel, dim3(a.B, (a.C + 255) / 256), dim3(256), smem, s, a);
   return hipGetLastError();
 }

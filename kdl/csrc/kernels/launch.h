@@ -285,6 +285,17 @@ struct DwkArgs {
 hipError_t dwk(const DwkArgs& a, hipStream_t s);
 void dwk_tiles(const DwkArgs& a, int* cg, int* rb, int* tw, int* ntiles);
 int dwk_seg(const DwkArgs& a);
+// What dwk() would launch for these arguments, without launching: dwk() itself launches from
+// this plan, so the two cannot disagree. hipErrorInvalidValue where dwk() refuses.
+struct DwkPlan {
+  int algo;               // 1 LDS-tiled (dwk_kernel), 2 direct streaming (dwv_kernel)
+  int cb;                 // algo 1: CG, 8-channel chunks per workgroup; algo 2: CB, 4-channel chunk lanes
+  int rb, tw, seg;        // output rows per band, output columns per tile (algo 2: 0), columns per item
+  int pd;                 // algo 2: input rows prefetched ahead (algo 1: 0)
+  int ntiles;             // pool parts per image; the grid is B * ntiles workgroups
+  long lds;               // LDS bytes per workgroup
+};
+hipError_t dwk_plan(const DwkArgs& a, DwkPlan* p);
 
 // Squeeze-excite tail: scale[b][c] = sigmoid(W2 SiLU(sum_parts pool / HW + b1) + b2).
 struct SeArgs {
