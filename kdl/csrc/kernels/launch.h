@@ -134,7 +134,7 @@ struct StemArgs {
   const uint16_t* wp;     // packed [cout/16][K32][64][8], k = (ky*KW+kx)*3 + c
   const float* bias;      // [cout]
   uint16_t* y;            // [B*OH*OW][ldy]
-  int B, H, W, OH, OW, ldy;
+  int B, H, W, OH, OW, ldy;       // OH, OW at most (H + 2 pad - K) / stride + 1; ldy multiple of 8
   int in_kind;
   int KH, KW, stride, pad, cout;  // generic KxK stride/pad conv from 3 channels (cout = 32 or 64)
   float scale[3], shift[3];       // per-channel input normalisation applied on load (zero padding
@@ -341,7 +341,8 @@ struct HeadArgs {
   float* out;             // [B][NC]
   float* feat;            // scratch [B][F] fp32 (pooled features)
   float* hid;             // scratch [F/64][B][H1] fp32 (dense1 K-split partials)
-  int B, HW, ldx, F, H1, NC;
+  int B, HW, ldx, F, H1, NC;   // F multiple of 64, ldx >= F multiple of 8, H1 <= 128,
+                               // (H1 + H1*NC + 256) floats of LDS within 64 KB
 };
 hipError_t head_dense(const HeadArgs& a, hipStream_t s);
 

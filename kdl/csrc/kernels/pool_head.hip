@@ -313,8 +313,13 @@ hipError_t head_dense(const HeadArgs& a, hipStream_t s) {
   if (a.F % D1_K != 0 || a.ldx % 8 != 0 || a.B <= 0 || a.H1 <= 0 || a.H1 > 128 || a.NC <= 0 ||
       !a.hid)
     return hipErrorInvalidValue;
+  if (a.F <= 0 || a.ldx < a.F || a.HW <= 0) return hipErrorInvalidValue;
+  // dense2_kernel: hid [H1] + w2 [H1][NC] + the two half-sums [2][128], in the 64 KB a launch
+  // gets without opting in to more
+  const size_t lds2 = ((size_t)a.H1 + (size_t)a.H1 * a.NC + 256) * sizeof(float);
+  if (lds2 > 64 * 1024) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gap_dense1_kernel, dim3(a.F / D1_K, (a.B + 7) / 8), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(dense2_kernel, dim3(a.B), dim3(256), (size_t)(a.H1 + a.H1 * a.NC + 256) * sizeof(float), s, a);
+  hipLaunchKernelGGL(dense2_kernel, dim3(a.B), dim3(256), lds2, s, a);
   return hipGetLastError();
 }
 

@@ -281,6 +281,14 @@ static hipError_t launch_stem(const StemArgs& a, dim3 grid, hipStream_t s) {
 hipError_t stem_conv(const StemArgs& a, hipStream_t s) {
   const int M = a.B * a.OH * a.OW;
   if (M <= 0 || a.ldy < a.cout || a.KH <= 0 || a.KW <= 0 || a.stride <= 0) return hipErrorInvalidValue;
+  if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.OH <= 0 || a.OW <= 0) return hipErrorInvalidValue;
+  // the kernels store 16 bytes at a time; the weight layouts assume a square kernel
+  if (a.ldy % 8 != 0 || a.KH != a.KW || a.in_kind < 0 || a.in_kind > 1 || a.pad < 0) return hipErrorInvalidValue;
+  // the non-generic kernels check no bounds at all: the output map may be smaller than the
+  // image gives, never larger
+  if (a.H + 2 * a.pad < a.KH || a.W + 2 * a.pad < a.KW) return hipErrorInvalidValue;
+  if (a.OH > (a.H + 2 * a.pad - a.KH) / a.stride + 1 || a.OW > (a.W + 2 * a.pad - a.KW) / a.stride + 1)
+    return hipErrorInvalidValue;
   const dim3 grid((M + 127) / 128);
   if (a.rows) {
     const bool generic = a.pad != 0 || a.scale[0] != 1.f || a.scale[1] != 1.f || a.scale[2] != 1.f ||
