@@ -221,6 +221,15 @@ GalleryTopkArgs gallery_topk_args(const py::dict& d) {
   a.B = I(d, "B"); a.N = I(d, "N"); a.F = I(d, "F"); a.K = I(d, "K"); a.ldq = I(d, "ldq"); a.ldg = I(d, "ldg");
   return a;
 }
+ClassMapArgs class_map_args(const py::dict& d) {
+  ClassMapArgs a{};
+  a.x = P<const uint16_t>(d, "x"); a.top = P<const int32_t>(d, "top"); a.w = P<const uint16_t>(d, "w");
+  a.w1 = P<const float>(d, "w1"); a.w2 = P<const float>(d, "w2"); a.b1 = P<const float>(d, "b1");
+  a.hid = P<const float>(d, "hid"); a.alpha = P<float>(d, "alpha"); a.out = P<float>(d, "out");
+  a.B = I(d, "B"); a.HW = I(d, "HW"); a.F = I(d, "F"); a.ldx = I(d, "ldx"); a.ldo = I(d, "ldo");
+  a.NC = I(d, "NC"); a.H1 = I(d, "H1"); a.dt = I(d, "dt"); a.head = I(d, "head"); a.norm = I(d, "norm");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -344,6 +353,15 @@ PYBIND11_MODULE(_C, m) {
     chk(gallery_topk(a, S(s)), "gallery_topk");
   });
   m.def("gallery_topk_workspace", [](int B, int N, int K) { return gallery_topk_workspace(B, N, K); });
+  m.def("class_map", [](py::dict d, uintptr_t s) {
+    const auto a = class_map_args(d);
+    py::gil_scoped_release nogil;
+    chk(class_map(a, S(s)), "class_map");
+  });
+  m.attr("CLASS_MAP_MAX_F") = int(kClassMapMaxF);
+  m.attr("CLASS_MAP_MAX_HW") = int(kClassMapMaxHW);
+  m.attr("CLASS_MAP_MAX_NC") = int(kClassMapMaxNC);
+  m.attr("CLASS_MAP_MAX_H1") = int(kClassMapMaxH1);
   m.attr("GALLERY_MAX_N") = int(kGalleryMaxN);
   m.attr("GALLERY_CHUNK") = int(kGalleryChunk);
   m.attr("EMBED_MAX_F") = int(kEmbedMaxF);
@@ -677,6 +695,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_embed_rows", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_EMBED_ROWS; op.name = name; op.er = embed_rows_args(d); p.add(op);
+      })
+      .def("add_class_map", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_CLASS_MAP; op.name = name; op.cm = class_map_args(d); p.add(op);
       })
       .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);

@@ -407,6 +407,47 @@ struct GalleryTopkArgs {
 size_t gallery_topk_workspace(int B, int N, int K);
 hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s);
 
+// Grad-CAM heatmaps (kernels/explain.hip): for each image the map of its predicted class,
+//   raw_p = (1/HW) sum_c d_c x[b][p][c],   d_c = dlogit_k / d(mean_p x[b][p][c]),   k = top[b][0],
+// with d in closed form for the two head kinds (no backward pass):
+//   head = 0, linear  logit = W g + b:                  d_c = w[k][c]
+//   head = 1, MLP     logit = relu(g W1 + b1) W2 + b2:  d_c = sum_j [z_j > 0] w2[j][k] w1[j][c], j ascending,
+//     z_j = b1[j] + (even K-split partials of hid) + (odd ones), dense2_kernel's own order, so the
+//     mask is the one the logits were computed with; z_j == 0 counts as off (torch's ReLU gradient).
+// Output row, ldo fp32 words: word 0 the class (int32 bits) and word 1 the score, both copied
+// from `top`; words 2 .. 2 + HW the map in the pixel order of x: max(raw_p, 0) for norm = 0, and for
+// norm = 1 that value divided (a real fp32 division) by the row's largest, all zeros when the
+// largest is 0. Columns past 2 + HW are not written. A class outside [0, NC) gives a zero map
+// and reads nothing of w / w2. Sums run in fp32 in a fixed order: launches are bit-identical.
+// `alpha` is an fp32 workspace [B][F] that receives d of the MLP head (the linear head's d is a
+// row of w, read in place). One launch for the linear head, two for the MLP head, one more with norm.
+// x, alpha and w 16-byte aligned, every other pointer aligned to its element and not null (the MLP
+// pointers only for head = 1, w only for head = 0); F % 8 == 0 (linear) or F % 64 == 0 (MLP),
+// 8 <= F <= kClassMapMaxF, 1 <= HW <= kClassMapMaxHW (16 values per thread of the norm's workgroup),
+// 1 <= NC <= kClassMapMaxNC, 1 <= H1 <= kClassMapMaxH1 (head_dense's limit), 1 <= B <= 65535,
+// ldx % 8 == 0, ldx >= F, ldo >= 2 + HW, dt / head / norm 0 or 1; anything else is
+// hipErrorInvalidValue and nothing is launched.
+constexpr int kClassMapMaxF = 4096;
+constexpr int kClassMapMaxHW = 4096;
+constexpr int kClassMapMaxNC = 1 << 20;
+constexpr int kClassMapMaxH1 = 128;
+struct ClassMapArgs {
+  const uint16_t* x;      // [B][HW][ldx] bf16 / fp16, F used per pixel
+  const int32_t* top;     // [B][2]: int32 class, fp32 score (a softmax_topk K = 1 row)
+  const uint16_t* w;      // head 0: [NC][F] in the element type of x, 16-byte aligned
+  const float* w1;        // head 1: [H1][F] (HeadArgs' layout)
+  const float* w2;        // head 1: [H1][NC]
+  const float* b1;        // head 1: [H1]
+  const float* hid;       // head 1: [F/64][B][H1], the partials head_dense left behind
+  float* alpha;           // workspace [B][F], 16-byte aligned (written for head 1)
+  float* out;             // [B][ldo]
+  int B, HW, F, ldx, ldo, NC, H1;
+  int dt;                 // element type of x and w: 0 bf16, 1 fp16
+  int head;               // 0 linear, 1 MLP
+  int norm;               // 0 max(raw, 0), 1 divided by the row's maximum
+};
+hipError_t class_map(const ClassMapArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

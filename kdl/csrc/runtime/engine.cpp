@@ -33,6 +33,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_SOFTMAX_TOPK: return softmax_topk(op.tk, s);
     case OP_EMBED_ROWS: return embed_rows(op.er, s);
     case OP_GALLERY_TOPK: return gallery_topk(op.gt, s);
+    case OP_CLASS_MAP: return class_map(op.cm, s);
   }
   return hipErrorInvalidValue;
 }

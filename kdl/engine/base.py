@@ -43,6 +43,29 @@ def unpack_topk(rows) -> tuple:
     return a[..., :k].view(np.int32).copy(), a[..., k:].view(np.float32).copy()
 
 
+def unpack_explain(rows, h: int, w: int) -> tuple:
+    """Packed explain rows [n, 2 + h*w] (a torch tensor or numpy array of 32-bit words) ->
+    (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w]) as numpy arrays."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    assert a.shape[-1] == 2 + h * w, (a.shape, h, w)
+    return (a[..., 0].view(np.int32).copy(), a[..., 1].view(np.float32).copy(),
+            a[..., 2:].view(np.float32).reshape(*a.shape[:-1], h, w).copy())
+
+
+def pack_explain(classes, scores, heat):
+    """The inverse of ``unpack_explain``: numpy rows [n, 2 + h*w] of fp32 words."""
+    import numpy as np
+    heat = np.asarray(heat, dtype=np.float32)
+    n = heat.shape[0]
+    rows = np.empty((n, 2 + heat[0].size), dtype=np.float32)
+    rows[:, 0] = np.asarray(classes, dtype=np.int32).reshape(n).view(np.float32)
+    rows[:, 1] = np.asarray(scores, dtype=np.float32).reshape(n)
+    rows[:, 2:] = heat.reshape(n, -1)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -62,7 +85,8 @@ class Similar:
 class EngineBase:
     model_name = "model"
 
-    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None):
+    def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
+                 explain: bool = False):
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -95,6 +119,13 @@ class EngineBase:
         self.similar: Similar | None = similar
         self.feature_slots: list[torch.Tensor] = []   # similar only: per-slot fp32 features [max_batch, F]
         self._similar_work: list[torch.Tensor] = []   # similar only: per-slot gallery_topk workspace
+        # Grad-CAM outputs: False = the output is the fp32 logits; True = two more steps write the
+        # predicted class, its score and the class's heatmap over the last feature map (_enable_explain)
+        if explain and (topk or embed or similar is not None):
+            raise ValueError("explain, similar, embed and topk all replace the output rows: set one of them")
+        self.explain = bool(explain)
+        self.top1_slots: list[torch.Tensor] = []      # explain only: per-slot [max_batch, 2] class and score
+        self._cam_alpha: list[torch.Tensor] = []      # explain only: per-slot class_map workspace [max_batch, F]
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -103,13 +134,14 @@ class EngineBase:
 
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
-        if self.topk or self.embed or self.similar:
+        if self.topk or self.embed or self.similar or self.explain:
             return _lib.ptr(self._logit_slot(self._slot))
         return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
 
     def slot_logits(self, slot: int) -> torch.Tensor:
         """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, the
-        feature rows of an ``embed`` engine, or the packed neighbour rows of a ``similar`` engine."""
+        feature rows of an ``embed`` engine, the packed neighbour rows of a ``similar`` engine, or the
+        packed heatmap rows of an ``explain`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
 
     # ---------------------------------------------------------------- classification outputs
@@ -145,8 +177,9 @@ class EngineBase:
 
     def last_logits(self, slot: int = 0) -> torch.Tensor:
         """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without
-        ``topk`` / ``embed`` / ``similar``."""
-        return self._logit_slot(slot) if (self.topk or self.embed or self.similar) else self.slot_logits(slot)
+        ``topk`` / ``embed`` / ``similar`` / ``explain``."""
+        return (self._logit_slot(slot) if (self.topk or self.embed or self.similar or self.explain)
+                else self.slot_logits(slot))
 
     # ---------------------------------------------------------------- embedding outputs
     def embed_source(self) -> tuple:
@@ -249,6 +282,67 @@ class EngineBase:
                                               N=g.shape[0], F=feat.shape[1], K=self.similar_k,
                                               ldq=feat.shape[1], ldg=g.shape[1]))
 
+    # ---------------------------------------------------------------- Grad-CAM outputs
+    def cam_source(self) -> tuple:
+        """A family's last feature map: (buffer name, h, w, row stride in elements, F, element type:
+        0 bf16 / 1 fp16). It is ``embed_source()``'s buffer with its two spatial sizes. A family
+        without a spatial map in front of its head raises ValueError."""
+        raise NotImplementedError
+
+    def cam_head(self) -> dict:
+        """A family's head as ``class_map`` takes it (launch.h ClassMapArgs): ``head=0, w, NC`` for a
+        linear classifier on the pooled features, ``head=1, w1, w2, b1, hid, H1, NC`` for the MLP."""
+        raise NotImplementedError
+
+    def _enable_explain(self) -> None:
+        """Called by a family's constructor next to ``_enable_similar``. With ``explain`` the head
+        keeps writing the per-slot logits, a step "top1" (softmax_topk, K = 1) fills a per-slot
+        [max_batch, 2] buffer with the predicted class and its score, and a last step "class_map"
+        (kernels/explain.hip) writes the output rows. ``self.logits`` -- the output the executor
+        copies to the host and ``forward`` returns -- becomes [max_batch, 2 + h*w] fp32 words: the
+        class (int32 bits), its score, then the Grad-CAM map of that class over ``cam_source()``,
+        divided by its maximum (``unpack_explain``). The class-map step names the map in ``src``, so
+        the stage pipeline's buffer renaming reaches it through ``_ptr``; what else it reads (the
+        logits through "top1", the head's weights and partials) belongs to the head's own stage."""
+        if not self.explain:
+            return
+        assert not self.inputs, "explain is set at construction, before input slots exist"
+        lib = _lib.lib()
+        src, h, w, _, F, _ = self.cam_source()
+        classes = self.logits.shape[1]
+        if classes > lib.TOPK_MAX_NC:
+            raise ValueError(f"explain: {classes} classes exceed the top-1 kernel's {lib.TOPK_MAX_NC}")
+        if F % 8 or F > lib.CLASS_MAP_MAX_F or h * w > lib.CLASS_MAP_MAX_HW:
+            raise ValueError(f"explain: a {h} x {w} map of {F} features; the kernel takes a multiple of 8 up to "
+                             f"{lib.CLASS_MAP_MAX_F} features and {lib.CLASS_MAP_MAX_HW} pixels")
+        self.logit_slots = [self.logits]
+        self.top1_slots = [torch.zeros((self.max_batch, 2), dtype=torch.float32, device=self.device)]
+        self._cam_alpha = [torch.zeros((self.max_batch, F), dtype=torch.float32, device=self.device)]
+        self.logits = torch.zeros((self.max_batch, 2 + h * w), dtype=torch.float32, device=self.device)
+        self.steps.append(Step("top1", "top1", src="logits"))
+        self.steps.append(Step("explain", "class_map", src=src))
+
+    def top1_slot(self, slot: int = 0) -> torch.Tensor:
+        """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` engine."""
+        while len(self.top1_slots) <= slot:
+            self.top1_slots.append(torch.zeros_like(self.top1_slots[0]))
+            self._cam_alpha.append(torch.zeros_like(self._cam_alpha[0]))
+        return self.top1_slots[slot]
+
+    def _emit_top1(self, prog, step: Step, b: int) -> None:
+        lg = self._logit_slot(self._slot)
+        prog.add_softmax_topk(step.name, dict(x=_lib.ptr(lg), out=_lib.ptr(self.top1_slot(self._slot)), B=b,
+                                              NC=lg.shape[1], K=1, ldx=lg.shape[1]))
+
+    def _emit_explain(self, prog, step: Step, b: int) -> None:
+        _, h, w, ldx, F, dt = self.cam_source()
+        top = self.top1_slot(self._slot)
+        out = self.outputs[self._slot] if self.outputs else self.logits
+        prog.add_class_map(step.name, dict(x=self._ptr(step.src), top=_lib.ptr(top),
+                                           alpha=_lib.ptr(self._cam_alpha[self._slot]), out=_lib.ptr(out), B=b,
+                                           HW=h * w, F=F, ldx=ldx, ldo=out.shape[1], dt=dt, norm=1,
+                                           **self.cam_head()))
+
     def add_input_slots(self, n: int) -> list[torch.Tensor]:
         """Extra static input AND logits buffers, each slot with its own captured
         graphs, so a pipelined caller can H2D batch i+1 into one slot while the graph
@@ -338,6 +432,10 @@ class EngineBase:
                     self._emit_embed(prog, st, b)
                 elif st.kind == "similar":
                     self._emit_similar(prog, st, b)
+                elif st.kind == "top1":
+                    self._emit_top1(prog, st, b)
+                elif st.kind == "explain":
+                    self._emit_explain(prog, st, b)
                 else:
                     self._emit(prog, st, b)
 
@@ -360,7 +458,8 @@ class EngineBase:
     def forward(self, x: torch.Tensor, capture: bool = True) -> torch.Tensor:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
-        engine: the fp32 feature rows [n, F])."""
+        engine: the fp32 feature rows [n, F]; an ``explain`` engine: the packed rows [n, 2 + h*w], see
+        ``unpack_explain``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

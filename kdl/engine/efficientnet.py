@@ -53,8 +53,8 @@ class EfficientNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
-                 topk: int = 0, embed: str = "", similar=None):
-        super().__init__(device, max_batch, buckets, topk, embed, similar)
+                 topk: int = 0, embed: str = "", similar=None, explain: bool = False):
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()
@@ -64,6 +64,9 @@ class EfficientNetEngine(EngineBase):
         self._enable_topk()
         self._enable_embed()
         self._enable_similar()
+        if self.explain:      # classifier.1.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
+            self.cam_w = params["classifier.1.weight"].float().to(torch.bfloat16).contiguous().to(self.device)
+        self._enable_explain()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -173,6 +176,14 @@ class EfficientNetEngine(EngineBase):
         """features.8's output, the input of the avgpool step: 19 x 19 pixels of 2560 bf16."""
         gap = next(s for s in self.steps if s.kind == "gap")
         return "E", gap.geom[0] * gap.geom[1], E.HEAD, E.HEAD, 0
+
+    def cam_source(self) -> tuple:
+        """features.8's output, ``embed_source()``'s map: 19 x 19 pixels of 2560 bf16 at 600 x 600."""
+        gap = next(s for s in self.steps if s.kind == "gap")
+        return "E", gap.geom[0], gap.geom[1], E.HEAD, E.HEAD, 0
+
+    def cam_head(self) -> dict:
+        return dict(head=0, w=_lib.ptr(self.cam_w), NC=self.classes)
 
     def scratch_buffers(self) -> list[str]:
         """SE partial pools (written by the dw kernel, not a step dst) and scales: used

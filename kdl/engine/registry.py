@@ -23,6 +23,11 @@ class ModelInfo:
     stage_cut: str = ""       # default stage-pipeline cut (stages.py) for bench / serving; "" = lanes
     features: int = 0         # F: floats of the pooled feature vector in front of the head
     feature_oracle: Callable = None   # (params, uint8 NHWC) -> fp32 [n, F], what engines pool with embed=
+    # (params, uint8 NHWC) -> (class int32 [n], score fp32 [n], heat fp32 [n, h, w]): the Grad-CAM map of
+    # the predicted class over the feature map in front of the head, what engines answer with
+    # explain=True; None for a family without a spatial map there (ViT)
+    cam_oracle: Callable = None
+    map_size: tuple = ()      # (h, w) of that map at the family's input size
 
 
 def _no_grad_mean(base, p, x_nchw):
@@ -30,6 +35,32 @@ def _no_grad_mean(base, p, x_nchw):
     import torch
     with torch.no_grad():
         return base(p, x_nchw).mean(dim=(2, 3))
+
+
+def _cam(base, head, p, x_nchw):
+    """Grad-CAM as the Keras example defines it, by ``torch.autograd`` through a family's own head
+    on its own fp32 feature map [n, F, H, W]: k the top-1 class, alpha_c the mean over the pixels of
+    dlogit_k/dA (= (1/HW) dlogit_k/dg_c), raw_p = sum_c alpha_c A[p][c], heat = max(raw, 0) / its
+    largest value, all zeros when that is 0. The score is the class's softmax probability."""
+    import torch
+    with torch.no_grad():
+        a = base(p, x_nchw).float()
+    a.requires_grad_(True)
+    with torch.enable_grad():
+        logits = head(p, a)
+        k = logits.argmax(dim=1)
+        (g,) = torch.autograd.grad(logits.gather(1, k[:, None]).sum(), a)
+    with torch.no_grad():
+        alpha = g.mean(dim=(2, 3), keepdim=True)
+        raw = torch.relu((alpha * a.detach()).sum(dim=1))
+        m = raw.amax(dim=(1, 2), keepdim=True)
+        heat = torch.where(m > 0, raw / m.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(raw))
+        score = torch.softmax(logits.detach(), dim=1).gather(1, k[:, None])[:, 0]
+    return k.to(torch.int32), score.float(), heat.float()
+
+
+def _linear_head(weight: str, bias: str):
+    return lambda p, a: a.mean(dim=(2, 3)) @ p[weight].t() + p[bias]
 
 
 def _xception():
@@ -43,7 +74,11 @@ def _xception():
                      lambda p, x: X.xception_forward(p, x.float() / 127.5 - 1.0),
                      stage_cut="block8_sepconv3", features=X.DEFAULT_HEAD.features,
                      feature_oracle=lambda p, x: _no_grad_mean(X.base_forward, p, (x.float() / 127.5 - 1.0)
-                                                               .permute(0, 3, 1, 2).contiguous()))
+                                                               .permute(0, 3, 1, 2).contiguous()),
+                     cam_oracle=lambda p, x, head=X.DEFAULT_HEAD: _cam(
+                         X.base_forward, lambda q, a: X.head_forward(q, a, head), p,
+                         (x.float() / 127.5 - 1.0).permute(0, 3, 1, 2).contiguous()),
+                     map_size=(10, 10))
 
 
 def _resnet50(dtype: str = "fp16"):
@@ -59,7 +94,10 @@ def _resnet50(dtype: str = "fp16"):
                      # three stages (3 compute streams): +1.3-1.9 % over the round-2 cut after layer3.1
                      # (profiles/stages3_ab_r3.txt)
                      R.resnet_forward, dtype=dtype, tuning="resnet50", stage_cut="layer2.1.conv3,layer3.3.conv3",
-                     features=2048, feature_oracle=lambda p, x: _no_grad_mean(R.features, p, R.preprocess(x)))
+                     features=2048, feature_oracle=lambda p, x: _no_grad_mean(R.features, p, R.preprocess(x)),
+                     cam_oracle=lambda p, x: _cam(R.features, _linear_head("fc.weight", "fc.bias"), p,
+                                                  R.preprocess(x)),
+                     map_size=(7, 7))
 
 
 def _vit_b16():
@@ -82,7 +120,11 @@ def _efficientnet_b7():
                      lambda p, max_batch, device, **kw: EfficientNetEngine(p, max_batch=max_batch, device=device,
                                                                            **kw),
                      E.efficientnet_forward, stage_cut="features.4.9.block.3",
-                     features=E.HEAD, feature_oracle=lambda p, x: _no_grad_mean(E.features, p, E.preprocess(x)))
+                     features=E.HEAD, feature_oracle=lambda p, x: _no_grad_mean(E.features, p, E.preprocess(x)),
+                     cam_oracle=lambda p, x: _cam(E.features, _linear_head("classifier.1.weight",
+                                                                           "classifier.1.bias"), p,
+                                                  E.preprocess(x)),
+                     map_size=(19, 19))
 
 
 def _vit_b16_fp8():

@@ -46,10 +46,10 @@ class ResNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
-                 dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None):
+                 dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None, explain: bool = False):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
-        super().__init__(device, max_batch, buckets, topk, embed, similar)
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind
@@ -63,6 +63,9 @@ class ResNetEngine(EngineBase):
         self._enable_topk()
         self._enable_embed()
         self._enable_similar()
+        if self.explain:      # fc.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
+            self.cam_w = params["fc.weight"].float().to(self.dtype).contiguous().to(self.device)
+        self._enable_explain()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -161,6 +164,16 @@ class ResNetEngine(EngineBase):
         h, w, c, border = self.shapes[gap.src]
         assert border == 0
         return gap.src, h * w, c, gap.extra["F"], self.dt
+
+    def cam_source(self) -> tuple:
+        """layer4's output, ``embed_source()``'s map: 7 x 7 pixels of 2048."""
+        gap = next(s for s in self.steps if s.kind == "gap")
+        h, w, c, border = self.shapes[gap.src]
+        assert border == 0
+        return gap.src, h, w, c, gap.extra["F"], self.dt
+
+    def cam_head(self) -> dict:
+        return dict(head=0, w=_lib.ptr(self.cam_w), NC=self.classes)
 
     def scratch_buffers(self) -> list[str]:
         return []

@@ -45,7 +45,10 @@ class ViTEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
-                 topk: int = 0, embed: str = "", similar=None):
+                 topk: int = 0, embed: str = "", similar=None, explain: bool = False):
+        if explain:      # before anything touches the device: the class token has no spatial map
+            raise ValueError("ViT-B/16 has no spatial feature map in front of its head: no explain outputs "
+                             "(attention rollout is not implemented)")
         super().__init__(device, max_batch, buckets, topk, embed, similar)
         self.fp8 = fp8
         if fp8:

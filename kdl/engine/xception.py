@@ -44,8 +44,9 @@ class XceptionEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
-                 tune_file: str | Path | None = None, topk: int = 0, embed: str = "", similar=None):
-        super().__init__(device, max_batch, buckets, topk, embed, similar)
+                 tune_file: str | Path | None = None, topk: int = 0, embed: str = "", similar=None,
+                 explain: bool = False):
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
@@ -70,6 +71,7 @@ class XceptionEngine(EngineBase):
         self._enable_topk()
         self._enable_embed()
         self._enable_similar()
+        self._enable_explain()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -252,6 +254,17 @@ class XceptionEngine(EngineBase):
         """block14's output, the map the head's fused pool reads: 10 x 10 pixels of 2048 bf16."""
         h, w, ld = self.shapes[self.feat_buf]
         return self.feat_buf, h * w, ld, self.head.features, 0
+
+    def cam_source(self) -> tuple:
+        """block14_sepconv2_act, the layer the Keras Grad-CAM example names: ``embed_source()``'s map."""
+        h, w, ld = self.shapes[self.feat_buf]
+        return self.feat_buf, h, w, ld, self.head.features, 0
+
+    def cam_head(self) -> dict:
+        """The clothing head's own weights, and the dense1 partials its last launch left in head_hid."""
+        hd = self.head
+        return dict(head=1, w1=_lib.ptr(self.w1), w2=_lib.ptr(self.w2), b1=_lib.ptr(self.b1),
+                    hid=_lib.ptr(self.head_hid), H1=hd.hidden_units, NC=hd.classes)
 
     def apply_tuning(self, d: dict) -> None:
         """The conv layers' table plus the optional fused-stem entry (an int: stem_conv3x3 config)."""

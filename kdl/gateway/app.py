@@ -5,6 +5,9 @@ top-K classes and softmax scores, its label strings: the classify signature of t
 model's head: the embed signature of the mode).
 ``POST /similar {"url": ...}`` -> ``{"neighbors": [{"id": ..., "score": ...}, ...]}`` (the nearest items
 of the model version's gallery, nearest first: the similar signature of the mode).
+``POST /explain {"url": ...}`` -> ``{"label": ..., "score": ..., "heatmap": [[...], ...]}`` (the predicted
+class and its Grad-CAM map over the model's last feature map, h rows of w values in 0..1: the explain
+signature of the mode; upsampling and colouring are the client's).
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -38,7 +41,8 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_embed_response, process_response, process_similar_response)
+                     process_embed_response, process_explain_response, process_response,
+                     process_similar_response)
 
 
 class GatewayConfig:
@@ -137,6 +141,9 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     similar_sig = {"bytes": ("similar_bytes", "image_bytes"), "raw": ("similar_image", "images")}.get(
         cfg.mode, ("similar", "images"))
 
+    explain_sig = {"bytes": ("explain_bytes", "image_bytes"), "raw": ("explain_image", "images")}.get(
+        cfg.mode, ("explain", "images"))
+
     def uint8_input(img):
         if cfg.mode == "bytes":
             return [img]
@@ -193,6 +200,22 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except grpc.RpcError as e:
             return grpc_fail(e)
         return jsonify({"neighbors": process_similar_response(pb_result)[0]})
+
+    @app.route("/explain", methods=["POST"])
+    def explain():
+        body = request.get_json(silent=True)
+        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
+            return fail(400, 'request body must be JSON {"url": "<image url>"}')
+        try:
+            img = load(body["url"])
+        except LookupError as e:
+            return fail(502, str(e))
+        try:
+            req = make_request(uint8_input(img), cfg.model_name, explain_sig[0], explain_sig[1])
+            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
+        except grpc.RpcError as e:
+            return grpc_fail(e)
+        return jsonify(process_explain_response(pb_result)[0])
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

@@ -90,3 +90,14 @@ def process_embed_response(pb_result) -> list[list[float]]:
     n, f = [d.size for d in t.tensor_shape.dim]
     vals = np.asarray(t.float_val, dtype=np.float32).reshape(n, f)
     return [[float(v) for v in row] for row in vals]
+
+
+def process_explain_response(pb_result) -> list[dict]:
+    """An explain signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT
+    [n, 1], ``heatmap`` DT_FLOAT [n, h, w]) -> per image ``{"label", "score", "heatmap"}``, the map
+    as h rows of w floats."""
+    cl, sc, hm = pb_result.outputs["classes"], pb_result.outputs["scores"], pb_result.outputs["heatmap"]
+    n, h, w = [d.size for d in hm.tensor_shape.dim]
+    maps = np.asarray(hm.float_val, dtype=np.float32).reshape(n, h, w)
+    return [{"label": cl.string_val[i].decode(), "score": float(sc.float_val[i]),
+             "heatmap": [[float(v) for v in row] for row in maps[i]]} for i in range(n)]

@@ -79,6 +79,9 @@ class SignatureInfo:
     # embed signatures (serving/embed.py): "raw" / "l2" = the single output is the pooled feature
     # vector in front of the head, [-1, F] fp32; "" for every other signature
     embed: str = ""
+    # explain signatures (serving/explain.py): (h, w) of the Grad-CAM map; a row is the predicted
+    # class, its score and h*w map values; () for every other signature
+    explain: tuple = ()
 
     def output_specs(self) -> tuple:
         return self.outputs or ((self.output_key, P.DT_FLOAT, self.output_shape),)
@@ -157,6 +160,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     if gallery:
         from .similar import add_signatures as add_similar_signatures
         add_similar_signatures(src, path, similar_top_k)
+    from .explain import add_signatures as add_explain_signatures
+    add_explain_signatures(src, path)
     return src
 
 
@@ -421,6 +426,8 @@ class GPUExecutor(_Executor):
             from ..engine.base import Similar
             from .similar import device_gallery
             tk = dict(similar=Similar(device_gallery(src, dev), r.similar_k, src.similar_metric))
+        if r.explain:                                          # the explain runner: rows of 2 + h*w words
+            tk = dict(explain=True)
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -612,10 +619,11 @@ class CPUExecutor(_Executor):
         self.staging = torch.zeros((bs, S, S, 3), dtype=torch.uint8 if u8 else torch.float32)
         self.out = torch.zeros((bs, self.runner.out_cols), dtype=torch.float32)
         self.u8 = u8
-        if src.family != "xception" or self.runner.embed:
+        if src.family != "xception" or self.runner.embed or self.runner.explain_hw:
             from ..engine import registry
             info = registry.get(src.family)
-            self.oracle = info.feature_oracle if self.runner.embed else info.oracle
+            self.oracle = (info.cam_oracle if self.runner.explain_hw else
+                           info.feature_oracle if self.runner.embed else info.oracle)
 
     def staging_ptr(self, slot: int = 0) -> int:
         return self.staging.data_ptr()
@@ -623,6 +631,12 @@ class CPUExecutor(_Executor):
     def execute(self, bucket: int, n_real: int) -> int:
         x = self.staging[:n_real]
         src = self.runner.source
+        if self.runner.explain_hw:         # the explain runner: autograd through the family's own head
+            from .explain import pack_rows
+            kw = dict(head=src.head) if src.family == "xception" and src.head is not None else {}
+            k, score, heat = self.oracle(src.params, x, **kw)
+            self.out[:n_real] = torch.from_numpy(pack_rows(k.numpy(), score.numpy(), heat.numpy()))
+            return self.out.data_ptr()
         if self.runner.embed:              # the embed runner: fp32 feature rows, normalised by the same rule
             rows = self.oracle(src.params, x)
             if self.runner.embed == "l2":
@@ -680,10 +694,14 @@ class SignatureRunner:
     embed_dim = 0
     similar = False     # the engines end in the similar step and rows are 2K words (SimilarRunner)
     similar_k = 0
+    explain = False     # the engines end in the class-map step and rows are 2 + h*w words (ExplainRunner)
+    explain_hw = ()     # (h, w) of an explain runner's map, on any device
 
     @property
     def out_cols(self) -> int:
         """32-bit words per result row, from the executor to the waiting handler."""
+        if self.explain_hw:
+            return 2 + self.explain_hw[0] * self.explain_hw[1]
         if self.similar:
             return 2 * self.similar_k
         if self.embed:
@@ -848,6 +866,24 @@ class SimilarRunner(SignatureRunner):
         return pack_rows(*similar_rule(rows, self.source.gallery, self.k, self.source.similar_metric))
 
 
+class ExplainRunner(SignatureRunner):
+    """The ``explain`` signature: like ``serving_uint8``'s runner, but a result row is the predicted
+    class (int32 bits), its score and the class's Grad-CAM map, 2 + h*w words (serving/explain.py).
+    GPU executors build their engines with ``explain=True``, so the rows come out of the captured
+    program; the CPU executor packs the family's ``cam_oracle`` answer the same way; the null
+    device's rows are zeroed here (class 0, score 0, an empty map)."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.explain_hw = tuple(sig.explain)
+        self.explain = bool(devices)
+        self._null = not devices and cfg.device == "null"
+        super().__init__(sig, source, cfg, devices)
+
+    def _run(self, n: int, submit) -> np.ndarray:
+        rows = super()._run(n, submit)
+        return np.zeros_like(rows) if self._null else rows
+
+
 class Servable:
     """One loaded model version (all its signatures)."""
 
@@ -878,8 +914,17 @@ class Servable:
                                        "in signature def")
                 from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
                 from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
+                from .explain import EXPLAIN_BYTES_SIGNATURE, EXPLAIN_IMAGE_SIGNATURE, EXPLAIN_SIGNATURE
                 from .similar import SIMILAR_BYTES_SIGNATURE, SIMILAR_IMAGE_SIGNATURE, SIMILAR_SIGNATURE
-                if sig_name == SIMILAR_SIGNATURE:
+                if sig_name == EXPLAIN_SIGNATURE:
+                    r = ExplainRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == EXPLAIN_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(EXPLAIN_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == EXPLAIN_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(EXPLAIN_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == SIMILAR_SIGNATURE:
                     r = SimilarRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 elif sig_name == SIMILAR_IMAGE_SIGNATURE:
                     r = ImageRunner(self.signatures[sig_name], self.runner(SIMILAR_SIGNATURE), self._devices,
@@ -925,7 +970,7 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # a wrapper (serving_image / serving_bytes, the classify_*, embed_* and similar_* pairs) has no batcher
+        # a wrapper (serving_image / serving_bytes, the classify_*, embed_*, similar_* and explain_* pairs) has no batcher
         # of its own: it feeds its inner runner's, so that is where its work shows
         def batcher(r):
             return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)

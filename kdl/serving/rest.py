@@ -9,6 +9,7 @@ Routes (TF-Serving REST semantics):
        (serving_bytes: every value is {"b64": "<base64 of the image file>"})
        (classify signatures: {"classes": [...], "scores": [...]} per instance, or by column)
        (embed signatures: the feature rows, as "predictions" or "outputs")
+       (explain signatures: {"classes": [label], "scores": [score], "heatmap": [[...]]} per instance, or by column)
   POST /v1/models/<name>[/versions/<v>|/labels/<l>]:classify
        {"signature_name"?, "examples": [{"image/encoded": {"b64": ...}}, ...]}
                                                 -> {"results": [[["label", score], ...], ...]}
@@ -146,7 +147,11 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
 
         @staticmethod
         def _body(s, sig, out, rows: bool) -> dict:
-            """The :predict answer: logits, or a classify signature's two named outputs."""
+            """The :predict answer: logits, a classify signature's two named outputs, or an explain
+            signature's three."""
+            if sig.explain:
+                from .explain import explain_body
+                return explain_body(s, sig, out, rows)
             if sig.embed:
                 METRICS.inc("kdl_embed_total", signature=sig.name)
             if not sig.top_k:
