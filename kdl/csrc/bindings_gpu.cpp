@@ -230,6 +230,19 @@ ClassMapArgs class_map_args(const py::dict& d) {
   a.NC = I(d, "NC"); a.H1 = I(d, "H1"); a.dt = I(d, "dt"); a.head = I(d, "head"); a.norm = I(d, "norm");
   return a;
 }
+AttnRolloutArgs attn_rollout_args(const py::dict& d) {
+  AttnRolloutArgs a{};
+  a.qkv = P<const uint16_t>(d, "qkv"); a.r_in = P<const float>(d, "r_in"); a.r_out = P<float>(d, "r_out");
+  a.B = I(d, "B"); a.T = I(d, "T"); a.Tq = I(d, "Tq"); a.H = I(d, "H"); a.dh = I(d, "dh", 64);
+  a.scale = F(d, "scale", 0.125f); a.ldr = I(d, "ldr");
+  return a;
+}
+RolloutMapArgs rollout_map_args(const py::dict& d) {
+  RolloutMapArgs a{};
+  a.r = P<const float>(d, "r"); a.top = P<const int32_t>(d, "top"); a.out = P<float>(d, "out");
+  a.B = I(d, "B"); a.T = I(d, "T"); a.ldr = I(d, "ldr"); a.ldo = I(d, "ldo");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -358,6 +371,17 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(class_map(a, S(s)), "class_map");
   });
+  m.def("attn_rollout", [](py::dict d, uintptr_t s) {
+    const auto a = attn_rollout_args(d);
+    py::gil_scoped_release nogil;
+    chk(attn_rollout(a, S(s)), "attn_rollout");
+  });
+  m.def("rollout_map", [](py::dict d, uintptr_t s) {
+    const auto a = rollout_map_args(d);
+    py::gil_scoped_release nogil;
+    chk(rollout_map(a, S(s)), "rollout_map");
+  });
+  m.attr("ROLLOUT_MAX_T") = int(kRolloutMaxT);
   m.attr("CLASS_MAP_MAX_F") = int(kClassMapMaxF);
   m.attr("CLASS_MAP_MAX_HW") = int(kClassMapMaxHW);
   m.attr("CLASS_MAP_MAX_NC") = int(kClassMapMaxNC);
@@ -698,6 +722,12 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_class_map", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_CLASS_MAP; op.name = name; op.cm = class_map_args(d); p.add(op);
+      })
+      .def("add_attn_rollout", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_ATTN_ROLLOUT; op.name = name; op.ar = attn_rollout_args(d); p.add(op);
+      })
+      .def("add_rollout_map", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_ROLLOUT_MAP; op.name = name; op.rm = rollout_map_args(d); p.add(op);
       })
       .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);

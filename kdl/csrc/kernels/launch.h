@@ -448,6 +448,43 @@ struct ClassMapArgs {
 };
 hipError_t class_map(const ClassMapArgs& a, hipStream_t s);
 
+// Attention rollout (kernels/rollout.hip; Abnar & Zuidema 2020): one launch per encoder layer next
+// to its attention step, on the same packed qkv [B*T][3*H*dh] bf16. With P_h = softmax over the keys
+// of Q_h K_h^T * scale (bf16 MFMA, fp32 accumulation, the full-row maximum and sum),
+//   A^ = (mean_h P_h + I) / 2   (its rows sum to 1),   r_out = A^ r_in,   r_in == null: r_out = A^.
+// r_in / r_out are fp32 [B][T][ldr]; the state and the product are fp32 throughout
+// (v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain). Only the query rows 0 .. Tq-1 are computed and
+// written (the last layer needs row 0 alone); columns >= T, rows >= Tq and images >= B of r_out
+// are never written, rows >= T of r_in never read and its columns >= T never used, keys >= T masked. Sums run in a
+// fixed order without atomics: launches are bit-identical, row 0 of a Tq = 1 launch equals row 0
+// of a Tq = T launch, and r_in == null equals an explicit identity r_in, bit for bit.
+// dh != 64, T outside 1..kRolloutMaxT, H < 1, B < 1, Tq outside 1..T, ldr < T, ldr % 4 != 0, a null
+// or not 16-byte aligned qkv / r_out (r_in: aligned when set) and r_in == r_out are
+// hipErrorInvalidValue, and nothing is launched.
+constexpr int kRolloutMaxT = 256;
+struct AttnRolloutArgs {
+  const uint16_t* qkv;
+  const float* r_in;      // null: the first layer
+  float* r_out;
+  int B, T, Tq, H, dh;    // dh = 64
+  float scale;            // 1/sqrt(dh)
+  int ldr;                // row stride of r_in / r_out in floats
+};
+hipError_t attn_rollout(const AttnRolloutArgs& a, hipStream_t s);
+
+// The rollout heatmap row of each image: out[b][0], out[b][1] = top[b] (int32 class, fp32 score: a
+// softmax_topk K = 1 row), out[b][2 .. T] = r[b][0][1 .. T-1] divided (a real fp32 division) by
+// their largest value: ClassMapArgs' row layout with h * w = T - 1. Columns past T are not written.
+// T outside 2..kRolloutMaxT, B < 1, ldr < T, ldr % 4 != 0, ldo < T + 1 and a null or unaligned r /
+// top / out are hipErrorInvalidValue, and nothing is launched.
+struct RolloutMapArgs {
+  const float* r;         // [B][T][ldr], row 0 of each image is read
+  const int32_t* top;     // [B][2]
+  float* out;             // [B][ldo]
+  int B, T, ldr, ldo;
+};
+hipError_t rollout_map(const RolloutMapArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

@@ -34,6 +34,8 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_EMBED_ROWS: return embed_rows(op.er, s);
     case OP_GALLERY_TOPK: return gallery_topk(op.gt, s);
     case OP_CLASS_MAP: return class_map(op.cm, s);
+    case OP_ATTN_ROLLOUT: return attn_rollout(op.ar, s);
+    case OP_ROLLOUT_MAP: return rollout_map(op.rm, s);
   }
   return hipErrorInvalidValue;
 }

@@ -86,7 +86,7 @@ class EngineBase:
     model_name = "model"
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
-                 explain: bool = False):
+                 explain: bool = False, rollout: bool = False):
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -126,6 +126,12 @@ class EngineBase:
         self.explain = bool(explain)
         self.top1_slots: list[torch.Tensor] = []      # explain only: per-slot [max_batch, 2] class and score
         self._cam_alpha: list[torch.Tensor] = []      # explain only: per-slot class_map workspace [max_batch, F]
+        # attention-rollout outputs (ViT): False = the output is the fp32 logits; True = one more step
+        # beside every layer's attention, then "top1" and "rollout_map" behind the head write the
+        # predicted class, its score and the rollout heatmap, explain's row layout (ViTEngine._enable_rollout)
+        if rollout and (topk or embed or similar is not None or explain):
+            raise ValueError("rollout, explain, similar, embed and topk all replace the output rows: set one of them")
+        self.rollout = bool(rollout)
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -134,14 +140,14 @@ class EngineBase:
 
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
-        if self.topk or self.embed or self.similar or self.explain:
+        if self.topk or self.embed or self.similar or self.explain or self.rollout:
             return _lib.ptr(self._logit_slot(self._slot))
         return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
 
     def slot_logits(self, slot: int) -> torch.Tensor:
         """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, the
         feature rows of an ``embed`` engine, the packed neighbour rows of a ``similar`` engine, or the
-        packed heatmap rows of an ``explain`` engine."""
+        packed heatmap rows of an ``explain`` or ``rollout`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
 
     # ---------------------------------------------------------------- classification outputs
@@ -177,8 +183,8 @@ class EngineBase:
 
     def last_logits(self, slot: int = 0) -> torch.Tensor:
         """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without
-        ``topk`` / ``embed`` / ``similar`` / ``explain``."""
-        return (self._logit_slot(slot) if (self.topk or self.embed or self.similar or self.explain)
+        ``topk`` / ``embed`` / ``similar`` / ``explain`` / ``rollout``."""
+        return (self._logit_slot(slot) if (self.topk or self.embed or self.similar or self.explain or self.rollout)
                 else self.slot_logits(slot))
 
     # ---------------------------------------------------------------- embedding outputs
@@ -323,10 +329,12 @@ class EngineBase:
         self.steps.append(Step("explain", "class_map", src=src))
 
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
-        """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` engine."""
+        """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
+        ``rollout`` engine."""
         while len(self.top1_slots) <= slot:
             self.top1_slots.append(torch.zeros_like(self.top1_slots[0]))
-            self._cam_alpha.append(torch.zeros_like(self._cam_alpha[0]))
+            if self._cam_alpha:
+                self._cam_alpha.append(torch.zeros_like(self._cam_alpha[0]))
         return self.top1_slots[slot]
 
     def _emit_top1(self, prog, step: Step, b: int) -> None:
@@ -458,8 +466,8 @@ class EngineBase:
     def forward(self, x: torch.Tensor, capture: bool = True) -> torch.Tensor:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
-        engine: the fp32 feature rows [n, F]; an ``explain`` engine: the packed rows [n, 2 + h*w], see
-        ``unpack_explain``)."""
+        engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
+        [n, 2 + h*w], see ``unpack_explain``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

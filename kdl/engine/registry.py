@@ -27,7 +27,11 @@ class ModelInfo:
     # the predicted class over the feature map in front of the head, what engines answer with
     # explain=True; None for a family without a spatial map there (ViT)
     cam_oracle: Callable = None
-    map_size: tuple = ()      # (h, w) of that map at the family's input size
+    map_size: tuple = ()      # (h, w) of that map (or of the rollout map) at the family's input size
+    # (params, uint8 NHWC) -> (class int32 [n], score fp32 [n], heat fp32 [n, h, w]): the attention-rollout
+    # map of a transformer (Abnar & Zuidema 2020) in fp32 torch, what engines answer with rollout=True;
+    # None for the CNN families. cam_oracle stays None for ViT: rollout is another method.
+    rollout_oracle: Callable = None
 
 
 def _no_grad_mean(base, p, x_nchw):
@@ -108,7 +112,8 @@ def _vit_b16():
                      lambda seed=0: V.init_params(seed=seed),
                      lambda p, max_batch, device, **kw: ViTEngine(p, max_batch=max_batch, device=device, **kw),
                      V.vit_forward, stage_cut="encoder.layers.encoder_layer_5.mlp.3",
-                     features=V.DIM, feature_oracle=V.vit_features)
+                     features=V.DIM, feature_oracle=V.vit_features,
+                     rollout_oracle=V.vit_rollout, map_size=(V.INPUT_SIZE // V.PATCH, V.INPUT_SIZE // V.PATCH))
 
 
 def _efficientnet_b7():
@@ -137,7 +142,8 @@ def _vit_b16_fp8():
                                                                   **kw),
                      V.vit_forward, dtype="fp8-e4m3 linears / bf16 rest",
                      stage_cut="encoder.layers.encoder_layer_5.mlp.3",
-                     features=V.DIM, feature_oracle=V.vit_features)
+                     features=V.DIM, feature_oracle=V.vit_features,
+                     rollout_oracle=V.vit_rollout, map_size=(V.INPUT_SIZE // V.PATCH, V.INPUT_SIZE // V.PATCH))
 
 
 _FACTORIES = {"xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),

@@ -10,6 +10,7 @@ Lowering (captured into one hipGraph per batch bucket; rows = B*197 tokens):
       layernorm     ln_1
       conv_gemm PW  QKV 768 -> 2304 (+bias)
       attention     flash-style MFMA attention, 12 heads x 64, online softmax
+      [attn_rollout rollout=True only: R := (mean_h softmax(QK^T/8) + I)/2 . R, fp32 (kernels/rollout.hip)]
       conv_gemm PW  out_proj 768 -> 768 (+bias) + residual (in place on X)
       layernorm     ln_2
       conv_gemm PW  mlp.0 768 -> 3072 (+bias, exact GELU epilogue)
@@ -19,6 +20,12 @@ Lowering (captured into one hipGraph per batch bucket; rows = B*197 tokens):
 
 = 3 + 12*7 + 2 = 89 launches. Every linear layer runs on the same pipelined
 LDS-DMA MFMA GEMM as the CNNs (a 1x1 conv over a 1 x rows "image").
+
+rollout=True (attention-rollout heatmaps, Abnar & Zuidema 2020): the attention kernel never
+materialises its probabilities, so every layer gets one more step behind its QKV GEMM that forms them
+again from the same QKV buffer, averages the heads, adds the identity and multiplies the fp32
+rollout state (two buffers R0 / R1, alternating; the last layer computes row 0 only). Behind the head,
+"top1" and "rollout_map" write [class, score, 196 heat values] per image: explain's row layout.
 
 fp8=True (BASELINE.json "fp8 MFMA" config): the four linears of every layer run on
 gemm_f8.hip (OCP e4m3 x e4m3, block-scaled MFMA 16x16x128); ln_1 / ln_2 /
@@ -45,11 +52,11 @@ class ViTEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
-                 topk: int = 0, embed: str = "", similar=None, explain: bool = False):
+                 topk: int = 0, embed: str = "", similar=None, explain: bool = False, rollout: bool = False):
         if explain:      # before anything touches the device: the class token has no spatial map
             raise ValueError("ViT-B/16 has no spatial feature map in front of its head: no explain outputs "
-                             "(attention rollout is not implemented)")
-        super().__init__(device, max_batch, buckets, topk, embed, similar)
+                             "(its heatmaps are attention rollout: rollout=True)")
+        super().__init__(device, max_batch, buckets, topk, embed, similar, rollout=rollout)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"
@@ -61,12 +68,15 @@ class ViTEngine(EngineBase):
         self.size = V.INPUT_SIZE
         self.T = V.TOKENS
         self.np = self.T - 1
+        self.ldr = (self.T + 3) // 4 * 4      # rollout only: row stride of the fp32 state R [max_batch, T, ldr]
+        self._r_last = None                   # rollout only: the buffer the last layer's rollout step writes
         self.classes = params["heads.head.bias"].numel()
         self._build(params)
         self._alloc()
         self._enable_topk()
         self._enable_embed()
         self._enable_similar()
+        self._enable_rollout()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -97,11 +107,13 @@ class ViTEngine(EngineBase):
             self.ln[f"{L}.ln_2"] = (p[f"{L}.ln_2.weight"].float().to(dev), p[f"{L}.ln_2.bias"].float().to(dev))
             if self.fp8:
                 self._build_layer_f8(p, i, L)
+                self._add_rollout_step(i, L)
                 continue
             self.steps.append(Step("ln", f"{L}.ln_1", src="X", dst="Xn"))
             self.steps.append(Step("conv", f"{L}.qkv", self._lin(
                 f"{L}.qkv", p[f"{L}.self_attention.in_proj_weight"], p[f"{L}.self_attention.in_proj_bias"]),
                 "Xn", "QKV"))
+            self._add_rollout_step(i, L)
             self.steps.append(Step("attn", f"{L}.attn", src="QKV", dst="A"))
             self.steps.append(Step("conv", f"{L}.out_proj", self._lin(
                 f"{L}.out_proj", p[f"{L}.self_attention.out_proj.weight"],
@@ -118,6 +130,20 @@ class ViTEngine(EngineBase):
         self.head_nf = nf
         self.head_b = p["heads.head.bias"].float().to(dev)
         self.steps.append(Step("fc", "heads.head", src="CLS", dst="logits"))
+
+    def _add_rollout_step(self, i: int, L: str) -> None:
+        """rollout only: layer i's rollout step, right behind its QKV GEMM (bf16 in both builds). It
+        names what it reads and writes like every step, so ``plan_stages`` versions R0 / R1 too: the R
+        that crosses a stage cut comes out double-buffered by batch parity."""
+        if not self.rollout:
+            return
+        dst = f"R{i & 1}"
+        step = Step("rollout", f"{L}.rollout", src="QKV", res=self._r_last, dst=dst,
+                    extra=dict(Tq=1 if i == V.DEPTH - 1 else self.T))      # only row 0 of the last R is used
+        # the fp8 layer is already complete: the step goes in behind its qkv step, in front of attention
+        at = next((k for k in range(len(self.steps) - 1, -1, -1) if self.steps[k].name == f"{L}.qkv"), None)
+        self.steps.insert(at + 1, step)
+        self._r_last = dst
 
     def _build_layer_f8(self, p: dict, i: int, L: str) -> None:
         """One encoder layer with all four linears on the e4m3 GEMM (static scales)."""
@@ -154,7 +180,30 @@ class ViTEngine(EngineBase):
             u8 = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=dev)  # noqa: E731
             self.bufs.update({"Xn8": u8(B * T, D), "A8": u8(B * T, D), "Hd8": u8(B * T, V.MLP)})
             self.ld.update({"Xn8": D, "A8": D, "Hd8": V.MLP})
+        if self.rollout:
+            for nm in ("R0", "R1"):
+                self.bufs[nm] = torch.zeros((B, T, self.ldr), dtype=torch.float32, device=dev)
+                self.ld[nm] = self.ldr
         self.logits = torch.zeros((B, self.classes), dtype=torch.float32, device=dev)
+
+    def _enable_rollout(self) -> None:
+        """With ``rollout`` the head keeps writing the per-slot logits, "top1" (softmax_topk, K = 1)
+        fills the per-slot [max_batch, 2] class and score, and a last step "rollout_map" writes the
+        output rows from row 0 of the last R, which it names in ``src``. ``self.logits`` becomes
+        [max_batch, 2 + 14 * 14] fp32 words (``unpack_explain`` with h = w = 14)."""
+        if not self.rollout:
+            return
+        assert not self.inputs, "rollout is set at construction, before input slots exist"
+        lib = _lib.lib()
+        if self.classes > lib.TOPK_MAX_NC:
+            raise ValueError(f"rollout: {self.classes} classes exceed the top-1 kernel's {lib.TOPK_MAX_NC}")
+        if self.T > lib.ROLLOUT_MAX_T:
+            raise ValueError(f"rollout: {self.T} tokens exceed the kernel's {lib.ROLLOUT_MAX_T}")
+        self.logit_slots = [self.logits]
+        self.top1_slots = [torch.zeros((self.max_batch, 2), dtype=torch.float32, device=self.device)]
+        self.logits = torch.zeros((self.max_batch, 2 + self.np), dtype=torch.float32, device=self.device)
+        self.steps.append(Step("top1", "top1", src="logits"))
+        self.steps.append(Step("rollout_map", "rollout_map", src=self._r_last))
 
     def _ptr(self, name: str) -> int:
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
@@ -222,6 +271,16 @@ class ViTEngine(EngineBase):
             out = dict(out8=self._ptr(step.dst), inv_scale=1.0 / osc) if osc else dict(out=self._ptr(step.dst))
             prog.add_attention(step.name, dict(qkv=self._ptr("QKV"), B=b, T=self.T, H=V.HEADS, dh=D // V.HEADS,
                                                scale=(D // V.HEADS) ** -0.5, **out))
+        elif step.kind == "rollout":
+            prog.add_attn_rollout(step.name, dict(qkv=self._ptr(step.src),
+                                                  r_in=self._ptr(step.res) if step.res else None,
+                                                  r_out=self._ptr(step.dst), B=b, T=self.T, Tq=step.extra["Tq"],
+                                                  H=V.HEADS, dh=D // V.HEADS, scale=(D // V.HEADS) ** -0.5,
+                                                  ldr=self.ldr))
+        elif step.kind == "rollout_map":
+            out = self.outputs[self._slot] if self.outputs else self.logits
+            prog.add_rollout_map(step.name, dict(r=self._ptr(step.src), top=_lib.ptr(self.top1_slot(self._slot)),
+                                                 out=_lib.ptr(out), B=b, T=self.T, ldr=self.ldr, ldo=out.shape[1]))
         elif step.kind == "fc":
             prog.add_fc_mfma(step.name, dict(xb=self._ptr("CLS"), wp=_lib.ptr(self.head_wp),
                                              bias=_lib.ptr(self.head_b), out=self.output_ptr(), B=b, F=D,

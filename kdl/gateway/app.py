@@ -8,6 +8,8 @@ of the model version's gallery, nearest first: the similar signature of the mode
 ``POST /explain {"url": ...}`` -> ``{"label": ..., "score": ..., "heatmap": [[...], ...]}`` (the predicted
 class and its Grad-CAM map over the model's last feature map, h rows of w values in 0..1: the explain
 signature of the mode; upsampling and colouring are the client's).
+``POST /attention {"url": ...}`` -> the same three fields from a ViT version's attention signature of
+the mode: the map is the 14 x 14 attention rollout of the class token.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -201,8 +203,19 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             return grpc_fail(e)
         return jsonify({"neighbors": process_similar_response(pb_result)[0]})
 
+    attention_sig = {"bytes": ("attention_bytes", "image_bytes"), "raw": ("attention_image", "images")}.get(
+        cfg.mode, ("attention", "images"))
+
+    @app.route("/attention", methods=["POST"])
+    def attention():
+        return heatmap_answer(attention_sig)
+
     @app.route("/explain", methods=["POST"])
     def explain():
+        return heatmap_answer(explain_sig)
+
+    def heatmap_answer(sig):
+        """/explain and /attention: one image through a heatmap signature -> label, score, heatmap."""
         body = request.get_json(silent=True)
         if not isinstance(body, dict) or not isinstance(body.get("url"), str):
             return fail(400, 'request body must be JSON {"url": "<image url>"}')
@@ -211,7 +224,7 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except LookupError as e:
             return fail(502, str(e))
         try:
-            req = make_request(uint8_input(img), cfg.model_name, explain_sig[0], explain_sig[1])
+            req = make_request(uint8_input(img), cfg.model_name, sig[0], sig[1])
             pb_result = next_stub().Predict(req, timeout=cfg.timeout)
         except grpc.RpcError as e:
             return grpc_fail(e)

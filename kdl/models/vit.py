@@ -126,6 +126,33 @@ def vit_forward(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
+def vit_rollout(p, x_u8_nhwc: torch.Tensor) -> tuple:
+    """fp32 oracle of the attention-rollout heatmap (Abnar & Zuidema 2020): uint8 NHWC [B,224,224,3] ->
+    (class int32 [B], softmax score fp32 [B], heat fp32 [B,14,14]). Per layer P_h = softmax(Q_h K_h^T /
+    sqrt(dh)), A^ = (mean_h P_h + I) / 2 (rows sum to 1), R_1 = A^_1, R_l = A^_l R_(l-1); the map is row 0
+    of R_12 without the class token's own column, divided by its largest value."""
+    x = embed(p, preprocess(x_u8_nhwc))
+    B, N, D = x.shape
+    eye = torch.eye(N, dtype=x.dtype, device=x.device)
+    r = None
+    for i in range(DEPTH):
+        L = _layer(i)
+        h = F.layer_norm(x, (DIM,), p[f"{L}.ln_1.weight"], p[f"{L}.ln_1.bias"], LN_EPS)
+        qkv = h @ p[f"{L}.self_attention.in_proj_weight"].t() + p[f"{L}.self_attention.in_proj_bias"]
+        q, k, _ = qkv.view(B, N, 3, HEADS, D // HEADS).permute(2, 0, 3, 1, 4)
+        a = (torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(D // HEADS), dim=-1).mean(dim=1) + eye) / 2
+        r = a if r is None else a @ r
+        x = encoder_layer(p, i, x)
+    feat = F.layer_norm(x[:, 0], (DIM,), p["encoder.ln.weight"], p["encoder.ln.bias"], LN_EPS)
+    logits = feat @ p["heads.head.weight"].t() + p["heads.head.bias"]
+    cls = logits.argmax(dim=1)
+    score = torch.softmax(logits, dim=1).gather(1, cls[:, None])[:, 0]
+    heat = r[:, 0, 1:]
+    heat = (heat / heat.amax(dim=1, keepdim=True)).reshape(B, INPUT_SIZE // PATCH, INPUT_SIZE // PATCH)
+    return cls.to(torch.int32), score.float(), heat.float()
+
+
+@torch.no_grad()
 def activation_amax(p, x_u8_nhwc: torch.Tensor) -> list[dict[str, float]]:
     """Calibration for the fp8 engine: per encoder layer, the max |value| of the four
     tensors that feed fp8 GEMMs (ln_1 out -> QKV, attention out -> out_proj,

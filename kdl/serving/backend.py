@@ -82,6 +82,8 @@ class SignatureInfo:
     # explain signatures (serving/explain.py): (h, w) of the Grad-CAM map; a row is the predicted
     # class, its score and h*w map values; () for every other signature
     explain: tuple = ()
+    # attention signatures (serving/rollout.py): the map of ``explain`` is ViT's attention rollout
+    rollout: bool = False
 
     def output_specs(self) -> tuple:
         return self.outputs or ((self.output_key, P.DT_FLOAT, self.output_shape),)
@@ -162,6 +164,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         add_similar_signatures(src, path, similar_top_k)
     from .explain import add_signatures as add_explain_signatures
     add_explain_signatures(src, path)
+    from .rollout import add_signatures as add_attention_signatures
+    add_attention_signatures(src, path)
     return src
 
 
@@ -428,6 +432,8 @@ class GPUExecutor(_Executor):
             tk = dict(similar=Similar(device_gallery(src, dev), r.similar_k, src.similar_metric))
         if r.explain:                                          # the explain runner: rows of 2 + h*w words
             tk = dict(explain=True)
+        if r.rollout:                                          # the attention runner: the same rows from rollout
+            tk = dict(rollout=True)
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -622,7 +628,8 @@ class CPUExecutor(_Executor):
         if src.family != "xception" or self.runner.embed or self.runner.explain_hw:
             from ..engine import registry
             info = registry.get(src.family)
-            self.oracle = (info.cam_oracle if self.runner.explain_hw else
+            self.oracle = (info.rollout_oracle if self.runner.attention else
+                           info.cam_oracle if self.runner.explain_hw else
                            info.feature_oracle if self.runner.embed else info.oracle)
 
     def staging_ptr(self, slot: int = 0) -> int:
@@ -632,6 +639,7 @@ class CPUExecutor(_Executor):
         x = self.staging[:n_real]
         src = self.runner.source
         if self.runner.explain_hw:         # the explain runner: autograd through the family's own head
+                                           # (the attention runner: the family's fp32 rollout)
             from .explain import pack_rows
             kw = dict(head=src.head) if src.family == "xception" and src.head is not None else {}
             k, score, heat = self.oracle(src.params, x, **kw)
@@ -695,7 +703,9 @@ class SignatureRunner:
     similar = False     # the engines end in the similar step and rows are 2K words (SimilarRunner)
     similar_k = 0
     explain = False     # the engines end in the class-map step and rows are 2 + h*w words (ExplainRunner)
-    explain_hw = ()     # (h, w) of an explain runner's map, on any device
+    explain_hw = ()     # (h, w) of an explain or attention runner's map, on any device
+    rollout = False     # the engines carry the rollout steps and rows are 2 + h*w words (RolloutRunner)
+    attention = False   # an attention runner, on any device
 
     @property
     def out_cols(self) -> int:
@@ -875,13 +885,24 @@ class ExplainRunner(SignatureRunner):
 
     def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
         self.explain_hw = tuple(sig.explain)
-        self.explain = bool(devices)
+        self.explain = bool(devices) and not self.attention
         self._null = not devices and cfg.device == "null"
         super().__init__(sig, source, cfg, devices)
 
     def _run(self, n: int, submit) -> np.ndarray:
         rows = super()._run(n, submit)
         return np.zeros_like(rows) if self._null else rows
+
+
+class RolloutRunner(ExplainRunner):
+    """The ``attention`` signature: ExplainRunner's rows with ViT's attention-rollout map in them
+    (serving/rollout.py). GPU executors build their engines with ``rollout=True``; the CPU executor
+    packs the family's ``rollout_oracle`` answer; the null device's rows are zeroed."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.attention = True
+        self.rollout = bool(devices)
+        super().__init__(sig, source, cfg, devices)
 
 
 class Servable:
@@ -915,8 +936,17 @@ class Servable:
                 from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
                 from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
                 from .explain import EXPLAIN_BYTES_SIGNATURE, EXPLAIN_IMAGE_SIGNATURE, EXPLAIN_SIGNATURE
+                from .rollout import ATTENTION_BYTES_SIGNATURE, ATTENTION_IMAGE_SIGNATURE, ATTENTION_SIGNATURE
                 from .similar import SIMILAR_BYTES_SIGNATURE, SIMILAR_IMAGE_SIGNATURE, SIMILAR_SIGNATURE
-                if sig_name == EXPLAIN_SIGNATURE:
+                if sig_name == ATTENTION_SIGNATURE:
+                    r = RolloutRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == ATTENTION_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(ATTENTION_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == ATTENTION_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(ATTENTION_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == EXPLAIN_SIGNATURE:
                     r = ExplainRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 elif sig_name == EXPLAIN_IMAGE_SIGNATURE:
                     r = ImageRunner(self.signatures[sig_name], self.runner(EXPLAIN_SIGNATURE), self._devices,
@@ -970,7 +1000,7 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # a wrapper (serving_image / serving_bytes, the classify_*, embed_*, similar_* and explain_* pairs) has no batcher
+        # a wrapper (serving_image / serving_bytes, the classify_*, embed_*, similar_*, explain_* and attention_* pairs) has no batcher
         # of its own: it feeds its inner runner's, so that is where its work shows
         def batcher(r):
             return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)

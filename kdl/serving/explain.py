@@ -41,25 +41,32 @@ def add_signatures(src, path=None) -> None:
     """Give a loaded ModelSource its three explain signatures (beside the existing ones), when its
     family has a ``cam_oracle``."""
     from ..engine import registry
-    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
-    from .jpeg import BYTES_SIGNATURE
-    from .resize import IMAGE_SIGNATURE
     info = registry.get(src.family)
     if info.cam_oracle is None:
         return
-    h, w = info.map_size
+    add_map_signatures(src, EXPLAIN_SIGNATURES, info.map_size)
+
+
+def add_map_signatures(src, names, hw, rollout: bool = False) -> None:
+    """The trio ``names`` = (uint8 pixels, any-size image, encoded file) of a heatmap method with an
+    h x w map, beside the source's existing signatures. ``rollout`` marks the attention signatures
+    (serving/rollout.py); rows, responses and bodies are the same for both methods."""
+    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
+    from .jpeg import BYTES_SIGNATURE
+    from .resize import IMAGE_SIGNATURE
+    h, w = hw
     S = src.input_size
     outs = (("classes", P.DT_STRING, (-1, 1)), ("scores", P.DT_FLOAT, (-1, 1)), ("heatmap", P.DT_FLOAT, (-1, h, w)))
-    like = {EXPLAIN_SIGNATURE: NATIVE_SIGNATURE, EXPLAIN_IMAGE_SIGNATURE: IMAGE_SIGNATURE,
-            EXPLAIN_BYTES_SIGNATURE: BYTES_SIGNATURE}
+    like = dict(zip(names, (NATIVE_SIGNATURE, IMAGE_SIGNATURE, BYTES_SIGNATURE)))
     for name, base in like.items():
         b = src.signatures.get(base)
         if b is None or name in src.signatures:
             continue
         key = b.input_key if b.input_dtype != P.DT_FLOAT else NATIVE_INPUT_KEY
-        shape = b.input_shape if name != EXPLAIN_SIGNATURE else (-1, S, S, 3)
+        shape = b.input_shape if name != names[0] else (-1, S, S, 3)
+        kw = dict(rollout=True) if rollout else {}
         src.signatures[name] = SignatureInfo(name, key, b.input_dtype, "classes", input_shape=shape,
-                                             output_shape=(-1, 1), outputs=outs, explain=(h, w))
+                                             output_shape=(-1, 1), outputs=outs, explain=(h, w), **kw)
 
 
 def explain_outputs(s, sig, rows) -> tuple:
@@ -67,7 +74,7 @@ def explain_outputs(s, sig, rows) -> tuple:
     A class index outside the label list (the null device's rows) is answered as its decimal."""
     from .metrics import METRICS
     classes, scores, heat = unpack_rows(rows, *sig.explain)
-    METRICS.inc("kdl_explain_total", signature=sig.name)
+    METRICS.inc("kdl_attention_total" if sig.rollout else "kdl_explain_total", signature=sig.name)
     lab = s.source.labels
     return [lab[int(c)] if 0 <= int(c) < len(lab) else str(int(c)) for c in classes], scores, heat
 

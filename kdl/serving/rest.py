@@ -9,7 +9,8 @@ Routes (TF-Serving REST semantics):
        (serving_bytes: every value is {"b64": "<base64 of the image file>"})
        (classify signatures: {"classes": [...], "scores": [...]} per instance, or by column)
        (embed signatures: the feature rows, as "predictions" or "outputs")
-       (explain signatures: {"classes": [label], "scores": [score], "heatmap": [[...]]} per instance, or by column)
+       (explain and attention signatures: {"classes": [label], "scores": [score], "heatmap": [[...]]} per instance,
+        or by column)
   POST /v1/models/<name>[/versions/<v>|/labels/<l>]:classify
        {"signature_name"?, "examples": [{"image/encoded": {"b64": ...}}, ...]}
                                                 -> {"results": [[["label", score], ...], ...]}
