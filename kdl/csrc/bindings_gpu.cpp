@@ -243,6 +243,15 @@ RolloutMapArgs rollout_map_args(const py::dict& d) {
   a.B = I(d, "B"); a.T = I(d, "T"); a.ldr = I(d, "ldr"); a.ldo = I(d, "ldo");
   return a;
 }
+HeatOverlayArgs heat_overlay_args(const py::dict& d) {
+  HeatOverlayArgs a{};
+  a.inp = P<const uint8_t>(d, "inp"); a.out = P<float>(d, "out"); a.tab = P<const uint8_t>(d, "tab");
+  a.xb = P<const int32_t>(d, "xb"); a.xk = P<const int32_t>(d, "xk"); a.yb = P<const int32_t>(d, "yb");
+  a.yk = P<const int32_t>(d, "yk"); a.h_xb = P<const int32_t>(d, "h_xb"); a.h_yb = P<const int32_t>(d, "h_yb");
+  a.B = I(d, "B"); a.S = I(d, "S"); a.h = I(d, "h"); a.w = I(d, "w"); a.ldo = I(d, "ldo");
+  a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.a = I(d, "a"); a.blend = I(d, "blend");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -381,6 +390,14 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(rollout_map(a, S(s)), "rollout_map");
   });
+  // rendered heatmap overlays (kernels/overlay.hip): d = the HeatOverlayArgs fields; h_xb / h_yb are HOST addresses
+  m.def("heat_overlay", [](py::dict d, uintptr_t s) {
+    const auto a = heat_overlay_args(d);
+    py::gil_scoped_release nogil;
+    chk(heat_overlay(a, S(s)), "heat_overlay");
+  });
+  m.attr("OVERLAY_MAX_S") = int(kOverlayMaxS);
+  m.attr("OVERLAY_MAX_TAPS") = int(kOverlayMaxTaps);
   m.attr("ROLLOUT_MAX_T") = int(kRolloutMaxT);
   m.attr("CLASS_MAP_MAX_F") = int(kClassMapMaxF);
   m.attr("CLASS_MAP_MAX_HW") = int(kClassMapMaxHW);
@@ -728,6 +745,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_rollout_map", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_ROLLOUT_MAP; op.name = name; op.rm = rollout_map_args(d); p.add(op);
+      })
+      .def("add_heat_overlay", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_HEAT_OVERLAY; op.name = name; op.ho = heat_overlay_args(d); p.add(op);
       })
       .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);

@@ -485,6 +485,50 @@ struct RolloutMapArgs {
 };
 hipError_t rollout_map(const RolloutMapArgs& a, hipStream_t s);
 
+// Rendered heatmap overlays (kernels/overlay.hip): behind class_map / rollout_map, one launch paints
+// each image's h x w map over the S x S x 3 uint8 picture the model saw, in integers throughout
+// (kdl/serving/overlay.py overlay_rule is the definition):
+//   q[p]  = rint(min(max(heat[p], 0), 1) * 255), one fp32 multiply, round-half-even, NaN -> 0
+//   u     = q resampled from h x w to S x S as Pillow's Image.resize does on an "L" image: the
+//           horizontal pass, then the vertical one, runtime/resample.h's arithmetic (22-bit
+//           coefficients, a uint8 intermediate, accumulators from 1 << 21) over the tables
+//           resample_coeffs(w, S, filter) / resample_coeffs(h, S, filter)
+//   c     = tab[u] (256 x 3 uint8, any colour table)
+//   a_p   = a (blend 0, flat) or (a * u + 127) / 255 (blend 1, heat-weighted)
+//   out   = (img * (256 - a_p) + c * a_p + 128) >> 8 per byte
+// heat is read from the image's own output row, out[b][2 .. 2 + h*w) (ClassMapArgs' layout), and the
+// picture's S*S*3 bytes are written behind it from word 2 + h*w on. Nothing else is written: words
+// 0 .. 2 + h*w of a row, the pad bytes of the picture's last word, the words past it up to ldo and
+// rows >= B stay as they were. Nothing outside [inp, inp + B*S*S*3) is read of the input, whose
+// images sit at any byte alignment (it is read as aligned dwords, by bytes at its two ends).
+// Launches are bit-identical. inp / out / tab / xb / xk / yb / yk / h_xb / h_yb null, out or a
+// device table (tab, xb, xk, yb, yk) not 16-byte aligned, B outside 1..65535, h < 1, w < 1, h*w >
+// kClassMapMaxHW, S < max(h, w), S > kOverlayMaxS, ldo < 2 + h*w + ceil(S*S*3 / 4), a outside
+// 0..256, blend not 0 or 1, xks / yks outside 1..kOverlayMaxTaps, and bounds tables (checked from
+// the host copies h_xb / h_yb, as resample.hip checks its own) whose taps leave the map, step
+// back, or need more than kOverlayMaxRows map rows for one band of kOverlayBand output rows (no
+// upscale does) are hipErrorInvalidValue, and nothing is launched.
+constexpr int kOverlayMaxS = 1024;
+constexpr int kOverlayMaxTaps = 8;
+constexpr int kOverlayBand = 8;
+constexpr int kOverlayMaxRows = 16;
+struct HeatOverlayArgs {
+  const uint8_t* inp;     // [B][S][S][3] uint8, packed
+  float* out;             // [B][ldo] words: class, score, h*w heat values (read), the picture (written)
+  const uint8_t* tab;     // 256 x 3 colour table
+  const int32_t* xb;      // device: bounds [S][2] of the columns, {first map column, taps}
+  const int32_t* xk;      // device: coefficients [S][xks]
+  const int32_t* yb;      // device: the same of the rows
+  const int32_t* yk;      // device: [S][yks]
+  const int32_t* h_xb;    // HOST copies of the bounds (checked here, never followed on the device)
+  const int32_t* h_yb;
+  int B, S, h, w, ldo;
+  int xks, yks;           // taps per column / row of the tables
+  int a;                  // round(alpha * 256), 0..256
+  int blend;              // 0 flat, 1 weighted by the heat
+};
+hipError_t heat_overlay(const HeatOverlayArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

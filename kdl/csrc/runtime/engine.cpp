@@ -36,6 +36,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_CLASS_MAP: return class_map(op.cm, s);
     case OP_ATTN_ROLLOUT: return attn_rollout(op.ar, s);
     case OP_ROLLOUT_MAP: return rollout_map(op.rm, s);
+    case OP_HEAT_OVERLAY: return heat_overlay(op.ho, s);
   }
   return hipErrorInvalidValue;
 }

@@ -66,6 +66,35 @@ def pack_explain(classes, scores, heat):
     return rows
 
 
+def overlay_words(S: int) -> int:
+    """32-bit words that hold the S x S x 3 picture bytes of an overlay row."""
+    return (S * S * 3 + 3) // 4
+
+
+def unpack_overlay(rows, h: int, w: int, S: int) -> tuple:
+    """Packed overlay rows [n, 2 + h*w + ceil(S*S*3/4)] (a torch tensor or numpy array of 32-bit words)
+    -> (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], pictures uint8 [n, S, S, 3])."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    assert a.ndim == 2 and a.shape[1] == 2 + h * w + overlay_words(S), (a.shape, h, w, S)
+    pics = np.ascontiguousarray(a[:, 2 + h * w:]).view(np.uint8)[:, :S * S * 3].reshape(-1, S, S, 3).copy()
+    return unpack_explain(a[:, :2 + h * w], h, w) + (pics,)
+
+
+def pack_overlay(classes, scores, heat, pictures):
+    """The inverse of ``unpack_overlay``: numpy rows of fp32 words (the pad bytes of the last word 0).
+    The picture bytes are copied as bytes, never through a float."""
+    import numpy as np
+    pics = np.ascontiguousarray(pictures, dtype=np.uint8)
+    n, S = pics.shape[0], pics.shape[1]
+    front = pack_explain(classes, scores, heat)
+    rows = np.zeros((n, front.shape[1] + overlay_words(S)), dtype=np.float32)
+    rows[:, :front.shape[1]] = front
+    rows.view(np.uint8)[:, 4 * front.shape[1]:4 * front.shape[1] + S * S * 3] = pics.reshape(n, -1)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -82,11 +111,28 @@ class Similar:
     metric: str = "cosine"
 
 
+@dataclass(frozen=True)
+class Overlay:
+    """Rendered overlay outputs of an ``explain`` / ``rollout`` engine (``EngineBase(overlay=...)``): the
+    heatmap upsampled to the input size with ``filter`` ("bilinear" | "bicubic", Pillow's), coloured
+    through ``colormap`` ("jet" | "hot" | "gray") and blended onto the input picture with ``alpha``
+    (0..1), ``blend`` "flat" or weighted by the "heat". kdl/serving/overlay.py defines the rule."""
+    colormap: str = "jet"
+    alpha: float = 0.5
+    blend: str = "heat"
+    filter: str = "bilinear"
+
+
 class EngineBase:
     model_name = "model"
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
-                 explain: bool = False, rollout: bool = False):
+                 explain: bool = False, rollout: bool = False, overlay: Overlay | None = None):
+        if overlay is not None:      # before anything touches the device
+            if not (explain or rollout):
+                raise ValueError("overlay paints a heatmap: it needs explain=True or rollout=True")
+            from ..serving.overlay import check
+            check(overlay)
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -132,6 +178,10 @@ class EngineBase:
         if rollout and (topk or embed or similar is not None or explain):
             raise ValueError("rollout, explain, similar, embed and topk all replace the output rows: set one of them")
         self.rollout = bool(rollout)
+        # rendered overlays: None = the rows end with the map; an ``Overlay`` = the rows also carry the
+        # S x S x 3 picture bytes, written by one more step behind the map's (_enable_overlay)
+        self.overlay: Overlay | None = overlay
+        self._overlay_tabs: dict = {}                 # overlay only: device tables and their host copies
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -328,6 +378,48 @@ class EngineBase:
         self.steps.append(Step("top1", "top1", src="logits"))
         self.steps.append(Step("explain", "class_map", src=src))
 
+    # ---------------------------------------------------------------- rendered overlays
+    def _enable_overlay(self, h: int, w: int) -> None:
+        """Called by a family's constructor behind ``_enable_explain`` / ``_enable_rollout``. With
+        ``overlay`` the output rows grow to 2 + h*w + ceil(S*S*3/4) words: ``class_map`` / ``rollout_map``
+        take ``ldo`` and write the front of the wider row unchanged, and one more step "overlay"
+        (kernels/overlay.hip) reads the map from the row and the slot's uint8 input (``src="input"``,
+        through ``_ptr``) and writes the picture bytes behind the map (``unpack_overlay``). The input
+        slot is not a planned buffer: a slot's input is only rewritten after that slot's rows were
+        copied out (the executors complete a slot before they refill it), so the last stage of a
+        stage pipeline may read it."""
+        if self.overlay is None:
+            return
+        assert not self.inputs, "overlay is set at construction, before input slots exist"
+        from ..serving import overlay as O
+        lib = _lib.lib()
+        S = self.inp.shape[1]
+        if self.inp.dtype != torch.uint8:
+            raise ValueError("overlay paints the uint8 picture the model saw: a float-input engine has none")
+        if self.inp.shape[2] != S or S < max(h, w) or S > lib.OVERLAY_MAX_S:
+            raise ValueError(f"overlay: a {h} x {w} map on a {tuple(self.inp.shape[1:3])} input; the kernel "
+                             f"upsamples onto square inputs up to {lib.OVERLAY_MAX_S}")
+        ov = self.overlay
+        xb, xk = O.axis_tables(w, S, ov.filter)
+        yb, yk = O.axis_tables(h, S, ov.filter)
+        host = dict(xb=xb, xk=xk, yb=yb, yk=yk, tab=O.colormap_table(ov.colormap))
+        self._overlay_tabs = dict(host=host, dev={k: torch.from_numpy(v).to(self.device) for k, v in host.items()},
+                                  hw=(h, w), a=O.alpha_fixed(ov.alpha), blend=O.BLENDS.index(ov.blend))
+        assert self.logits.shape[1] == 2 + h * w, (self.logits.shape, h, w)
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + overlay_words(S)), dtype=torch.float32,
+                                  device=self.device)
+        self.steps.append(Step("overlay", "overlay", src="input"))
+
+    def _emit_overlay(self, prog, step: Step, b: int) -> None:
+        t = self._overlay_tabs
+        host, dev, (h, w) = t["host"], t["dev"], t["hw"]
+        out = self.outputs[self._slot] if self.outputs else self.logits
+        prog.add_heat_overlay(step.name, dict(
+            inp=self._ptr(step.src), out=_lib.ptr(out), tab=_lib.ptr(dev["tab"]), xb=_lib.ptr(dev["xb"]),
+            xk=_lib.ptr(dev["xk"]), yb=_lib.ptr(dev["yb"]), yk=_lib.ptr(dev["yk"]),
+            h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
+            ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], a=t["a"], blend=t["blend"]))
+
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
         ``rollout`` engine."""
@@ -444,6 +536,8 @@ class EngineBase:
                     self._emit_top1(prog, st, b)
                 elif st.kind == "explain":
                     self._emit_explain(prog, st, b)
+                elif st.kind == "overlay":
+                    self._emit_overlay(prog, st, b)
                 else:
                     self._emit(prog, st, b)
 
@@ -467,7 +561,7 @@ class EngineBase:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
         engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
-        [n, 2 + h*w], see ``unpack_explain``)."""
+        [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

@@ -53,8 +53,8 @@ class EfficientNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
-                 topk: int = 0, embed: str = "", similar=None, explain: bool = False):
-        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
+                 topk: int = 0, embed: str = "", similar=None, explain: bool = False, overlay=None):
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()
@@ -67,6 +67,8 @@ class EfficientNetEngine(EngineBase):
         if self.explain:      # classifier.1.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
             self.cam_w = params["classifier.1.weight"].float().to(torch.bfloat16).contiguous().to(self.device)
         self._enable_explain()
+        if self.explain:
+            self._enable_overlay(*self.cam_source()[1:3])
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -168,6 +170,8 @@ class EfficientNetEngine(EngineBase):
         self.logits = torch.zeros((B, self.classes), dtype=torch.float32, device=dev)
 
     def _ptr(self, name: str) -> int:
+        if name == "input":
+            return self.input_ptr()
         if name == "logits":
             return self.output_ptr()
         return _lib.ptr(self.bufs[self._remap.get(name, name)])

@@ -46,10 +46,11 @@ class ResNetEngine(EngineBase):
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
-                 dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None, explain: bool = False):
+                 dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None, explain: bool = False,
+                 overlay=None):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
-        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind
@@ -66,6 +67,8 @@ class ResNetEngine(EngineBase):
         if self.explain:      # fc.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
             self.cam_w = params["fc.weight"].float().to(self.dtype).contiguous().to(self.device)
         self._enable_explain()
+        if self.explain:
+            self._enable_overlay(*self.cam_source()[1:3])
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

@@ -52,11 +52,12 @@ class ViTEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
-                 topk: int = 0, embed: str = "", similar=None, explain: bool = False, rollout: bool = False):
+                 topk: int = 0, embed: str = "", similar=None, explain: bool = False, rollout: bool = False,
+                 overlay=None):
         if explain:      # before anything touches the device: the class token has no spatial map
             raise ValueError("ViT-B/16 has no spatial feature map in front of its head: no explain outputs "
                              "(its heatmaps are attention rollout: rollout=True)")
-        super().__init__(device, max_batch, buckets, topk, embed, similar, rollout=rollout)
+        super().__init__(device, max_batch, buckets, topk, embed, similar, rollout=rollout, overlay=overlay)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"
@@ -77,6 +78,8 @@ class ViTEngine(EngineBase):
         self._enable_embed()
         self._enable_similar()
         self._enable_rollout()
+        if self.rollout:
+            self._enable_overlay(self.size // V.PATCH, self.size // V.PATCH)
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -206,6 +209,8 @@ class ViTEngine(EngineBase):
         self.steps.append(Step("rollout_map", "rollout_map", src=self._r_last))
 
     def _ptr(self, name: str) -> int:
+        if name == "input":
+            return self.input_ptr()
         return _lib.ptr(self.bufs[self._remap.get(name, name)])
 
     def embed_source(self) -> tuple:

@@ -45,8 +45,8 @@ class XceptionEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
                  tune_file: str | Path | None = None, topk: int = 0, embed: str = "", similar=None,
-                 explain: bool = False):
-        super().__init__(device, max_batch, buckets, topk, embed, similar, explain)
+                 explain: bool = False, overlay=None):
+        super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
@@ -72,6 +72,8 @@ class XceptionEngine(EngineBase):
         self._enable_embed()
         self._enable_similar()
         self._enable_explain()
+        if self.explain:
+            self._enable_overlay(*self.cam_source()[1:3])
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

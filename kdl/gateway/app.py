@@ -7,9 +7,12 @@ model's head: the embed signature of the mode).
 of the model version's gallery, nearest first: the similar signature of the mode).
 ``POST /explain {"url": ...}`` -> ``{"label": ..., "score": ..., "heatmap": [[...], ...]}`` (the predicted
 class and its Grad-CAM map over the model's last feature map, h rows of w values in 0..1: the explain
-signature of the mode; upsampling and colouring are the client's).
+signature of the mode; ``/overlay`` renders the map).
 ``POST /attention {"url": ...}`` -> the same three fields from a ViT version's attention signature of
 the mode: the map is the 14 x 14 attention rollout of the class token.
+``POST /overlay {"url": ...}`` -> ``image/png``: the picture the model saw with the heatmap of whatever
+method the version has painted on it (the overlay signature of the mode), label and score in the headers
+``X-KDL-Label`` / ``X-KDL-Score``; with ``"format": "json"`` -> ``{"label", "score", "heatmap", "png": "<base64>"}``.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -43,8 +46,8 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_embed_response, process_explain_response, process_response,
-                     process_similar_response)
+                     process_embed_response, process_explain_response, process_overlay_response,
+                     process_response, process_similar_response, png_bytes)
 
 
 class GatewayConfig:
@@ -229,6 +232,36 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except grpc.RpcError as e:
             return grpc_fail(e)
         return jsonify(process_explain_response(pb_result)[0])
+
+    overlay_sig = {"bytes": ("overlay_bytes", "image_bytes"), "raw": ("overlay_image", "images")}.get(
+        cfg.mode, ("overlay", "images"))
+
+    @app.route("/overlay", methods=["POST"])
+    def overlay():
+        """One image through the overlay signature -> the rendered picture as a PNG (or, with
+        "format": "json", label, score, heatmap and the PNG in base64)."""
+        body = request.get_json(silent=True)
+        if (not isinstance(body, dict) or not isinstance(body.get("url"), str)
+                or body.get("format", "png") not in ("png", "json")):
+            return fail(400, 'request body must be JSON {"url": "<image url>", "format"?: "png" | "json"}')
+        try:
+            img = load(body["url"])
+        except LookupError as e:
+            return fail(502, str(e))
+        try:
+            req = make_request(uint8_input(img), cfg.model_name, overlay_sig[0], overlay_sig[1])
+            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
+        except grpc.RpcError as e:
+            return grpc_fail(e)
+        ans = process_overlay_response(pb_result)[0]
+        png = png_bytes(ans.pop("picture"))
+        if body.get("format") == "json":
+            import base64
+            return jsonify(dict(ans, png=base64.b64encode(png).decode()))
+        resp = app.response_class(png, mimetype="image/png")
+        resp.headers["X-KDL-Label"] = ans["label"]
+        resp.headers["X-KDL-Score"] = repr(ans["score"])
+        return resp
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

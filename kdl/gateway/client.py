@@ -101,3 +101,32 @@ def process_explain_response(pb_result) -> list[dict]:
     maps = np.asarray(hm.float_val, dtype=np.float32).reshape(n, h, w)
     return [{"label": cl.string_val[i].decode(), "score": float(sc.float_val[i]),
              "heatmap": [[float(v) for v in row] for row in maps[i]]} for i in range(n)]
+
+
+def process_overlay_response(pb_result) -> list[dict]:
+    """An overlay signature's PredictResponse (explain's three outputs and ``overlay`` DT_UINT8
+    [n, S, S, 3] as ``tensor_content``) -> per image ``{"label", "score", "heatmap", "picture"}``, the
+    picture a uint8 array [S, S, 3]."""
+    out = process_explain_response(pb_result)
+    t = pb_result.outputs["overlay"]
+    shape = [d.size for d in t.tensor_shape.dim]
+    pics = np.frombuffer(t.tensor_content, dtype=np.uint8).reshape(shape)
+    for o, p in zip(out, pics):
+        o["picture"] = p
+    return out
+
+
+def png_bytes(picture) -> bytes:
+    """uint8 [H, W, 3] -> an 8-bit RGB PNG file, written with zlib and struct alone (the gateway's
+    ``bytes`` mode needs no image library)."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(picture, dtype=np.uint8)
+    H, W, _ = a.shape
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    rows = np.concatenate([np.zeros((H, 1), dtype=np.uint8), a.reshape(H, W * 3)], axis=1)   # filter type 0 per row
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+            + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))

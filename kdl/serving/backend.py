@@ -84,6 +84,9 @@ class SignatureInfo:
     explain: tuple = ()
     # attention signatures (serving/rollout.py): the map of ``explain`` is ViT's attention rollout
     rollout: bool = False
+    # overlay signatures (serving/overlay.py): S, the side of the picture that follows the map in a
+    # row (``explain`` and ``rollout`` say which map); 0 for every other signature
+    overlay: int = 0
 
     def output_specs(self) -> tuple:
         return self.outputs or ((self.output_key, P.DT_FLOAT, self.output_shape),)
@@ -116,6 +119,8 @@ class ModelSource:
     similar_metric: str = "cosine"
     gallery_device: dict = field(default_factory=dict)
     gallery_lock: object = field(default_factory=threading.Lock)
+    # rendered overlays (serving/overlay.py): the version's engine.base.Overlay (None = no overlay signatures)
+    overlay: object = None
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -136,14 +141,17 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      classify_top_k: int | None = None, embedding_normalize: str | None = None,
-                     similar_top_k: int | None = None, gallery: bool = True) -> ModelSource:
+                     similar_top_k: int | None = None, gallery: bool = True,
+                     overlay_colormap: str | None = None, overlay_alpha: float | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
     (the server's --classify_top_k) overrides the version's classify K (serving/classify.py),
     ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py),
     ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py);
-    ``gallery=False`` leaves the version's gallery files alone (the tool that writes them)."""
+    ``gallery=False`` leaves the version's gallery files alone (the tool that writes them);
+    ``overlay_colormap`` / ``overlay_alpha`` (--overlay_colormap, --overlay_alpha) override the
+    version's "overlay" block (serving/overlay.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -166,6 +174,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     add_explain_signatures(src, path)
     from .rollout import add_signatures as add_attention_signatures
     add_attention_signatures(src, path)
+    from .overlay import add_signatures as add_overlay_signatures
+    add_overlay_signatures(src, path, overlay_colormap, overlay_alpha)
     return src
 
 
@@ -434,6 +444,8 @@ class GPUExecutor(_Executor):
             tk = dict(explain=True)
         if r.rollout:                                          # the attention runner: the same rows from rollout
             tk = dict(rollout=True)
+        if r.overlay_size:                                     # the overlay runner: the picture behind the map
+            tk = dict(tk, overlay=src.overlay)
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -643,6 +655,12 @@ class CPUExecutor(_Executor):
             from .explain import pack_rows
             kw = dict(head=src.head) if src.family == "xception" and src.head is not None else {}
             k, score, heat = self.oracle(src.params, x, **kw)
+            if self.runner.overlay_size:   # the overlay runner: the rule on the very tensor the oracle was fed
+                from .overlay import overlay_rule, pack_rows as pack_overlay_rows
+                pics = [overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat.numpy())]
+                self.out[:n_real] = torch.from_numpy(pack_overlay_rows(k.numpy(), score.numpy(), heat.numpy(),
+                                                                       np.stack(pics)))
+                return self.out.data_ptr()
             self.out[:n_real] = torch.from_numpy(pack_rows(k.numpy(), score.numpy(), heat.numpy()))
             return self.out.data_ptr()
         if self.runner.embed:              # the embed runner: fp32 feature rows, normalised by the same rule
@@ -706,12 +724,13 @@ class SignatureRunner:
     explain_hw = ()     # (h, w) of an explain or attention runner's map, on any device
     rollout = False     # the engines carry the rollout steps and rows are 2 + h*w words (RolloutRunner)
     attention = False   # an attention runner, on any device
+    overlay_size = 0    # S of an overlay runner: rows also carry ceil(S*S*3/4) words of picture (OverlayRunner)
 
     @property
     def out_cols(self) -> int:
         """32-bit words per result row, from the executor to the waiting handler."""
         if self.explain_hw:
-            return 2 + self.explain_hw[0] * self.explain_hw[1]
+            return 2 + self.explain_hw[0] * self.explain_hw[1] + (self.overlay_size * self.overlay_size * 3 + 3) // 4
         if self.similar:
             return 2 * self.similar_k
         if self.embed:
@@ -905,6 +924,20 @@ class RolloutRunner(ExplainRunner):
         super().__init__(sig, source, cfg, devices)
 
 
+class OverlayRunner(ExplainRunner):
+    """The ``overlay`` signature: the rows of the family's heatmap runner (ExplainRunner's Grad-CAM, or
+    RolloutRunner's attention rollout where the signature says ``rollout``) with the rendered picture
+    behind the map, 2 + h*w + ceil(S*S*3/4) words (serving/overlay.py). GPU executors build their
+    engines with ``explain=True`` or ``rollout=True`` and ``overlay=``; the CPU executor packs the
+    oracle's map and ``overlay_rule`` of the tensor it fed the oracle; the null device's rows are zeroed."""
+
+    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
+        self.overlay_size = int(sig.overlay)
+        self.attention = bool(sig.rollout)
+        self.rollout = bool(devices) and self.attention
+        super().__init__(sig, source, cfg, devices)
+
+
 class Servable:
     """One loaded model version (all its signatures)."""
 
@@ -937,8 +970,17 @@ class Servable:
                 from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
                 from .explain import EXPLAIN_BYTES_SIGNATURE, EXPLAIN_IMAGE_SIGNATURE, EXPLAIN_SIGNATURE
                 from .rollout import ATTENTION_BYTES_SIGNATURE, ATTENTION_IMAGE_SIGNATURE, ATTENTION_SIGNATURE
+                from .overlay import OVERLAY_BYTES_SIGNATURE, OVERLAY_IMAGE_SIGNATURE, OVERLAY_SIGNATURE
                 from .similar import SIMILAR_BYTES_SIGNATURE, SIMILAR_IMAGE_SIGNATURE, SIMILAR_SIGNATURE
-                if sig_name == ATTENTION_SIGNATURE:
+                if sig_name == OVERLAY_SIGNATURE:
+                    r = OverlayRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                elif sig_name == OVERLAY_IMAGE_SIGNATURE:
+                    r = ImageRunner(self.signatures[sig_name], self.runner(OVERLAY_SIGNATURE), self._devices,
+                                    self.source.preprocess)
+                elif sig_name == OVERLAY_BYTES_SIGNATURE:
+                    r = BytesRunner(self.signatures[sig_name], self.runner(OVERLAY_SIGNATURE), self._devices,
+                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                elif sig_name == ATTENTION_SIGNATURE:
                     r = RolloutRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
                 elif sig_name == ATTENTION_IMAGE_SIGNATURE:
                     r = ImageRunner(self.signatures[sig_name], self.runner(ATTENTION_SIGNATURE), self._devices,
@@ -1000,7 +1042,7 @@ class Servable:
         beside a working one leaves the device alive."""
         with self._lock:
             runners = list(self.runners.values())
-        # a wrapper (serving_image / serving_bytes, the classify_*, embed_*, similar_*, explain_* and attention_* pairs) has no batcher
+        # a wrapper (serving_image / serving_bytes, the classify_*, embed_*, similar_*, explain_*, attention_* and overlay_* pairs) has no batcher
         # of its own: it feeds its inner runner's, so that is where its work shows
         def batcher(r):
             return getattr(r, "batcher", None) or getattr(getattr(r, "inner", None), "batcher", None)

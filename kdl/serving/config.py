@@ -98,6 +98,10 @@ class ServerConfig:
     # K of the similar signatures (serving/similar.py); None = the model version's own
     # "similar": {"top_k": K}, else 5. 1..32, clipped to the gallery's row count
     similar_top_k: int | None = None
+    # colour table and strength of the overlay signatures (serving/overlay.py); None = the model
+    # version's own "overlay": {"colormap": ..., "alpha": ...}, else jet and 0.5
+    overlay_colormap: str | None = None
+    overlay_alpha: float | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -203,6 +207,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "are (Keras pooling=\"avg\"), l2 = each divided by its L2 norm; overrides the model version's "
                          "\"embedding\": {\"normalize\": ...} (env KDL_EMBEDDING_NORMALIZE, default: the version's, "
                          "else none)")
+    ap.add_argument("--overlay_colormap", choices=["jet", "hot", "gray"], default=None,
+                    help="colour table of the overlay / overlay_image / overlay_bytes signatures; overrides the model "
+                         "version's \"overlay\": {\"colormap\": ...} (env KDL_OVERLAY_COLORMAP, default: the "
+                         "version's, else jet)")
+    ap.add_argument("--overlay_alpha", type=float, default=None,
+                    help="strength of the heat on the picture of the overlay signatures, 0..1; overrides the model "
+                         "version's \"overlay\": {\"alpha\": ...} (env KDL_OVERLAY_ALPHA, default: the version's, "
+                         "else 0.5)")
     ap.add_argument("--similar_top_k", type=int, default=None,
                     help="gallery items and scores per image of the similar / similar_image / similar_bytes "
                          "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
@@ -270,6 +282,9 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         embedding_normalize=a.embedding_normalize or env.get("KDL_EMBEDDING_NORMALIZE") or None,
                         similar_top_k=(a.similar_top_k if a.similar_top_k is not None
                                        else int(env["KDL_SIMILAR_TOP_K"]) if env.get("KDL_SIMILAR_TOP_K") else None),
+                        overlay_colormap=a.overlay_colormap or env.get("KDL_OVERLAY_COLORMAP") or None,
+                        overlay_alpha=(a.overlay_alpha if a.overlay_alpha is not None
+                                       else float(env["KDL_OVERLAY_ALPHA"]) if env.get("KDL_OVERLAY_ALPHA") else None),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

@@ -178,7 +178,10 @@ class Servicer:
             t1 = time.perf_counter()
             logits = runner.predict(buf, n, _deadline_us(context))
             t2 = time.perf_counter()
-            if sig.explain:             # explain / attention signatures: label, score and heatmap from the packed rows
+            if sig.overlay:             # overlay signatures: explain's three outputs and the rendered picture
+                from .overlay import overlay_response
+                out = overlay_response(s, sig, logits, req["output_filter"])
+            elif sig.explain:           # explain / attention signatures: label, score and heatmap from the packed rows
                 from .explain import explain_response
                 out = explain_response(s, sig, logits, req["output_filter"])
             elif sig.top_k:             # classify / similar signatures: strings + scores from the packed rows

@@ -39,7 +39,8 @@ def latest_version_source(cfg: ServerConfig):
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
     return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess,
                             classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize,
-                            similar_top_k=cfg.similar_top_k)
+                            similar_top_k=cfg.similar_top_k, overlay_colormap=cfg.overlay_colormap,
+                            overlay_alpha=cfg.overlay_alpha)
 
 
 class ModelManager:
@@ -78,7 +79,8 @@ class ModelManager:
             src = load_version_dir(self.base / str(v), synthetic=self.cfg.synthetic, preprocess=self.cfg.preprocess,
                                    classify_top_k=self.cfg.classify_top_k,
                                    embedding_normalize=self.cfg.embedding_normalize,
-                                   similar_top_k=self.cfg.similar_top_k)
+                                   similar_top_k=self.cfg.similar_top_k,
+                                   overlay_colormap=self.cfg.overlay_colormap, overlay_alpha=self.cfg.overlay_alpha)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

@@ -127,7 +127,7 @@ class NativeFront:
         runner = s.runner(sig_name)
         sig = runner.sig
         if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or sig.top_k or sig.explain or not runner.healthy():
-            return                              # serving_image / serving_bytes / classify* / explain* / attention*: slow path
+            return                              # serving_image / serving_bytes / classify* / explain* / attention* / overlay*: slow path
         u8 = None
         if self.f32_exact_u8 and sig.input_dtype == P.DT_FLOAT and NATIVE_SIGNATURE in s.signatures:
             u8 = s.runner(NATIVE_SIGNATURE).batcher

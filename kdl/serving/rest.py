@@ -10,7 +10,7 @@ Routes (TF-Serving REST semantics):
        (classify signatures: {"classes": [...], "scores": [...]} per instance, or by column)
        (embed signatures: the feature rows, as "predictions" or "outputs")
        (explain and attention signatures: {"classes": [label], "scores": [score], "heatmap": [[...]]} per instance,
-        or by column)
+        or by column; overlay signatures add "overlay": the S x S x 3 picture as nested integer lists)
   POST /v1/models/<name>[/versions/<v>|/labels/<l>]:classify
        {"signature_name"?, "examples": [{"image/encoded": {"b64": ...}}, ...]}
                                                 -> {"results": [[["label", score], ...], ...]}
@@ -150,6 +150,9 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
         def _body(s, sig, out, rows: bool) -> dict:
             """The :predict answer: logits, a classify signature's two named outputs, or an explain
             signature's three."""
+            if sig.overlay:
+                from .overlay import overlay_body
+                return overlay_body(s, sig, out, rows)
             if sig.explain:
                 from .explain import explain_body
                 return explain_body(s, sig, out, rows)
