@@ -125,6 +125,9 @@ class Overlay:
 
 class EngineBase:
     model_name = "model"
+    # tail step kind -> the method that emits it; every other kind is the family's (_emit)
+    TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
+                     "explain": "_emit_explain", "overlay": "_emit_overlay"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
                  explain: bool = False, rollout: bool = False, overlay: Overlay | None = None):
@@ -133,6 +136,8 @@ class EngineBase:
                 raise ValueError("overlay paints a heatmap: it needs explain=True or rollout=True")
             from ..serving.overlay import check
             check(overlay)
+        if sum(map(bool, (topk, embed, similar is not None, explain, rollout))) > 1:
+            raise ValueError("rollout, explain, similar, embed and topk all replace the output rows: set one of them")
         self.device = torch.device(device)
         self.max_batch = max_batch
         self.buckets = sorted(set(buckets or [max_batch]))
@@ -154,29 +159,21 @@ class EngineBase:
         # the pooled features in front of the head into the output rows (_enable_embed)
         if embed not in EMBED_MODES:
             raise ValueError(f"embed must be one of {EMBED_MODES}, got {embed!r}")
-        if embed and topk:
-            raise ValueError("embed and topk both replace the output rows: set one of them")
         self.embed = embed
         self._embed_step: Step | None = None
         # gallery search outputs: None = the output is the fp32 logits; a ``Similar`` = two more
         # steps write the K nearest gallery rows of each image's features (_enable_similar)
-        if similar is not None and (topk or embed):
-            raise ValueError("similar, embed and topk all replace the output rows: set one of them")
         self.similar: Similar | None = similar
         self.feature_slots: list[torch.Tensor] = []   # similar only: per-slot fp32 features [max_batch, F]
         self._similar_work: list[torch.Tensor] = []   # similar only: per-slot gallery_topk workspace
         # Grad-CAM outputs: False = the output is the fp32 logits; True = two more steps write the
         # predicted class, its score and the class's heatmap over the last feature map (_enable_explain)
-        if explain and (topk or embed or similar is not None):
-            raise ValueError("explain, similar, embed and topk all replace the output rows: set one of them")
         self.explain = bool(explain)
         self.top1_slots: list[torch.Tensor] = []      # explain only: per-slot [max_batch, 2] class and score
         self._cam_alpha: list[torch.Tensor] = []      # explain only: per-slot class_map workspace [max_batch, F]
         # attention-rollout outputs (ViT): False = the output is the fp32 logits; True = one more step
         # beside every layer's attention, then "top1" and "rollout_map" behind the head write the
-        # predicted class, its score and the rollout heatmap, explain's row layout (ViTEngine._enable_rollout)
-        if rollout and (topk or embed or similar is not None or explain):
-            raise ValueError("rollout, explain, similar, embed and topk all replace the output rows: set one of them")
+        # predicted class, its score and the rollout heatmap, explain's row layout (ViTEngine._enable_heatmap)
         self.rollout = bool(rollout)
         # rendered overlays: None = the rows end with the map; an ``Overlay`` = the rows also carry the
         # S x S x 3 picture bytes, written by one more step behind the map's (_enable_overlay)
@@ -188,11 +185,17 @@ class EngineBase:
         """Device pointer of the input slot the program being built reads."""
         return _lib.ptr(self.inputs[self._slot] if self.inputs else self.inp)
 
+    def _rows_replaced(self) -> bool:
+        """The head writes per-slot logits, not the output rows: a tail step writes those."""
+        return bool(self.topk or self.embed or self.similar or self.explain or self.rollout)
+
+    def _out_rows(self) -> torch.Tensor:
+        """The output rows of the slot the program being built writes."""
+        return self.outputs[self._slot] if self.outputs else self.logits
+
     def output_ptr(self) -> int:
         """Device pointer of the logits buffer the program being built writes."""
-        if self.topk or self.embed or self.similar or self.explain or self.rollout:
-            return _lib.ptr(self._logit_slot(self._slot))
-        return _lib.ptr(self.outputs[self._slot] if self.outputs else self.logits)
+        return _lib.ptr(self._logit_slot(self._slot) if self._rows_replaced() else self._out_rows())
 
     def slot_logits(self, slot: int) -> torch.Tensor:
         """Output buffer of a slot: fp32 logits, the packed top-k rows of a ``topk`` engine, the
@@ -200,9 +203,29 @@ class EngineBase:
         packed heatmap rows of an ``explain`` or ``rollout`` engine."""
         return self.outputs[slot] if self.outputs else self.logits
 
+    # ---------------------------------------------------------------- output tails
+    def _enable_outputs(self) -> None:
+        """Called once by a family's constructor when ``self.logits`` [max_batch, classes] exists:
+        appends the tail steps of the one row-replacing mode that is set, and behind a heatmap the
+        overlay step."""
+        self._enable_topk()
+        self._enable_embed()
+        self._enable_similar()
+        hw = self._enable_heatmap()
+        if hw:
+            self._enable_overlay(*hw)
+
+    def _enable_heatmap(self) -> tuple:
+        """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
+        ViT overrides it with attention rollout."""
+        if not self.explain:
+            return ()
+        self._enable_explain()
+        return self.cam_source()[1:3]
+
     # ---------------------------------------------------------------- classification outputs
     def _enable_topk(self) -> None:
-        """Called by a family's constructor once ``self.logits`` [max_batch, classes] exists. With
+        """Called by ``_enable_outputs``. With
         ``topk = K`` (clipped to the class count) the head keeps writing that buffer, a last
         step of kind "topk" (kernels/classify.hip) reads it, and ``self.logits`` -- the output
         the executor copies to the host and ``forward`` returns -- becomes [max_batch, 2K]
@@ -226,16 +249,14 @@ class EngineBase:
         return self.logit_slots[slot]
 
     def _emit_topk(self, prog, step: Step, b: int) -> None:
-        lg = self._logit_slot(self._slot)
-        out = self.outputs[self._slot] if self.outputs else self.logits
+        lg, out = self._logit_slot(self._slot), self._out_rows()
         prog.add_softmax_topk(step.name, dict(x=_lib.ptr(lg), out=_lib.ptr(out), B=b, NC=lg.shape[1],
                                               K=self.topk, ldx=lg.shape[1]))
 
     def last_logits(self, slot: int = 0) -> torch.Tensor:
         """fp32 logits [max_batch, classes] of the last forward in ``slot``, with or without
         ``topk`` / ``embed`` / ``similar`` / ``explain`` / ``rollout``."""
-        return (self._logit_slot(slot) if (self.topk or self.embed or self.similar or self.explain or self.rollout)
-                else self.slot_logits(slot))
+        return self._logit_slot(slot) if self._rows_replaced() else self.slot_logits(slot)
 
     # ---------------------------------------------------------------- embedding outputs
     def embed_source(self) -> tuple:
@@ -250,7 +271,7 @@ class EngineBase:
         return self.embed_source()[3]
 
     def _enable_embed(self) -> None:
-        """Called by a family's constructor next to ``_enable_topk``. With ``embed`` "raw" or "l2"
+        """Called by ``_enable_outputs``. With ``embed`` "raw" or "l2"
         the head keeps writing the per-slot logits, a last step of kind "embed" (kernels/embed.hip)
         pools ``embed_source()`` and ``self.logits`` -- the output the executor copies to the host
         and ``forward`` returns -- becomes [max_batch, F] fp32: the mean over the pixels, for "l2"
@@ -273,13 +294,13 @@ class EngineBase:
         if self.similar is not None:       # the query rows of the "similar" step
             out, norm = self.feature_slot(self._slot), int(self.similar.metric == "cosine")
         else:
-            out, norm = (self.outputs[self._slot] if self.outputs else self.logits), int(self.embed == "l2")
+            out, norm = self._out_rows(), int(self.embed == "l2")
         prog.add_embed_rows(step.name, dict(x=self._ptr(step.src), out=_lib.ptr(out), B=b, HW=hw, F=F, ldx=ldx,
                                             ldo=out.shape[1], dt=dt, norm=norm))
 
     # ---------------------------------------------------------------- gallery search outputs
     def _enable_similar(self) -> None:
-        """Called by a family's constructor next to ``_enable_embed``. With ``similar`` the head keeps
+        """Called by ``_enable_outputs``. With ``similar`` the head keeps
         writing the per-slot logits, a step "embed_rows" pools ``embed_source()`` into a per-slot
         fp32 feature buffer [max_batch, F] (L2-normalised for "cosine"), and a last step of kind
         "similar" (kernels/similar.hip) scores those rows against the gallery. ``self.logits`` --
@@ -331,8 +352,7 @@ class EngineBase:
         return self._similar_work[slot]
 
     def _emit_similar(self, prog, step: Step, b: int) -> None:
-        g, feat = self.similar.gallery, self.feature_slot(self._slot)
-        out = self.outputs[self._slot] if self.outputs else self.logits
+        g, feat, out = self.similar.gallery, self.feature_slot(self._slot), self._out_rows()
         prog.add_gallery_topk(step.name, dict(q=_lib.ptr(feat), g=_lib.ptr(g), out=_lib.ptr(out),
                                               work=_lib.ptr(self._similar_workspace(self._slot)), B=b,
                                               N=g.shape[0], F=feat.shape[1], K=self.similar_k,
@@ -351,7 +371,7 @@ class EngineBase:
         raise NotImplementedError
 
     def _enable_explain(self) -> None:
-        """Called by a family's constructor next to ``_enable_similar``. With ``explain`` the head
+        """Called by ``_enable_heatmap``. With ``explain`` the head
         keeps writing the per-slot logits, a step "top1" (softmax_topk, K = 1) fills a per-slot
         [max_batch, 2] buffer with the predicted class and its score, and a last step "class_map"
         (kernels/explain.hip) writes the output rows. ``self.logits`` -- the output the executor
@@ -360,8 +380,6 @@ class EngineBase:
         divided by its maximum (``unpack_explain``). The class-map step names the map in ``src``, so
         the stage pipeline's buffer renaming reaches it through ``_ptr``; what else it reads (the
         logits through "top1", the head's weights and partials) belongs to the head's own stage."""
-        if not self.explain:
-            return
         assert not self.inputs, "explain is set at construction, before input slots exist"
         lib = _lib.lib()
         src, h, w, _, F, _ = self.cam_source()
@@ -380,7 +398,7 @@ class EngineBase:
 
     # ---------------------------------------------------------------- rendered overlays
     def _enable_overlay(self, h: int, w: int) -> None:
-        """Called by a family's constructor behind ``_enable_explain`` / ``_enable_rollout``. With
+        """Called by ``_enable_outputs`` behind the heatmap tail. With
         ``overlay`` the output rows grow to 2 + h*w + ceil(S*S*3/4) words: ``class_map`` / ``rollout_map``
         take ``ldo`` and write the front of the wider row unchanged, and one more step "overlay"
         (kernels/overlay.hip) reads the map from the row and the slot's uint8 input (``src="input"``,
@@ -412,8 +430,7 @@ class EngineBase:
 
     def _emit_overlay(self, prog, step: Step, b: int) -> None:
         t = self._overlay_tabs
-        host, dev, (h, w) = t["host"], t["dev"], t["hw"]
-        out = self.outputs[self._slot] if self.outputs else self.logits
+        host, dev, (h, w), out = t["host"], t["dev"], t["hw"], self._out_rows()
         prog.add_heat_overlay(step.name, dict(
             inp=self._ptr(step.src), out=_lib.ptr(out), tab=_lib.ptr(dev["tab"]), xb=_lib.ptr(dev["xb"]),
             xk=_lib.ptr(dev["xk"]), yb=_lib.ptr(dev["yb"]), yk=_lib.ptr(dev["yk"]),
@@ -436,8 +453,7 @@ class EngineBase:
 
     def _emit_explain(self, prog, step: Step, b: int) -> None:
         _, h, w, ldx, F, dt = self.cam_source()
-        top = self.top1_slot(self._slot)
-        out = self.outputs[self._slot] if self.outputs else self.logits
+        top, out = self.top1_slot(self._slot), self._out_rows()
         prog.add_class_map(step.name, dict(x=self._ptr(step.src), top=_lib.ptr(top),
                                            alpha=_lib.ptr(self._cam_alpha[self._slot]), out=_lib.ptr(out), B=b,
                                            HW=h * w, F=F, ldx=ldx, ldo=out.shape[1], dt=dt, norm=1,
@@ -526,20 +542,10 @@ class EngineBase:
         with ctx:
             for st, m in zip(steps, maps):
                 self._remap = m
-                if st.kind == "topk":
-                    self._emit_topk(prog, st, b)
-                elif st is self._embed_step:
+                if st is self._embed_step:     # by identity: ViT has its own step of kind "embed"
                     self._emit_embed(prog, st, b)
-                elif st.kind == "similar":
-                    self._emit_similar(prog, st, b)
-                elif st.kind == "top1":
-                    self._emit_top1(prog, st, b)
-                elif st.kind == "explain":
-                    self._emit_explain(prog, st, b)
-                elif st.kind == "overlay":
-                    self._emit_overlay(prog, st, b)
                 else:
-                    self._emit(prog, st, b)
+                    getattr(self, self.TAIL_EMITTERS.get(st.kind, "_emit"))(prog, st, b)
 
     def invalidate(self) -> None:
         self.programs.clear()

@@ -61,14 +61,9 @@ class EfficientNetEngine(EngineBase):
         self.bufsz: dict[str, int] = {}            # buffer -> elements per image (max over uses)
         self._build(params)
         self._alloc()
-        self._enable_topk()
-        self._enable_embed()
-        self._enable_similar()
         if self.explain:      # classifier.1.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
             self.cam_w = params["classifier.1.weight"].float().to(torch.bfloat16).contiguous().to(self.device)
-        self._enable_explain()
-        if self.explain:
-            self._enable_overlay(*self.cam_source()[1:3])
+        self._enable_outputs()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

@@ -61,14 +61,9 @@ class ResNetEngine(EngineBase):
         self.shapes: dict[str, tuple[int, int, int, int]] = {}   # buffer -> (H, W, C, border)
         self._build(params)
         self._alloc()
-        self._enable_topk()
-        self._enable_embed()
-        self._enable_similar()
         if self.explain:      # fc.weight [NC][F] row-major, rounded as the packed MFMA copy (fc_wp) is
             self.cam_w = params["fc.weight"].float().to(self.dtype).contiguous().to(self.device)
-        self._enable_explain()
-        if self.explain:
-            self._enable_overlay(*self.cam_source()[1:3])
+        self._enable_outputs()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

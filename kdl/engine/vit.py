@@ -74,12 +74,7 @@ class ViTEngine(EngineBase):
         self.classes = params["heads.head.bias"].numel()
         self._build(params)
         self._alloc()
-        self._enable_topk()
-        self._enable_embed()
-        self._enable_similar()
-        self._enable_rollout()
-        if self.rollout:
-            self._enable_overlay(self.size // V.PATCH, self.size // V.PATCH)
+        self._enable_outputs()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 
@@ -189,13 +184,13 @@ class ViTEngine(EngineBase):
                 self.ld[nm] = self.ldr
         self.logits = torch.zeros((B, self.classes), dtype=torch.float32, device=dev)
 
-    def _enable_rollout(self) -> None:
-        """With ``rollout`` the head keeps writing the per-slot logits, "top1" (softmax_topk, K = 1)
+    def _enable_heatmap(self) -> tuple:
+        """ViT's heatmap tail is attention rollout. With ``rollout`` the head keeps writing the per-slot logits, "top1" (softmax_topk, K = 1)
         fills the per-slot [max_batch, 2] class and score, and a last step "rollout_map" writes the
         output rows from row 0 of the last R, which it names in ``src``. ``self.logits`` becomes
         [max_batch, 2 + 14 * 14] fp32 words (``unpack_explain`` with h = w = 14)."""
         if not self.rollout:
-            return
+            return ()
         assert not self.inputs, "rollout is set at construction, before input slots exist"
         lib = _lib.lib()
         if self.classes > lib.TOPK_MAX_NC:
@@ -207,6 +202,7 @@ class ViTEngine(EngineBase):
         self.logits = torch.zeros((self.max_batch, 2 + self.np), dtype=torch.float32, device=self.device)
         self.steps.append(Step("top1", "top1", src="logits"))
         self.steps.append(Step("rollout_map", "rollout_map", src=self._r_last))
+        return self.size // V.PATCH, self.size // V.PATCH
 
     def _ptr(self, name: str) -> int:
         if name == "input":
@@ -283,7 +279,7 @@ class ViTEngine(EngineBase):
                                                   H=V.HEADS, dh=D // V.HEADS, scale=(D // V.HEADS) ** -0.5,
                                                   ldr=self.ldr))
         elif step.kind == "rollout_map":
-            out = self.outputs[self._slot] if self.outputs else self.logits
+            out = self._out_rows()
             prog.add_rollout_map(step.name, dict(r=self._ptr(step.src), top=_lib.ptr(self.top1_slot(self._slot)),
                                                  out=_lib.ptr(out), B=b, T=self.T, ldr=self.ldr, ldo=out.shape[1]))
         elif step.kind == "fc":

@@ -68,12 +68,7 @@ class XceptionEngine(EngineBase):
         self.shapes: dict[str, tuple[int, int, int]] = {}  # buffer -> (H, W, C) per image
         self._build(params)
         self._alloc()
-        self._enable_topk()
-        self._enable_embed()
-        self._enable_similar()
-        self._enable_explain()
-        if self.explain:
-            self._enable_overlay(*self.cam_source()[1:3])
+        self._enable_outputs()
         if tune_file and Path(tune_file).exists():
             self.load_tuning(tune_file)
 

@@ -137,17 +137,11 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             return grpc_fail(e)
         return jsonify(process_response(pb_result, cfg.labels, cfg.output_key))
 
-    # the classify / embed signature of each mode; compat and uint8 resize here, as for /predict,
-    # and both send uint8 pixels (these signatures take no f32 input)
-    classify_sig = {"bytes": ("classify_bytes", "image_bytes"), "raw": ("classify_image", "images")}.get(
-        cfg.mode, ("classify", "images"))
-    embed_sig = {"bytes": ("embed_bytes", "image_bytes"), "raw": ("embed_image", "images")}.get(
-        cfg.mode, ("embed", "images"))
-    similar_sig = {"bytes": ("similar_bytes", "image_bytes"), "raw": ("similar_image", "images")}.get(
-        cfg.mode, ("similar", "images"))
-
-    explain_sig = {"bytes": ("explain_bytes", "image_bytes"), "raw": ("explain_image", "images")}.get(
-        cfg.mode, ("explain", "images"))
+    def trio(first: str) -> tuple:
+        """(signature, input key) of a trio for the gateway's mode; compat and uint8 resize here, as for
+        /predict, and both send uint8 pixels (these signatures take no f32 input)."""
+        return {"bytes": (f"{first}_bytes", "image_bytes"), "raw": (f"{first}_image", "images")}.get(
+            cfg.mode, (first, "images"))
 
     def uint8_input(img):
         if cfg.mode == "bytes":
@@ -158,110 +152,61 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             return pp.apply_spec_pil(img, cfg.preprocess, pp.TARGET[0])[None]
         return pp.to_uint8(img)[None]
 
-    @app.route("/classify", methods=["POST"])
-    def classify():
+    def one_image(first: str, shape, formats=None):
+        """One image URL through the trio ``first`` -> shape(PredictResponse, body), or the error answer."""
         body = request.get_json(silent=True)
-        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
+        ok = isinstance(body, dict) and isinstance(body.get("url"), str)
+        if formats:
+            if not ok or body.get("format", formats[0]) not in formats:
+                return fail(400, 'request body must be JSON {"url": "<image url>", "format"?: "png" | "json"}')
+        elif not ok:
             return fail(400, 'request body must be JSON {"url": "<image url>"}')
         try:
             img = load(body["url"])
         except LookupError as e:
             return fail(502, str(e))
         try:
-            req = make_request(uint8_input(img), cfg.model_name, classify_sig[0], classify_sig[1])
+            req = make_request(uint8_input(img), cfg.model_name, *trio(first))
             pb_result = next_stub().Predict(req, timeout=cfg.timeout)
         except grpc.RpcError as e:
             return grpc_fail(e)
-        return jsonify(process_classify_response(pb_result)[0])
+        return shape(pb_result, body)
+
+    @app.route("/classify", methods=["POST"])
+    def classify():
+        return one_image("classify", lambda pb, _: jsonify(process_classify_response(pb)[0]))
 
     @app.route("/embed", methods=["POST"])
     def embed():
-        body = request.get_json(silent=True)
-        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
-            return fail(400, 'request body must be JSON {"url": "<image url>"}')
-        try:
-            img = load(body["url"])
-        except LookupError as e:
-            return fail(502, str(e))
-        try:
-            req = make_request(uint8_input(img), cfg.model_name, embed_sig[0], embed_sig[1])
-            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
-        except grpc.RpcError as e:
-            return grpc_fail(e)
-        return jsonify({"embedding": process_embed_response(pb_result)[0]})
+        return one_image("embed", lambda pb, _: jsonify({"embedding": process_embed_response(pb)[0]}))
 
     @app.route("/similar", methods=["POST"])
     def similar():
-        body = request.get_json(silent=True)
-        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
-            return fail(400, 'request body must be JSON {"url": "<image url>"}')
-        try:
-            img = load(body["url"])
-        except LookupError as e:
-            return fail(502, str(e))
-        try:
-            req = make_request(uint8_input(img), cfg.model_name, similar_sig[0], similar_sig[1])
-            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
-        except grpc.RpcError as e:
-            return grpc_fail(e)
-        return jsonify({"neighbors": process_similar_response(pb_result)[0]})
-
-    attention_sig = {"bytes": ("attention_bytes", "image_bytes"), "raw": ("attention_image", "images")}.get(
-        cfg.mode, ("attention", "images"))
-
-    @app.route("/attention", methods=["POST"])
-    def attention():
-        return heatmap_answer(attention_sig)
+        return one_image("similar", lambda pb, _: jsonify({"neighbors": process_similar_response(pb)[0]}))
 
     @app.route("/explain", methods=["POST"])
     def explain():
-        return heatmap_answer(explain_sig)
+        return one_image("explain", lambda pb, _: jsonify(process_explain_response(pb)[0]))
 
-    def heatmap_answer(sig):
-        """/explain and /attention: one image through a heatmap signature -> label, score, heatmap."""
-        body = request.get_json(silent=True)
-        if not isinstance(body, dict) or not isinstance(body.get("url"), str):
-            return fail(400, 'request body must be JSON {"url": "<image url>"}')
-        try:
-            img = load(body["url"])
-        except LookupError as e:
-            return fail(502, str(e))
-        try:
-            req = make_request(uint8_input(img), cfg.model_name, sig[0], sig[1])
-            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
-        except grpc.RpcError as e:
-            return grpc_fail(e)
-        return jsonify(process_explain_response(pb_result)[0])
-
-    overlay_sig = {"bytes": ("overlay_bytes", "image_bytes"), "raw": ("overlay_image", "images")}.get(
-        cfg.mode, ("overlay", "images"))
+    @app.route("/attention", methods=["POST"])
+    def attention():
+        return one_image("attention", lambda pb, _: jsonify(process_explain_response(pb)[0]))
 
     @app.route("/overlay", methods=["POST"])
     def overlay():
         """One image through the overlay signature -> the rendered picture as a PNG (or, with
         "format": "json", label, score, heatmap and the PNG in base64)."""
-        body = request.get_json(silent=True)
-        if (not isinstance(body, dict) or not isinstance(body.get("url"), str)
-                or body.get("format", "png") not in ("png", "json")):
-            return fail(400, 'request body must be JSON {"url": "<image url>", "format"?: "png" | "json"}')
-        try:
-            img = load(body["url"])
-        except LookupError as e:
-            return fail(502, str(e))
-        try:
-            req = make_request(uint8_input(img), cfg.model_name, overlay_sig[0], overlay_sig[1])
-            pb_result = next_stub().Predict(req, timeout=cfg.timeout)
-        except grpc.RpcError as e:
-            return grpc_fail(e)
-        ans = process_overlay_response(pb_result)[0]
-        png = png_bytes(ans.pop("picture"))
-        if body.get("format") == "json":
-            import base64
-            return jsonify(dict(ans, png=base64.b64encode(png).decode()))
-        resp = app.response_class(png, mimetype="image/png")
-        resp.headers["X-KDL-Label"] = ans["label"]
-        resp.headers["X-KDL-Score"] = repr(ans["score"])
-        return resp
+        def shape(pb_result, body):
+            ans = process_overlay_response(pb_result)[0]
+            png = png_bytes(ans.pop("picture"))
+            if body.get("format") == "json":
+                import base64
+                return jsonify(dict(ans, png=base64.b64encode(png).decode()))
+            resp = app.response_class(png, mimetype="image/png")
+            resp.headers["X-KDL-Label"] = ans["label"]
+            resp.headers["X-KDL-Score"] = repr(ans["score"])
+            return resp
+        return one_image("overlay", shape, formats=("png", "json"))
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

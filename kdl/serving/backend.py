@@ -43,14 +43,14 @@ from ..ops import _lib
 from . import protos as P
 from .config import ServerConfig
 from .metrics import BATCH_BUCKETS, METRICS
+from . import outputs as O
 from .jpeg import BYTES_SIGNATURE, BytesRunner, bytes_signature
+from .outputs import NATIVE_INPUT_KEY, NATIVE_SIGNATURE
 from .resize import IMAGE_SIGNATURE, ImageRunner
 
 log = logging.getLogger("kdl.serving")
 
 IMG = X.INPUT_SIZE
-NATIVE_SIGNATURE = "serving_uint8"     # native fast path: uint8 HWC images (4x fewer bytes)
-NATIVE_INPUT_KEY = "images"
 
 
 class ServingError(Exception):
@@ -163,19 +163,14 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
-    from .classify import add_signatures
-    add_signatures(src, path, classify_top_k)
-    from .embed import add_signatures as add_embed_signatures
-    add_embed_signatures(src, path, embedding_normalize)
+    from . import classify, embed, explain, overlay, rollout, similar
+    classify.add_signatures(src, path, classify_top_k)
+    embed.add_signatures(src, path, embedding_normalize)
     if gallery:
-        from .similar import add_signatures as add_similar_signatures
-        add_similar_signatures(src, path, similar_top_k)
-    from .explain import add_signatures as add_explain_signatures
-    add_explain_signatures(src, path)
-    from .rollout import add_signatures as add_attention_signatures
-    add_attention_signatures(src, path)
-    from .overlay import add_signatures as add_overlay_signatures
-    add_overlay_signatures(src, path, overlay_colormap, overlay_alpha)
+        similar.add_signatures(src, path, similar_top_k)
+    explain.add_signatures(src, path)
+    rollout.add_signatures(src, path)
+    overlay.add_signatures(src, path, overlay_colormap, overlay_alpha)
     return src
 
 
@@ -433,19 +428,7 @@ class GPUExecutor(_Executor):
         cap = bool(self.engine_kwargs.get("graph", True))      # --graph off: eager launches
         in_kind = "u8" if r.sig.input_dtype == P.DT_UINT8 else "f32"
         dev = f"cuda:{self.device}"
-        tk = dict(topk=r.topk) if r.topk else {}               # the classify runner: rows of 2K words
-        if r.embed:
-            tk = dict(embed=r.embed)                           # the embed runner: rows of F floats
-        if r.similar:                                          # the similar runner: rows of 2K words
-            from ..engine.base import Similar
-            from .similar import device_gallery
-            tk = dict(similar=Similar(device_gallery(src, dev), r.similar_k, src.similar_metric))
-        if r.explain:                                          # the explain runner: rows of 2 + h*w words
-            tk = dict(explain=True)
-        if r.rollout:                                          # the attention runner: the same rows from rollout
-            tk = dict(rollout=True)
-        if r.overlay_size:                                     # the overlay runner: the picture behind the map
-            tk = dict(tk, overlay=src.overlay)
+        tk = O.engine_kwargs(r.sig, src, dev)                  # the rows come out of the captured program
         def make(b, buckets=None):
             if fam == "xception":
                 from ..engine.xception import XceptionEngine
@@ -636,45 +619,13 @@ class CPUExecutor(_Executor):
         S = src.input_size
         self.staging = torch.zeros((bs, S, S, 3), dtype=torch.uint8 if u8 else torch.float32)
         self.out = torch.zeros((bs, self.runner.out_cols), dtype=torch.float32)
-        self.u8 = u8
-        if src.family != "xception" or self.runner.embed or self.runner.explain_hw:
-            from ..engine import registry
-            info = registry.get(src.family)
-            self.oracle = (info.rollout_oracle if self.runner.attention else
-                           info.cam_oracle if self.runner.explain_hw else
-                           info.feature_oracle if self.runner.embed else info.oracle)
 
     def staging_ptr(self, slot: int = 0) -> int:
         return self.staging.data_ptr()
 
     def execute(self, bucket: int, n_real: int) -> int:
-        x = self.staging[:n_real]
-        src = self.runner.source
-        if self.runner.explain_hw:         # the explain runner: autograd through the family's own head
-                                           # (the attention runner: the family's fp32 rollout)
-            from .explain import pack_rows
-            kw = dict(head=src.head) if src.family == "xception" and src.head is not None else {}
-            k, score, heat = self.oracle(src.params, x, **kw)
-            if self.runner.overlay_size:   # the overlay runner: the rule on the very tensor the oracle was fed
-                from .overlay import overlay_rule, pack_rows as pack_overlay_rows
-                pics = [overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat.numpy())]
-                self.out[:n_real] = torch.from_numpy(pack_overlay_rows(k.numpy(), score.numpy(), heat.numpy(),
-                                                                       np.stack(pics)))
-                return self.out.data_ptr()
-            self.out[:n_real] = torch.from_numpy(pack_rows(k.numpy(), score.numpy(), heat.numpy()))
-            return self.out.data_ptr()
-        if self.runner.embed:              # the embed runner: fp32 feature rows, normalised by the same rule
-            rows = self.oracle(src.params, x)
-            if self.runner.embed == "l2":
-                from .embed import l2_rule
-                rows = torch.from_numpy(l2_rule(rows.numpy()))
-            self.out[:n_real] = rows
-            return self.out.data_ptr()
-        if src.family != "xception":
-            self.out[:n_real] = self.oracle(src.params, x)
-            return self.out.data_ptr()
-        x = x.float() / 127.5 - 1.0 if self.u8 else x
-        self.out[:n_real] = X.xception_forward(src.params, x, head=src.head)
+        r = self.runner
+        self.out[:n_real] = O.cpu_rows(r.sig, r.source, self.staging[:n_real])
         return self.out.data_ptr()
 
 
@@ -715,30 +666,18 @@ class NullExecutor(_Executor):
 class SignatureRunner:
     """One C++ batcher + the executors serving one signature of one version."""
 
-    topk = 0            # K: the GPU engines end in the top-k step and rows are 2K words (ClassifyRunner)
-    embed = ""          # "raw" / "l2": the engines end in the embed step and rows are F floats (EmbedRunner)
-    embed_dim = 0
-    similar = False     # the engines end in the similar step and rows are 2K words (SimilarRunner)
-    similar_k = 0
-    explain = False     # the engines end in the class-map step and rows are 2 + h*w words (ExplainRunner)
-    explain_hw = ()     # (h, w) of an explain or attention runner's map, on any device
-    rollout = False     # the engines carry the rollout steps and rows are 2 + h*w words (RolloutRunner)
-    attention = False   # an attention runner, on any device
-    overlay_size = 0    # S of an overlay runner: rows also carry ceil(S*S*3/4) words of picture (OverlayRunner)
-
     @property
     def out_cols(self) -> int:
         """32-bit words per result row, from the executor to the waiting handler."""
-        if self.explain_hw:
-            return 2 + self.explain_hw[0] * self.explain_hw[1] + (self.overlay_size * self.overlay_size * 3 + 3) // 4
-        if self.similar:
-            return 2 * self.similar_k
-        if self.embed:
-            return self.embed_dim
-        return 2 * self.topk if self.topk else self.source.classes
+        return O.out_cols(self.sig, self.source, self.gpu)
 
     def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
         self.sig, self.source, self.cfg = sig, source, cfg
+        # the kind of its rows (serving/outputs.py), and who packs them: GPU engines in their
+        # captured programs, or _run on the host from what a CPU / null executor returned
+        self.kind = O.kind_of(sig).name
+        self.gpu = bool(devices)
+        self._null = not devices and cfg.device == "null"
         bp = cfg.batching
         self.buckets = cfg.rank_buckets()
         dp = cfg.scatter == "rccl" and cfg.dp_rank == 0 and sig.name == cfg.dp_signature
@@ -828,7 +767,7 @@ class SignatureRunner:
             raise ServingError("DEADLINE_EXCEEDED", "deadline exceeded while queued for batching")
         if status != rt.ST_OK:
             raise ServingError("INTERNAL" if status == rt.ST_ERROR else "UNAVAILABLE", f"batch failed (status {status})")
-        return out
+        return out if self.gpu else O.host_rows(self.sig, self.source, out, self._null)
 
     def healthy(self) -> bool:
         return any(ex.healthy and ex.error is None for ex in self.executors)
@@ -839,103 +778,6 @@ class SignatureRunner:
         self.batcher.shutdown()
         for ex in self.executors:
             ex.join(timeout=5)
-
-
-class ClassifyRunner(SignatureRunner):
-    """The ``classify`` signature: like ``serving_uint8``'s runner, but a result row is the packed
-    top-K (K int32 class indices, K fp32 softmax scores: classify.unpack_rows). GPU executors build
-    their engines with ``topk=K``, so the rows come out of the captured program; the CPU and null
-    executors return logits as ever and the rule is applied here in numpy."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.k = sig.top_k
-        self.topk = self.k if devices else 0
-        super().__init__(sig, source, cfg, devices)
-
-    def _run(self, n: int, submit) -> np.ndarray:
-        from .classify import pack_rows, topk_rule
-        rows = super()._run(n, submit)
-        return rows if self.topk else pack_rows(*topk_rule(rows, self.k))
-
-
-class EmbedRunner(SignatureRunner):
-    """The ``embed`` signature: like ``serving_uint8``'s runner, but a result row is the pooled
-    feature vector in front of the head, F fp32 (serving/embed.py). GPU executors build their
-    engines with ``embed="raw"`` or ``"l2"``, so the rows come out of the captured program; the CPU
-    executor returns the family's ``feature_oracle`` rows, normalised in numpy for "l2"; the null
-    executor's rows are F wide."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.embed = sig.embed
-        self.embed_dim = sig.output_shape[1]
-        super().__init__(sig, source, cfg, devices)
-
-
-class SimilarRunner(SignatureRunner):
-    """The ``similar`` signature: like ``serving_uint8``'s runner, but a result row is the packed
-    K nearest gallery rows (K int32 row indices, K fp32 scores: classify.unpack_rows). GPU executors
-    build their engines with ``similar=`` over the version's one device gallery, so the rows come
-    out of the captured program; the CPU and null executors return feature rows as an embed
-    runner's do, and ``similar_rule`` is applied here in numpy."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.k = sig.top_k
-        if devices:
-            self.similar, self.similar_k = True, self.k
-        else:
-            self.embed, self.embed_dim = "raw", source.gallery.shape[1]
-        super().__init__(sig, source, cfg, devices)
-
-    def _run(self, n: int, submit) -> np.ndarray:
-        from .classify import pack_rows
-        from .similar import similar_rule
-        rows = super()._run(n, submit)
-        if self.similar:
-            return rows
-        return pack_rows(*similar_rule(rows, self.source.gallery, self.k, self.source.similar_metric))
-
-
-class ExplainRunner(SignatureRunner):
-    """The ``explain`` signature: like ``serving_uint8``'s runner, but a result row is the predicted
-    class (int32 bits), its score and the class's Grad-CAM map, 2 + h*w words (serving/explain.py).
-    GPU executors build their engines with ``explain=True``, so the rows come out of the captured
-    program; the CPU executor packs the family's ``cam_oracle`` answer the same way; the null
-    device's rows are zeroed here (class 0, score 0, an empty map)."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.explain_hw = tuple(sig.explain)
-        self.explain = bool(devices) and not self.attention
-        self._null = not devices and cfg.device == "null"
-        super().__init__(sig, source, cfg, devices)
-
-    def _run(self, n: int, submit) -> np.ndarray:
-        rows = super()._run(n, submit)
-        return np.zeros_like(rows) if self._null else rows
-
-
-class RolloutRunner(ExplainRunner):
-    """The ``attention`` signature: ExplainRunner's rows with ViT's attention-rollout map in them
-    (serving/rollout.py). GPU executors build their engines with ``rollout=True``; the CPU executor
-    packs the family's ``rollout_oracle`` answer; the null device's rows are zeroed."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.attention = True
-        self.rollout = bool(devices)
-        super().__init__(sig, source, cfg, devices)
-
-
-class OverlayRunner(ExplainRunner):
-    """The ``overlay`` signature: the rows of the family's heatmap runner (ExplainRunner's Grad-CAM, or
-    RolloutRunner's attention rollout where the signature says ``rollout``) with the rendered picture
-    behind the map, 2 + h*w + ceil(S*S*3/4) words (serving/overlay.py). GPU executors build their
-    engines with ``explain=True`` or ``rollout=True`` and ``overlay=``; the CPU executor packs the
-    oracle's map and ``overlay_rule`` of the tensor it fed the oracle; the null device's rows are zeroed."""
-
-    def __init__(self, sig: SignatureInfo, source: ModelSource, cfg: ServerConfig, devices: list[int]):
-        self.overlay_size = int(sig.overlay)
-        self.attention = bool(sig.rollout)
-        self.rollout = bool(devices) and self.attention
-        super().__init__(sig, source, cfg, devices)
 
 
 class Servable:
@@ -966,68 +808,16 @@ class Servable:
                 if sig_name not in self.signatures:
                     raise ServingError("INVALID_ARGUMENT", f"Serving signature name: \"{sig_name}\" not found "
                                        "in signature def")
-                from .classify import CLASSIFY_BYTES_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE, CLASSIFY_SIGNATURE
-                from .embed import EMBED_BYTES_SIGNATURE, EMBED_IMAGE_SIGNATURE, EMBED_SIGNATURE
-                from .explain import EXPLAIN_BYTES_SIGNATURE, EXPLAIN_IMAGE_SIGNATURE, EXPLAIN_SIGNATURE
-                from .rollout import ATTENTION_BYTES_SIGNATURE, ATTENTION_IMAGE_SIGNATURE, ATTENTION_SIGNATURE
-                from .overlay import OVERLAY_BYTES_SIGNATURE, OVERLAY_IMAGE_SIGNATURE, OVERLAY_SIGNATURE
-                from .similar import SIMILAR_BYTES_SIGNATURE, SIMILAR_IMAGE_SIGNATURE, SIMILAR_SIGNATURE
-                if sig_name == OVERLAY_SIGNATURE:
-                    r = OverlayRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == OVERLAY_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(OVERLAY_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == OVERLAY_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(OVERLAY_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == ATTENTION_SIGNATURE:
-                    r = RolloutRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == ATTENTION_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(ATTENTION_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == ATTENTION_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(ATTENTION_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == EXPLAIN_SIGNATURE:
-                    r = ExplainRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == EXPLAIN_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(EXPLAIN_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == EXPLAIN_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(EXPLAIN_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == SIMILAR_SIGNATURE:
-                    r = SimilarRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == SIMILAR_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(SIMILAR_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == SIMILAR_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(SIMILAR_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == EMBED_SIGNATURE:
-                    r = EmbedRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == EMBED_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(EMBED_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == EMBED_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(EMBED_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == CLASSIFY_SIGNATURE:
-                    r = ClassifyRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
-                elif sig_name == CLASSIFY_IMAGE_SIGNATURE:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(CLASSIFY_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == CLASSIFY_BYTES_SIGNATURE:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(CLASSIFY_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
-                elif sig_name == IMAGE_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
-                    r = ImageRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
-                                    self.source.preprocess)
-                elif sig_name == BYTES_SIGNATURE and NATIVE_SIGNATURE in self.signatures:
-                    r = BytesRunner(self.signatures[sig_name], self.runner(NATIVE_SIGNATURE), self._devices,
-                                    self.source.preprocess, entropy=getattr(self._cfg, "jpeg_entropy", "host"))
+                sig, (wrap, first) = self.signatures[sig_name], O.WRAPPED.get(sig_name, (None, None))
+                if wrap is not None and first == NATIVE_SIGNATURE and first not in self.signatures:
+                    wrap = None
+                if wrap is None:
+                    r = SignatureRunner(sig, self.source, self._cfg, self._devices)
+                elif wrap == 0:
+                    r = ImageRunner(sig, self.runner(first), self._devices, self.source.preprocess)
                 else:
-                    r = SignatureRunner(self.signatures[sig_name], self.source, self._cfg, self._devices)
+                    r = BytesRunner(sig, self.runner(first), self._devices, self.source.preprocess,
+                                    entropy=getattr(self._cfg, "jpeg_entropy", "host"))
                 self.runners[sig_name] = r
             return r
 

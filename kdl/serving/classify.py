@@ -16,7 +16,6 @@ carries one encoded image under the feature ``image/encoded`` (``"classify": {"f
 """
 from __future__ import annotations
 
-import json
 from pathlib import Path
 
 import numpy as np
@@ -53,17 +52,11 @@ def unpack_rows(rows: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return np.ascontiguousarray(rows[:, :k]).view(np.int32), np.ascontiguousarray(rows[:, k:])
 
 
-def _meta(path: Path) -> dict:
-    for name in ("kdl_model.json", "synthetic.json"):
-        if (path / name).exists():
-            return json.loads((path / name).read_text())
-    return {}
-
-
 def resolve(path: Path, classes: int, top_k_flag: int | None = None) -> tuple[int, str, list[str]]:
     """(K, tf.Example feature key, labels) of the version in ``path``; ValueError fails the load."""
+    from .outputs import _meta
     path = Path(path)
-    meta = _meta(path)
+    meta, _ = _meta(path)
     spec = meta.get("classify", {})
     if not isinstance(spec, dict):
         raise ValueError(f"{path}: \"classify\" must be an object like {{\"top_k\": 5}}")
@@ -89,23 +82,11 @@ def resolve(path: Path, classes: int, top_k_flag: int | None = None) -> tuple[in
 
 def add_signatures(src, path: Path, top_k_flag: int | None = None) -> None:
     """Give a loaded ModelSource its three classify signatures (beside the existing ones)."""
-    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
-    from .jpeg import BYTES_SIGNATURE
-    from .resize import IMAGE_SIGNATURE
+    from .outputs import add_trio
     k, feature, labels = resolve(path, src.classes, top_k_flag)
     src.labels, src.classify_k, src.classify_feature = labels, k, feature
-    S = src.input_size
     outs = (("classes", P.DT_STRING, (-1, k)), ("scores", P.DT_FLOAT, (-1, k)))
-    like = {CLASSIFY_SIGNATURE: NATIVE_SIGNATURE, CLASSIFY_IMAGE_SIGNATURE: IMAGE_SIGNATURE,
-            CLASSIFY_BYTES_SIGNATURE: BYTES_SIGNATURE}
-    for name, base in like.items():
-        b = src.signatures.get(base)
-        if b is None or name in src.signatures:
-            continue
-        key = b.input_key if b.input_dtype != P.DT_FLOAT else NATIVE_INPUT_KEY
-        shape = b.input_shape if name != CLASSIFY_SIGNATURE else (-1, S, S, 3)
-        src.signatures[name] = SignatureInfo(name, key, b.input_dtype, "classes", input_shape=shape,
-                                             output_shape=(-1, k), outputs=outs, top_k=k)
+    add_trio(src, CLASSIFY_SIGNATURES, "classes", (-1, k), outputs=outs, top_k=k)
 
 
 def labels_of(src, classes: np.ndarray) -> list[list[str]]:

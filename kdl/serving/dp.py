@@ -157,6 +157,11 @@ class _FollowerRunner:
         self.exec_group = None
         self.faults = FaultInjector("")
 
+    @property
+    def out_cols(self) -> int:
+        from . import outputs as O
+        return O.out_cols(self.sig, self.source, gpu=True)
+
 
 def _comms(rank: int, world: int, device: int):
     """Two RCCL communicators (scatter, gather) on fresh unique ids from rank 0."""

@@ -13,12 +13,10 @@ Normalisation comes from the version's ``kdl_model.json`` / ``synthetic.json`` k
 """
 from __future__ import annotations
 
-import json
 from pathlib import Path
 
 import numpy as np
 
-from . import protos as P
 
 EMBED_SIGNATURE = "embed"
 EMBED_IMAGE_SIGNATURE = "embed_image"
@@ -36,15 +34,9 @@ def l2_rule(rows: np.ndarray) -> np.ndarray:
     return (x / n).astype(np.float32)
 
 
-def _meta(path: Path) -> tuple[dict, str]:
-    for name in ("kdl_model.json", "synthetic.json"):
-        if (path / name).exists():
-            return json.loads((path / name).read_text()), name
-    return {}, "kdl_model.json"
-
-
 def resolve(path: Path, normalize_flag: str | None = None) -> str:
     """"none" or "l2" for the version in ``path``; ValueError (naming the file) fails the load."""
+    from .outputs import _meta
     path = Path(path)
     meta, name = _meta(path)
     spec = meta.get("embedding", {})
@@ -63,20 +55,8 @@ def resolve(path: Path, normalize_flag: str | None = None) -> str:
 def add_signatures(src, path: Path, normalize_flag: str | None = None) -> None:
     """Give a loaded ModelSource its three embed signatures (beside the existing ones)."""
     from ..engine import registry
-    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
-    from .jpeg import BYTES_SIGNATURE
-    from .resize import IMAGE_SIGNATURE
+    from .outputs import add_trio
     norm = resolve(path, normalize_flag)
     F = src.head.features if src.head is not None else registry.get(src.family).features
     src.embed_normalize, src.embed_dim = norm, F
-    S = src.input_size
-    like = {EMBED_SIGNATURE: NATIVE_SIGNATURE, EMBED_IMAGE_SIGNATURE: IMAGE_SIGNATURE,
-            EMBED_BYTES_SIGNATURE: BYTES_SIGNATURE}
-    for name, base in like.items():
-        b = src.signatures.get(base)
-        if b is None or name in src.signatures:
-            continue
-        key = b.input_key if b.input_dtype != P.DT_FLOAT else NATIVE_INPUT_KEY
-        shape = b.input_shape if name != EMBED_SIGNATURE else (-1, S, S, 3)
-        src.signatures[name] = SignatureInfo(name, key, b.input_dtype, OUTPUT_KEY, input_shape=shape,
-                                             output_shape=(-1, F), embed=ENGINE_MODE[norm])
+    add_trio(src, EMBED_SIGNATURES, OUTPUT_KEY, (-1, F), embed=ENGINE_MODE[norm])

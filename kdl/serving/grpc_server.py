@@ -20,7 +20,8 @@ import numpy as np
 from ..ops import _lib
 from . import protos as P
 from .backend import NATIVE_SIGNATURE, ServingError
-from .classify import CLASSIFY_BYTES_SIGNATURE, examples_to_images, labels_of, unpack_rows
+from . import outputs as O
+from .classify import CLASSIFY_BYTES_SIGNATURE, examples_to_images
 from .metrics import METRICS
 from .model_repo import ModelManager
 
@@ -178,18 +179,7 @@ class Servicer:
             t1 = time.perf_counter()
             logits = runner.predict(buf, n, _deadline_us(context))
             t2 = time.perf_counter()
-            if sig.overlay:             # overlay signatures: explain's three outputs and the rendered picture
-                from .overlay import overlay_response
-                out = overlay_response(s, sig, logits, req["output_filter"])
-            elif sig.explain:           # explain / attention signatures: label, score and heatmap from the packed rows
-                from .explain import explain_response
-                out = explain_response(s, sig, logits, req["output_filter"])
-            elif sig.top_k:             # classify / similar signatures: strings + scores from the packed rows
-                out = classify_response(s, sig, logits, req["output_filter"])
-            else:
-                out = rt.build_predict_response([(sig.output_key, logits)], s.name, s.version, sig_name)
-            if sig.embed:               # answers built here; the native front-end's learned route counts
-                METRICS.inc("kdl_embed_total", signature=sig.name)      # its own in kdl_requests_total only
+            out = predict_response(s, sig, logits, req["output_filter"])
             # per-request stage trace (SURVEY.md §5 tracing): parse+validate, batcher wait+run, respond
             METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")
             METRICS.observe("kdl_stage_ms", (t2 - t1) * 1e3, stage="batch_and_run")
@@ -296,40 +286,38 @@ class Servicer:
 
 
 def classify_outputs(s, sig, rows) -> tuple[list[list[str]], np.ndarray]:
-    """Packed top-K rows of a classify signature -> (labels [n][K], scores fp32 [n, K]); of a
-    similar signature -> (gallery ids [n][K], scores fp32 [n, K])."""
-    classes, scores = unpack_rows(rows)
-    if sig.similar:
-        from .similar import ids_of
-        METRICS.inc("kdl_similar_total", signature=sig.name)
-        return ids_of(s.source, classes), scores
-    METRICS.inc("kdl_classify_total", signature=sig.name)
-    return labels_of(s.source, classes), scores
+    """Packed top-K rows of a classify signature -> (labels [n][K], scores fp32 [n, K])."""
+    (_, _, labels), (_, _, scores) = O.columns(s.source, sig, rows)
+    return labels, scores
 
 
-def classify_response(s, sig, rows, output_filter) -> bytes:
-    """PredictResponse of a classify signature: ``classes`` DT_STRING [n, K] and ``scores``
-    DT_FLOAT [n, K] (float_val), or the subset ``output_filter`` names. A similar signature's
-    strings are gallery ids under ``ids``."""
-    labels, scores = classify_outputs(s, sig, rows)
-    names = sig.output_key                      # "classes" | "ids"
-    n, k = scores.shape
+def predict_response(s, sig, rows, output_filter) -> bytes:
+    """The PredictResponse of an answered request. A kind with named outputs (serving/outputs.py):
+    every column, or the subset ``output_filter`` names, strings as ``string_val``, floats as
+    ``float_val``, uint8 as ``tensor_content``. The single fp32 output of the logits and embed
+    signatures is built natively (the hot path; the native front-end's learned route counts its
+    own in kdl_requests_total only)."""
+    cols = O.columns(s.source, sig, rows)
+    if cols is None:
+        O.answered(sig)
+        return _lib.rt().build_predict_response([(sig.output_key, rows)], s.name, s.version, sig.name)
     resp = P.PredictResponse()
     resp.model_spec.name = s.name
     resp.model_spec.version.value = s.version
     resp.model_spec.signature_name = sig.name
-    want = list(output_filter) or [names, "scores"]
-    if names in want:
-        t = resp.outputs[names]
-        t.dtype = P.DT_STRING
-        t.string_val.extend(name.encode() for row in labels for name in row)
-    if "scores" in want:
-        t = resp.outputs["scores"]
-        t.dtype = P.DT_FLOAT
-        t.float_val.extend(scores.reshape(-1).tolist())
-    for key in resp.outputs:
-        for d in (n, k):
-            resp.outputs[key].tensor_shape.dim.add(size=d)
+    for key, dtype, values in cols:
+        if output_filter and key not in output_filter:
+            continue
+        t = resp.outputs[key]
+        t.dtype = dtype
+        if dtype == P.DT_STRING:
+            t.string_val.extend(v.encode() for row in values for v in row)
+        elif dtype == P.DT_UINT8:
+            t.tensor_content = values.tobytes()
+        else:
+            t.float_val.extend(values.reshape(-1).tolist())
+        for d in np.shape(values):
+            t.tensor_shape.dim.add(size=d)
     return resp.SerializeToString()
 
 

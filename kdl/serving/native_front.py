@@ -28,6 +28,7 @@ from ..ops import _lib
 from . import protos as P
 from .backend import NATIVE_SIGNATURE, ServingError
 from .metrics import METRICS
+from .outputs import kind_of
 
 log = logging.getLogger("kdl.serving")
 
@@ -126,7 +127,8 @@ class NativeFront:
             gen = self._gen
         runner = s.runner(sig_name)
         sig = runner.sig
-        if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or sig.top_k or sig.explain or not runner.healthy():
+        named = kind_of(sig).columns is not None         # an answer the native route cannot build
+        if not hasattr(runner, "batcher") or sig.input_shape[1] <= 0 or named or not runner.healthy():
             return                              # serving_image / serving_bytes / classify* / explain* / attention* / overlay*: slow path
         u8 = None
         if self.f32_exact_u8 and sig.input_dtype == P.DT_FLOAT and NATIVE_SIGNATURE in s.signatures:

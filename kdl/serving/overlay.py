@@ -24,7 +24,6 @@ the picture bytes (``pack_rows`` / ``unpack_rows``).
 """
 from __future__ import annotations
 
-import json
 from pathlib import Path
 
 import numpy as np
@@ -145,16 +144,10 @@ def unpack_rows(rows, h: int, w: int, S: int) -> tuple:
 
 
 # ------------------------------------------------------------------------------------------ config
-def _meta(path: Path) -> tuple[dict, str]:
-    for name in ("kdl_model.json", "synthetic.json"):
-        if (path / name).exists():
-            return json.loads((path / name).read_text()), name
-    return {}, "kdl_model.json"
-
-
 def resolve(path: Path, colormap_flag: str | None = None, alpha_flag: float | None = None) -> Overlay:
     """The version's ``Overlay``: its "overlay" block over the defaults, the two flags over that.
     ValueError (naming the file) fails the load."""
+    from .outputs import _meta
     path = Path(path)
     meta, name = _meta(path)
     block = meta.get("overlay", {})
@@ -182,9 +175,8 @@ def add_signatures(src, path, colormap_flag: str | None = None, alpha_flag: floa
     """Give a loaded ModelSource its three overlay signatures (beside the existing ones): the family's
     heatmap method (Grad-CAM or rollout) and one more output."""
     from ..engine import registry
-    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
-    from .jpeg import BYTES_SIGNATURE
-    from .resize import IMAGE_SIGNATURE
+    from .explain import map_outputs
+    from .outputs import add_trio
     info = registry.get(src.family)
     if info.cam_oracle is None and info.rollout_oracle is None:
         return
@@ -193,70 +185,6 @@ def add_signatures(src, path, colormap_flag: str | None = None, alpha_flag: floa
     S = src.input_size
     if S < max(h, w):
         raise ValueError(f"{path}: overlays only upsample, the {h} x {w} map is larger than the {S} x {S} input")
-    outs = (("classes", P.DT_STRING, (-1, 1)), ("scores", P.DT_FLOAT, (-1, 1)), ("heatmap", P.DT_FLOAT, (-1, h, w)),
-            ("overlay", P.DT_UINT8, (-1, S, S, 3)))
-    like = dict(zip(OVERLAY_SIGNATURES, (NATIVE_SIGNATURE, IMAGE_SIGNATURE, BYTES_SIGNATURE)))
-    for name, base in like.items():
-        b = src.signatures.get(base)
-        if b is None or name in src.signatures:
-            continue
-        key = b.input_key if b.input_dtype != P.DT_FLOAT else NATIVE_INPUT_KEY
-        shape = b.input_shape if name != OVERLAY_SIGNATURE else (-1, S, S, 3)
-        src.signatures[name] = SignatureInfo(name, key, b.input_dtype, "classes", input_shape=shape, output_shape=(-1, 1),
-                                             outputs=outs, explain=(h, w), rollout=info.cam_oracle is None,
-                                             overlay=S)
-
-
-# ------------------------------------------------------------------------------------------ answers
-def overlay_outputs(s, sig, rows) -> tuple:
-    """Packed rows of an overlay signature -> (labels [n], scores [n], heat [n, h, w], pictures uint8
-    [n, S, S, 3]). A class index outside the label list (the null device's rows) is its decimal."""
-    from .metrics import METRICS
-    classes, scores, heat, pics = unpack_rows(rows, *sig.explain, sig.overlay)
-    METRICS.inc("kdl_overlay_total", signature=sig.name)
-    lab = s.source.labels
-    return [lab[int(c)] if 0 <= int(c) < len(lab) else str(int(c)) for c in classes], scores, heat, pics
-
-
-def overlay_response(s, sig, rows, output_filter) -> bytes:
-    """PredictResponse of an overlay signature: explain's three outputs and ``overlay`` DT_UINT8
-    [n, S, S, 3] as ``tensor_content``, or the subset ``output_filter`` names."""
-    labels, scores, heat, pics = overlay_outputs(s, sig, rows)
-    n, (h, w), S = len(labels), sig.explain, sig.overlay
-    resp = P.PredictResponse()
-    resp.model_spec.name = s.name
-    resp.model_spec.version.value = s.version
-    resp.model_spec.signature_name = sig.name
-    want = list(output_filter) or list(OUTPUT_KEYS)
-    if "classes" in want:
-        t = resp.outputs["classes"]
-        t.dtype = P.DT_STRING
-        t.string_val.extend(name.encode() for name in labels)
-    if "scores" in want:
-        t = resp.outputs["scores"]
-        t.dtype = P.DT_FLOAT
-        t.float_val.extend(scores.reshape(-1).tolist())
-    if "heatmap" in want:
-        t = resp.outputs["heatmap"]
-        t.dtype = P.DT_FLOAT
-        t.float_val.extend(heat.reshape(-1).tolist())
-    if "overlay" in want:
-        t = resp.outputs["overlay"]
-        t.dtype = P.DT_UINT8
-        t.tensor_content = pics.tobytes()
-    shapes = {"heatmap": (n, h, w), "overlay": (n, S, S, 3)}
-    for key in resp.outputs:
-        for d in shapes.get(key, (n, 1)):
-            resp.outputs[key].tensor_shape.dim.add(size=d)
-    return resp.SerializeToString()
-
-
-def overlay_body(s, sig, rows, by_row: bool) -> dict:
-    """REST ``:predict`` answer of an overlay signature, per instance or by column; the picture as
-    nested integer lists like any numeric tensor."""
-    labels, scores, heat, pics = overlay_outputs(s, sig, rows)
-    if by_row:
-        return {"predictions": [{"classes": [c], "scores": [float(v)], "heatmap": m.tolist(), "overlay": p.tolist()}
-                                for c, v, m, p in zip(labels, scores, heat, pics)]}
-    return {"outputs": {"classes": [[c] for c in labels], "scores": [[float(v)] for v in scores],
-                        "heatmap": heat.tolist(), "overlay": pics.tolist()}}
+    outs = map_outputs(h, w) + (("overlay", P.DT_UINT8, (-1, S, S, 3)),)
+    add_trio(src, OVERLAY_SIGNATURES, "classes", (-1, 1), outputs=outs, explain=(h, w),
+             rollout=info.cam_oracle is None, overlay=S)

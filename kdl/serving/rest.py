@@ -30,9 +30,10 @@ from google.protobuf import json_format
 
 from ..ops import _lib
 from . import protos as P
+from . import outputs as O
 from .backend import ServingError
 from .classify import CLASSIFY_BYTES_SIGNATURE
-from .grpc_server import classify_examples, classify_outputs, route_exact_u8, signature_def_map
+from .grpc_server import classify_examples, route_exact_u8, signature_def_map
 from .metrics import METRICS
 from .model_repo import STATE_NAMES, ModelManager
 
@@ -40,6 +41,19 @@ _ROUTE = re.compile(r"^/v1/models/(?P<name>[^/:]+)(?:/versions/(?P<ver>\d+)|/lab
                     r"(?P<tail>:predict|:classify|/metadata)?/?$")
 _HTTP = {"INVALID_ARGUMENT": 400, "NOT_FOUND": 404, "DEADLINE_EXCEEDED": 504, "UNAVAILABLE": 503,
          "RESOURCE_EXHAUSTED": 429, "UNIMPLEMENTED": 501, "INTERNAL": 500}
+
+
+def predict_body(s, sig, rows, by_row: bool) -> dict:
+    """The :predict answer, per instance ("predictions") or by column ("outputs"): the rows of a
+    single fp32 output as they are, else an object of the kind's named outputs (serving/outputs.py)."""
+    cols = O.columns(s.source, sig, rows)
+    if cols is None:
+        O.answered(sig)
+        return {"predictions" if by_row else "outputs": rows.tolist()}
+    cols = [(key, v if isinstance(v, list) else v.tolist()) for key, _, v in cols]
+    if by_row:
+        return {"predictions": [{key: v[i] for key, v in cols} for i in range(len(rows))]}
+    return {"outputs": dict(cols)}
 
 
 def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
@@ -130,7 +144,7 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 if f32_exact_u8:     # same routing as gRPC (--scatter rccl serves serving_uint8 over the node)
                     runner, x = route_exact_u8(s, runner, x, n_img)
                 t1 = time.perf_counter()
-                out = self._body(s, sig, runner.predict(x, n_img, deadline), rows)
+                out = predict_body(s, sig, runner.predict(x, n_img, deadline), rows)
                 t2 = time.perf_counter()
                 r = self._send(200, out)
                 # same per-request stage trace as the gRPC path (SURVEY.md §5 tracing)
@@ -145,26 +159,6 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
                 return self._err(e)
             except (ValueError, KeyError, TypeError) as e:
                 return self._err(ServingError("INVALID_ARGUMENT", str(e)))
-
-        @staticmethod
-        def _body(s, sig, out, rows: bool) -> dict:
-            """The :predict answer: logits, a classify signature's two named outputs, or an explain
-            signature's three."""
-            if sig.overlay:
-                from .overlay import overlay_body
-                return overlay_body(s, sig, out, rows)
-            if sig.explain:
-                from .explain import explain_body
-                return explain_body(s, sig, out, rows)
-            if sig.embed:
-                METRICS.inc("kdl_embed_total", signature=sig.name)
-            if not sig.top_k:
-                return {"predictions": out.tolist()} if rows else {"outputs": out.tolist()}
-            labels, scores = classify_outputs(s, sig, out)
-            names = sig.output_key              # "classes", or a similar signature's "ids"
-            if rows:
-                return {"predictions": [{names: c, "scores": v} for c, v in zip(labels, scores.tolist())]}
-            return {"outputs": {names: labels, "scores": scores.tolist()}}
 
         def _classify(self, m):
             t0 = time.perf_counter()
@@ -246,7 +240,7 @@ def make_handler(manager: ModelManager, f32_exact_u8: bool = True):
             dl = self.headers.get("X-Deadline-Ms")
             deadline = int(_lib.rt().now_us() + float(dl) * 1e3) if dl else 0
             t1 = time.perf_counter()
-            out = self._body(s, sig, runner.predict(images, len(images), deadline), rows)
+            out = predict_body(s, sig, runner.predict(images, len(images), deadline), rows)
             t2 = time.perf_counter()
             r = self._send(200, out)
             METRICS.observe("kdl_stage_ms", (t1 - t0) * 1e3, stage="parse")

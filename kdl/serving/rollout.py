@@ -14,7 +14,7 @@ signatures, as ViT has no explain signatures.
 """
 from __future__ import annotations
 
-from .explain import add_map_signatures, pack_rows, unpack_rows  # noqa: F401  (the row layout is shared)
+from .explain import map_outputs, pack_rows, unpack_rows  # noqa: F401  (the row layout is shared)
 
 ATTENTION_SIGNATURE = "attention"
 ATTENTION_IMAGE_SIGNATURE = "attention_image"
@@ -26,7 +26,8 @@ def add_signatures(src, path=None) -> None:
     """Give a loaded ModelSource its three attention signatures (beside the existing ones), when its
     family has a ``rollout_oracle``."""
     from ..engine import registry
+    from .outputs import add_trio
     info = registry.get(src.family)
-    if info.rollout_oracle is None:
-        return
-    add_map_signatures(src, ATTENTION_SIGNATURES, info.map_size, rollout=True)
+    if info.rollout_oracle is not None:
+        add_trio(src, ATTENTION_SIGNATURES, "classes", (-1, 1), outputs=map_outputs(*info.map_size),
+                 explain=tuple(info.map_size), rollout=True)

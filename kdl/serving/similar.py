@@ -20,7 +20,6 @@ sum_i q_i * g_ji with the query as fp32 (for cosine L2-normalised first, ``embed
 bf16 values as they stand; rows rank by descending score, equal scores by ascending row index."""
 from __future__ import annotations
 
-import json
 from pathlib import Path
 
 import numpy as np
@@ -89,16 +88,10 @@ def similar_rule(features_fp32: np.ndarray, gallery_bf16: np.ndarray, k: int,
     return order.astype(np.int32), np.take_along_axis(s, order, axis=1).astype(np.float32)
 
 
-def _meta(path: Path) -> tuple[dict, str]:
-    for name in ("kdl_model.json", "synthetic.json"):
-        if (path / name).exists():
-            return json.loads((path / name).read_text()), name
-    return {}, "kdl_model.json"
-
-
 def resolve(path: Path, features: int, top_k_flag: int | None = None):
     """None for a version without a gallery, else (K, metric, bf16 patterns [N, F], ids [N]) of the
     version in ``path``; ValueError (naming the file) fails the load."""
+    from .outputs import _meta
     path = Path(path)
     meta, name = _meta(path)
     spec = meta.get("similar", {})
@@ -131,27 +124,15 @@ def resolve(path: Path, features: int, top_k_flag: int | None = None):
 def add_signatures(src, path: Path, top_k_flag: int | None = None) -> None:
     """Give a loaded ModelSource with a gallery its three similar signatures (beside the others)."""
     from ..engine import registry
-    from .backend import NATIVE_INPUT_KEY, NATIVE_SIGNATURE, SignatureInfo
-    from .jpeg import BYTES_SIGNATURE
-    from .resize import IMAGE_SIGNATURE
+    from .outputs import add_trio
     F = src.head.features if src.head is not None else registry.get(src.family).features
     got = resolve(path, F, top_k_flag)
     if got is None:
         return
     k, src.similar_metric, src.gallery, src.gallery_ids = got
     src.similar_k = k
-    S = src.input_size
     outs = (("ids", P.DT_STRING, (-1, k)), ("scores", P.DT_FLOAT, (-1, k)))
-    like = {SIMILAR_SIGNATURE: NATIVE_SIGNATURE, SIMILAR_IMAGE_SIGNATURE: IMAGE_SIGNATURE,
-            SIMILAR_BYTES_SIGNATURE: BYTES_SIGNATURE}
-    for name, base in like.items():
-        b = src.signatures.get(base)
-        if b is None or name in src.signatures:
-            continue
-        key = b.input_key if b.input_dtype != P.DT_FLOAT else NATIVE_INPUT_KEY
-        shape = b.input_shape if name != SIMILAR_SIGNATURE else (-1, S, S, 3)
-        src.signatures[name] = SignatureInfo(name, key, b.input_dtype, "ids", input_shape=shape,
-                                             output_shape=(-1, k), outputs=outs, top_k=k, similar=True)
+    add_trio(src, SIMILAR_SIGNATURES, "ids", (-1, k), outputs=outs, top_k=k, similar=True)
 
 
 def ids_of(src, rows: np.ndarray) -> list[list[str]]:

@@ -234,7 +234,7 @@ def test_server_classify_bytes_and_classify_rpc_follow_serving_bytes(tmp_path):
             raw = ch.unary_unary(P.CLASSIFY_METHOD)(req.SerializeToString(), timeout=120)
         s = srv.manager.get("clothing-model", None, None)
         r = s.runner("classify")
-        assert r.topk == 5 and r.out_cols == 10 and all(ex.engine.topk == 5 for ex in r.executors)
+        assert r.gpu and r.sig.top_k == 5 and r.out_cols == 10 and all(ex.engine.topk == 5 for ex in r.executors)
         order, p = reference(logits)
         want_cls = [[str(c) for c in row] for row in order[:, :5]]
         want = np.take_along_axis(p, order[:, :5], axis=1)

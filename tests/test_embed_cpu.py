@@ -189,7 +189,7 @@ def test_embed_equals_the_feature_oracle_over_grpc_and_rest(server, stub, pixels
     _close(_rows(resp, 2), oracle)
     assert np.asarray(process_embed_response(resp), np.float32).shape == (2, F)
     r = server.manager.get("clothing-model", None, None).runner("embed")
-    assert r.out_cols == F and r.embed == "raw"
+    assert r.out_cols == F and r.sig.embed == "raw"
     url = f"http://127.0.0.1:{server.rest_port}/v1/models/clothing-model:predict"
     st, out = _post(url, {"signature_name": "embed", "instances": pixels[:1].tolist()})
     assert st == 200, out
@@ -251,7 +251,7 @@ def test_l2_server(repo, pixels, oracle):
         with grpc.insecure_channel(f"127.0.0.1:{srv.grpc_port}") as ch:
             got = _rows(PredictionStub(ch).Predict(make_request(pixels, signature="embed", input_key="images"),
                                                    timeout=120), 2)
-        assert srv.manager.get("clothing-model", None, None).runner("embed").embed == "l2"
+        assert srv.manager.get("clothing-model", None, None).runner("embed").sig.embed == "l2"
     finally:
         srv.stop(0)
     assert np.abs(np.linalg.norm(got.astype(np.float64), axis=1) - 1).max() <= (F / 2 + 8) * U

@@ -276,7 +276,7 @@ def test_metadata_and_runner(server, stub, answers):
         assert out["heatmap"].dtype == P.DT_FLOAT and [d.size for d in out["heatmap"].tensor_shape.dim] == [-1, 10, 10]
     assert sorted(sdm.signature_def["classify"].outputs) == ["classes", "scores"]      # the others are as they were
     r = server.manager.get("clothing-model", None, None).runner("explain")
-    assert r.out_cols == 102 and r.explain_hw == (10, 10) and not r.explain          # no engines on a CPU
+    assert r.out_cols == 102 and r.sig.explain == (10, 10) and not r.gpu          # no engines on a CPU
 
 
 def _post(url, body):

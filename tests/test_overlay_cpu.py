@@ -349,8 +349,8 @@ def test_metadata_and_runner(server, stub):
         assert out["classes"].dtype == P.DT_STRING and out["scores"].dtype == P.DT_FLOAT
     assert sorted(sdm.signature_def["explain"].outputs) == ["classes", "heatmap", "scores"]
     r = server.manager.get("clothing-model", None, None).runner("overlay")
-    assert r.out_cols == 102 + overlay_words(299) and r.explain_hw == (10, 10) and r.overlay_size == 299
-    assert not r.explain and not r.rollout and not r.attention      # no engines on a CPU; Grad-CAM's family
+    assert r.out_cols == 102 + overlay_words(299) and r.sig.explain == (10, 10) and r.sig.overlay == 299
+    assert not r.gpu and r.kind == "overlay" and not r.sig.rollout      # no engines on a CPU; Grad-CAM's family
 
 
 def _post(url, body):

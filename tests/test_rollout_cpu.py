@@ -240,8 +240,8 @@ def test_metadata_and_runner(server, stub, answers):
         assert [d.size for d in out["heatmap"].tensor_shape.dim] == [-1, 14, 14]
     assert "explain" not in sdm.signature_def
     r = server.manager.get("vit", None, None).runner("attention")
-    assert r.out_cols == 198 and r.explain_hw == (14, 14) and r.attention
-    assert not r.rollout and not r.explain                      # no engines on a CPU
+    assert r.out_cols == 198 and r.sig.explain == (14, 14) and r.kind == "attention"
+    assert not r.gpu                                            # no engines on a CPU
 
 
 def _post(url, body):

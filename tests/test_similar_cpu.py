@@ -264,7 +264,7 @@ def test_cpu_server_follows_the_rule(server, stub, pixels, expected):
     assert ids[0][:2] == ["item-07", "item-09"] and ids[1][:2] == ["item-02", "item-05"]    # ties by row index
     assert sc[0, 0] == sc[0, 1] and abs(sc[0, 0] - 1) < 5e-3                                # bf16 storage
     r = server.manager.get("clothing-model", None, None).runner("similar")
-    assert r.out_cols == F and not r.similar and r.k == K
+    assert r.out_cols == F and not r.gpu and r.sig.top_k == K
     url = f"http://127.0.0.1:{server.rest_port}/v1/models/clothing-model:predict"
     st, out = _post(url, {"signature_name": "similar", "instances": pixels[:1].tolist()})
     assert st == 200, out
