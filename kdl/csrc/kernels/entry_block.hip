@@ -25,7 +25,8 @@
 // pairs, fp32 accumulate), each lane producing the 8 channels of one pixel = exactly its MFMA
 // operand fragment, written fragment-linear to an LDS A buffer. Phases per step, separated by
 // workgroup barriers: dw1 -> GEMM1 (+ residual GEMM) -> dw2 -> GEMM2 + pool (five barriers with B0).
-// TWOPH (config 21, block3's default): the same step skewed by one stage, TWO barriers per step --
+// TWOPH (configs 21 and 23, block3's default: 21 with both depthwise convs on the matrix cores, the
+// block-diagonal operand of sepconv_ws.hip): the same step skewed by one stage, TWO barriers per step --
 // a DW phase (dw2 of step i, dw1 + residual GEMM of step i+1) and a GEMM phase (GEMM2 + pool + output
 // of step i, GEMM1 of step i+1, the x-row DMA of step i+2 in flight); A1 and A2 are separate buffers,
 // the horizontal pool exchanges lanes (ds_bpermute) instead of LDS rows, no register is spilled.
@@ -259,6 +260,38 @@ __device__ __forceinline__ void eb_dw_mfma_rowpair(Addr addr, Wop wop, int lane,
   out[1] = (u32x2){pack_bf16(acc1[0], acc1[1]), pack_bf16(acc1[2], acc1[3])};
 }
 
+// Two output rows of ONE 16-channel group that share their weight operands (eb_dw_mfma_rowpair's
+// arithmetic, operand for operand), for the two-phase loop: a0[j] / a1[j] + off -> the input of MFMA j of
+// row 0 / row 1 in this lane (the caller folds the tap parity of the half-wave into the addresses once
+// per part; off is common to all lanes, an immediate of the read), so the rows need not be neighbours.
+// The ten reads are fenced off from the MFMAs (sched_barrier): left alone, the scheduler interleaves
+// read, wait and MFMA one by one to save registers, and a wave with a single partner on its SIMD then
+// waits out every LDS latency in turn (profiles/entry_block3_dwm.txt, form 1 against form 2).
+template <bool RELU, class Wop>
+__device__ __forceinline__ void eb_dw_mfma_two(const uint8_t* const (&a0)[5], const uint8_t* const (&a1)[5], int off, Wop wop,
+                                               u32x2 (&out)[2]) {
+  u32x4 r0[5], r1[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    r0[j] = *(const u32x4*)(a0[j] + off);
+    r1[j] = *(const u32x4*)(a1[j] + off);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    if constexpr (RELU) {
+#pragma unroll
+      for (int d = 0; d < 4; ++d) { r0[j][d] = relu_bf16x2(r0[j][d]); r1[j][d] = relu_bf16x2(r1[j][d]); }
+    }
+    const u32x4 wf = wop(j);
+    acc0 = mfma16(__builtin_bit_cast(s16x8, wf), __builtin_bit_cast(s16x8, r0[j]), acc0);
+    acc1 = mfma16(__builtin_bit_cast(s16x8, wf), __builtin_bit_cast(s16x8, r1[j]), acc1);
+  }
+  out[0] = (u32x2){pack_bf16(acc0[0], acc0[1]), pack_bf16(acc0[2], acc0[3])};
+  out[1] = (u32x2){pack_bf16(acc1[0], acc1[1]), pack_bf16(acc1[2], acc1[3])};
+}
+
 // one channel group's C fragment [16 ch][16 px], transposed into the A fragment at dst (eb_dw_store's
 // mapping for group g)
 __device__ __forceinline__ void eb_dw_store_g(uint8_t* dst, int lane, int g, u32x2 val) {
@@ -455,8 +488,8 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     // y1 ring slots are counted by steps: step j writes its rows R+2, R+3 into pair j & 1 and reads
     // R, R+1 from the other pair (its predecessor's), so the rows of two runs walked back to back
     // never meet in a slot whatever their row numbers are.
-    static_assert(!DWM && !WIDE && PT == 0 && Y2FR == 2 && U1 % NW == 0 && NW == KT1,
-                  "two-phase schedule: block3's VALU-depthwise, two-slice build (a wave's dw2 units: one k-step)");
+    static_assert(!WIDE && PT == 0 && Y2FR == 2 && U1 % NW == 0 && NW == KT1,
+                  "two-phase schedule: block3's two-slice build (a wave's dw2 units: one k-step)");
     uint8_t* const A2 = Ab;
     uint8_t* const A1 = smem + G::OFF_A1;
     auto word = [&](int q) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)stl[q - s0]); };
@@ -465,6 +498,19 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     // as loop invariants they are hoisted out of the loop by the dozen and kept in scratch, and a
     // scratch reload in the GEMM phase waits, in vmcnt order, for the x-row DMA issued ahead of it
     auto fresh = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
+    // DWM: the v_perm selectors of the block-diagonal operand, rebuilt per iteration like the addresses
+    auto mksel = [](int lane, uint32_t (&sl)[2][4]) {
+      const int p16 = lane & 15, q16 = lane >> 4, e = p16 & 7;
+      const bool wv = (p16 >> 3) == (q16 & 1);
+#pragma unroll
+      for (int jp = 0; jp < 2; ++jp)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          const uint32_t pair = (2u * jp) | ((2u * jp + 1u) << 8);
+          const uint32_t val = (e & 1) ? (0x0c0cu | (pair << 16)) : (0x0c0c0000u | pair);
+          sl[jp][d] = (wv && (e >> 1) == d) ? val : 0x0c0c0c0cu;
+        }
+    };
     // residual carry: dw1 runs a step early, so the residual of pooled row k + 1 (read with x row
     // 2k + 2 in the ring) is two iterations ahead of its output. fp32, never rounded.
     f32x4 res0[NFW], res1[NFW], res2[NFW];           // of the output of step it / it + 1 / it + 2
@@ -480,30 +526,68 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
       const int pcn = (int)((en >> 8) & 63) * PC, Rn = 2 * ((int)((en >> 14) & 511) - 2);
       const int R = 2 * k;
       if (it >= s0) stamp(it, 0);
+      // DWM (config 23): both depthwise convs on the matrix cores. The v_perm selectors of the block-diagonal
+      // weight operand are rebuilt once per DW phase, and each part folds the half-wave's tap parity into
+      // five addresses per row once (MFMA j reads tap 2j in the parity-0 lanes, 2j + 1 in the parity-1
+      // lanes; j 4, parity 1: any tap, its weight is 0): the items of a part differ by an immediate
+      uint32_t sel[2][4];
+      if constexpr (DWM) mksel(fresh(), sel);
       // ---- DW phase. dw2(it) -> A2 (y2 rows R+1, R+2: fragments [row][col / 16])
       if (mc >= 1) {
         const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
-        // a wave's four units are the two rows of both column fragments at its k-step: per fragment a
-        // row pair (eb_dw8_n: 12 distinct tap reads for the two rows), all four stored after the last read
-        const uint32_t* wq = dwl + ((KT0 + t2) * 4 + q16) * 40;
-        s16x8 o2[Y2FR][2];
+        if constexpr (DWM) {
+          // per 16-channel group g the five weight operands are rebuilt from the group's LDS entry (no
+          // registers to keep them) and serve the row pair of both column fragments: 10 tap reads and 10
+          // MFMAs per (g, fragment), all eight results stored after the last read
+          const bool par = (lane & 32) != 0;
+          const uint8_t* base = y1r + (4 * t2 + (q16 & 1)) * PLB + p16 * 16;
+          const uint8_t *a0[5], *a1[5];              // y2 row R+1 reads y1 rows R..R+2, row R+2 rows R+1..R+3
 #pragma unroll
-        for (int fc = 0; fc < Y2FR; ++fc) {
-          const uint8_t* base = y1r + (4 * t2 + q16) * PLB + (fc * 16 + p16) * 16;
-          auto tap = [&](int rr, int ti) {           // y2 row R+1+rr reads y1 rows R+rr .. R+rr+2
-            return *(const u32x4*)(base + yslot(it, rr + ti / 3) * Y1ROW + (ti % 3) * 16);
-          };
-          eb_dw8_n<false, 2>(tap, wq, o2[fc]);
+          for (int j = 0; j < 5; ++j) {
+            const int te = 2 * j, to = j < 4 ? 2 * j + 1 : 8;
+            a0[j] = base + (par ? yslot(it, to / 3) * Y1ROW + (to % 3) * 16 : yslot(it, te / 3) * Y1ROW + (te % 3) * 16);
+            a1[j] = base + (par ? yslot(it, to / 3 + 1) * Y1ROW + (to % 3) * 16 : yslot(it, te / 3 + 1) * Y1ROW + (te % 3) * 16);
+          }
+          u32x2 dv[2][Y2FR][2];
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const u32x4 we = *(const u32x4*)((const uint8_t*)dwl + (KT0 + t2) * G::DWQ + ((g * 16 + p16) * 2 + (q16 >> 1)) * 16);
+            u32x4 wk[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) wk[j] = eb_dw_wop(we, j, sel);
+#pragma unroll
+            for (int fc = 0; fc < Y2FR; ++fc)
+              eb_dw_mfma_two<false>(a0, a1, 2 * g * PLB + fc * 256, [&](int j) { return wk[j]; }, dv[g][fc]);
+          }
+#pragma unroll
+          for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int fc = 0; fc < Y2FR; ++fc)
+#pragma unroll
+              for (int rr = 0; rr < 2; ++rr)
+                eb_dw_store_g(A2 + (t2 * Y2F + rr * Y2FR + fc) * 1024, lane, g, dv[g][fc][rr]);
+        } else {
+          // a wave's four units are the two rows of both column fragments at its k-step: per fragment a
+          // row pair (eb_dw8_n: 12 distinct tap reads for the two rows), all four stored after the last read
+          const uint32_t* wq = dwl + ((KT0 + t2) * 4 + q16) * 40;
+          s16x8 o2[Y2FR][2];
+#pragma unroll
+          for (int fc = 0; fc < Y2FR; ++fc) {
+            const uint8_t* base = y1r + (4 * t2 + q16) * PLB + (fc * 16 + p16) * 16;
+            auto tap = [&](int rr, int ti) {         // y2 row R+1+rr reads y1 rows R+rr .. R+rr+2
+              return *(const u32x4*)(base + yslot(it, rr + ti / 3) * Y1ROW + (ti % 3) * 16);
+            };
+            eb_dw8_n<false, 2>(tap, wq, o2[fc]);
+          }
+#pragma unroll
+          for (int fc = 0; fc < Y2FR; ++fc)
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) *(s16x8*)(A2 + (t2 * Y2F + rr * Y2FR + fc) * 1024 + lane * 16) = o2[fc][rr];
         }
-#pragma unroll
-        for (int fc = 0; fc < Y2FR; ++fc)
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) *(s16x8*)(A2 + (t2 * Y2F + rr * Y2FR + fc) * 1024 + lane * 16) = o2[fc][rr];
       }
       // dw1(it + 1) -> A1 (y1 rows Rn+2, Rn+3) and the residual of pooled row kn + 1 (x row Rn+2)
       if (hn) {
         const int lane = fresh(), p16 = lane & 15, q16 = lane >> 4;
-        const uint32_t* wq = dwl + (t1 * 4 + q16) * 40;
         const uint8_t* base[U1W];
         int row[U1W];
 #pragma unroll
@@ -512,21 +596,53 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
           pi = pi < 2 * Y1C ? pi : 2 * Y1C - 1;
           const int rr = pi >= Y1C, col = pi - rr * Y1C;
           row[i] = Rn + 2 + rr;
-          base[i] = xr + (4 * t1 + q16) * PLB + col * 16;
+          base[i] = xr + (4 * t1 + (DWM ? q16 & 1 : q16)) * PLB + col * 16;
         }
-        auto tap = [&](int i, int ti) {
-          return *(const u32x4*)(base[i] + ((row[i] - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
-        };
-        s16x8 o1[U1W];
-        eb_dw8_n<RELU1, U1W>(tap, wq, o1);
+        if constexpr (DWM) {
+          // the y1 fragments are 16 of the two rows' linearised pixels, not a row each, so no row pairs: the
+          // wave's two units (each lane its own pixel and row) share a group's weight operands instead
+          static_assert(U1W == 2, "the wave's two dw1 units as one pair");
+          const bool par = (lane & 32) != 0;
+          const uint8_t* ad[U1W][5];
 #pragma unroll
-        for (int i = 0; i < U1W; ++i) *(s16x8*)(A1 + (t1 * Y1F + (w + NW * i) / KT0) * 1024 + lane * 16) = o1[i];
+          for (int i = 0; i < U1W; ++i)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+              const int te = 2 * j, to = j < 4 ? 2 * j + 1 : 8;
+              ad[i][j] = base[i] + (par ? ((row[i] - 1 + to / 3) & 3) * XROW + (to % 3) * 16
+                                        : ((row[i] - 1 + te / 3) & 3) * XROW + (te % 3) * 16);
+            }
+          u32x2 dv[U1W][2];
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const u32x4 we = *(const u32x4*)((const uint8_t*)dwl + t1 * G::DWQ + ((g * 16 + p16) * 2 + (q16 >> 1)) * 16);
+            u32x4 wk[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) wk[j] = eb_dw_wop(we, j, sel);
+            u32x2 o[2];
+            eb_dw_mfma_two<RELU1>(ad[0], ad[1], 2 * g * PLB, [&](int j) { return wk[j]; }, o);
+            dv[0][g] = o[0];
+            dv[1][g] = o[1];
+          }
+#pragma unroll
+          for (int i = 0; i < U1W; ++i) eb_dw_store(A1 + (t1 * Y1F + (w + NW * i) / KT0) * 1024, lane, dv[i]);
+        } else {
+          const uint32_t* wq = dwl + (t1 * 4 + q16) * 40;
+          auto tap = [&](int i, int ti) {
+            return *(const u32x4*)(base[i] + ((row[i] - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
+          };
+          s16x8 o1[U1W];
+          eb_dw8_n<RELU1, U1W>(tap, wq, o1);
+#pragma unroll
+          for (int i = 0; i < U1W; ++i) *(s16x8*)(A1 + (t1 * Y1F + (w + NW * i) / KT0) * 1024 + lane * 16) = o1[i];
+        }
         if (mn >= 1) {
           // the residual weights are fetched here, every step (8 KiB per wave, L2-resident; nothing else is
           // in flight: barrier B drained vmcnt), and live only for the eight MFMAs below. As residents (32
           // VGPRs) they pushed the allocation into scratch, and so did fetching them any earlier in the
-          // phase (the allocator parked them in scratch across the depthwise); a scratch reload in the
-          // GEMM phase waits, in vmcnt order, for the x-row DMA issued ahead of it
+          // phase (the allocator parked them in scratch across the depthwise; with the MFMA depthwise too:
+          // 12 VGPRs spilled); a scratch reload in the GEMM phase waits, in vmcnt order, for the x-row DMA
+          // issued ahead of it
           s16x8 wrs[NFW][KT0];
 #pragma unroll
           for (int n = 0; n < NFW; ++n)
@@ -1405,7 +1521,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 // (74x74x128 -> 37x37x256, the asymmetric 74 -> 37 pool: leading pad 0); 100 + id: the same
 // with per-phase s_memtime stamps (EntryBlockArgs.stamps; diagnostics only); 2, 3: 0, 1 with the
 // depthwise convs on the matrix cores (block-diagonal operand) instead of the VALU (block2 only:
-// block3's LDS map has no room for the larger entries); 4, 5: block2
+// block3's four-phase LDS map has no room for the larger entries; the two-phase map has: config 23); 4, 5: block2
 // with 13-column strips, small enough (LDS, <= 128 VGPRs) for two workgroups per CU. Measured and removed (round 5,
 // profiles/entry_block3_r5.txt): block3 as 16 waves of one slice (VALU / MFMA depthwise: 328 / 246 us)
 // and block3 with the MFMA depthwise (378 us) against config 1's 188 us -- all spill (78 / 56 / 91 VGPRs)
@@ -1432,13 +1548,25 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 // product sits in -- block outputs equal on small maps, bench logits off by 7.6e-3; 8 reads with
 // v_permlane32_swap: bit-identical, iteration 6,472: 24 swaps / selects + 16 copies per item cost more
 // than two reads), and block3 (VALU depthwise) was not changed: see the same file.
-// 21 / 121 (block3's default): config 1 on the two-phase schedule (TWOPH, see the loop's comment). Bit-identical
+// 21 / 121: config 1 on the two-phase schedule (TWOPH, see the loop's comment). Bit-identical
 // to config 1 (tests/test_entry_block3_twophase_gpu.py; the bench logits equal the parent build's). One lease
 // (profiles/entry_block3_twophase.txt): 185 -> 145 us per launch, step 23.4k -> 18.4k cycles (DW phase 8.0k,
 // GEMM phase 7.8k, barrier B 2.6k), 254 VGPRs and no spill against 256 with 26 spilled; bench +2.6 % in 8 of 8
 // interleaved pairs (A spread 1.4 %). The barriers were the smaller part: the same schedule with config 1's
 // resident residual weights and hoisted lane addresses spilled 37 VGPRs and ran 174 us, with the depthwise
 // reads shared on top 54 spilled and 221 us -- a scratch reload in the GEMM phase waits behind the x-row DMA.
+// 23 / 123 (block3's default): config 21 with both depthwise convs on the matrix cores (DWM in the two-phase
+// loop: eb_dw_mfma_two; dw2 as row pairs per column fragment and 16-channel group, dw1 as the wave's two
+// units per group; weight operands rebuilt from the LDS entries every iteration). NOT bit-identical to 21
+// (the MFMA sums a tap pair's products its own way; tests/test_entry_block3_dwm_gpu.py: same bound against
+// the fp32 oracle, bit-equal across plans and launches). One lease (profiles/entry_block3_dwm.txt): 240
+// VGPRs, no spill; DW phase 715 -> 342 VALU, 8 -> 68 MFMA, 68 -> 70 ds_read per wave; 148 -> 128 us per
+// launch, DW phase 8.0k -> 6.0k cycles of an 18.4k -> 16.5k iteration; bench +1.25 % in 8 of 8 interleaved
+// pairs (A spread 0.62 %), bench logits within 7.7e-3 of the parent build's. Forms measured and dropped, same
+// file: the reads left to the scheduler (eb_dw_mfma_rowpair / single rows: it interleaves read, wait and
+// MFMA one by one, 137 us), the reads fenced off but every address rebuilt per item (384 VALU, 133 us),
+// the residual weights fetched ahead of dw1 (12 VGPRs spilled, 140 us) or half of them (254 VGPRs, 126 us:
+// inside the noise of the simpler form).
 #define KDL_EBW_CONFIGS(X) \
   X(13, 64, 128, 13, 16, 8, 1, false, 0, false) \
   X(15, 64, 128, 13, 16, 8, 1, false, 1, false) \
@@ -1456,12 +1584,14 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   X(4, 64, 128, 13, 1, 1, false, false, 2, false)  \
   X(5, 64, 128, 13, 1, 1, false, true, 2, false)   \
   X(21, 128, 256, 13, 2, 0, true, false, 1, true)  \
+  X(23, 128, 256, 13, 2, 0, true, true, 1, true)   \
   X(100, 64, 128, 15, 1, 1, false, false, 1, false) \
   X(101, 128, 256, 13, 2, 0, true, false, 1, false) \
   X(102, 64, 128, 15, 1, 1, false, true, 1, false) \
   X(104, 64, 128, 13, 1, 1, false, false, 2, false) \
   X(105, 64, 128, 13, 1, 1, false, true, 2, false) \
-  X(121, 128, 256, 13, 2, 0, true, false, 1, true)
+  X(121, 128, 256, 13, 2, 0, true, false, 1, true) \
+  X(123, 128, 256, 13, 2, 0, true, true, 1, true)
 
 int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds, int* occ) {
   switch (cfg) {

@@ -30,8 +30,9 @@ def entry_block_config(cfg: int) -> tuple[int, int, int, int, int]:
 
 
 # kernel config per (block input channels, block output channels): entry_block.hip KDL_EB_CONFIGS
-# (the four-phase builds, any map parity they were built for; the engine's default for block3 is config 21,
-# the two-phase schedule of config 1: kdl/engine/xception.py KDL_ENTRY_BLOCK)
+# (the four-phase builds, any map parity they were built for; the engine's default for block3 is config 23,
+# the two-phase schedule of config 1 (config 21) with the depthwise on the matrix cores:
+# kdl/engine/xception.py KDL_ENTRY_BLOCK)
 CONFIGS = {(64, 128): 0, (128, 256): 1}
 
 

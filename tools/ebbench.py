@@ -23,7 +23,8 @@ def stamps(p, blocks, B, only=None):
         b = X.SPEC[blk - 1]
         s1, s2, r = XE._sep(p, b.main[0], "cuda"), XE._sep(p, b.main[1], "cuda"), XE._pw(p, b.res_conv, "cuda")
         H, C0 = geom[blk]
-        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1, 21]  # 17 / 19: 13 / 15 with the row-pair depthwise; 21: two-phase
+        # 17 / 19: 13 / 15 with the row-pair depthwise; 21: two-phase; 23: 21 with the depthwise on the matrix cores
+        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1, 21, 23]
         cfgs = [c for c in cfgs if only is None or c in only]
         for cfg in [c for b in cfgs for c in (b, 100 + b)]:
             eb = EntryBlock(f"block{blk}", s1, s2, r, cfg=cfg)
@@ -61,7 +62,7 @@ def stamps(p, blocks, B, only=None):
                     if xs:
                         print(f"    {n:20s} {statistics.median(xs):8.0f}", flush=True)
                 continue
-            if cfg == 121:                       # two-phase: [iteration start, barrier A, end of the GEMM phase]
+            if cfg in (121, 123):         # two-phase: [iteration start, barrier A, end of the GEMM phase]
                 ph = {n: [] for n in ("DW phase", "GEMM phase", "vmcnt + barrier B", "iteration")}
                 for wg in range(8):
                     for k in range(3, 62):
