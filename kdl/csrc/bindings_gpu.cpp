@@ -252,6 +252,15 @@ HeatOverlayArgs heat_overlay_args(const py::dict& d) {
   a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.a = I(d, "a"); a.blend = I(d, "blend");
   return a;
 }
+JpegEncodeArgs jpeg_encode_args(const py::dict& d) {
+  JpegEncodeArgs a{};
+  a.inp = P<const uint8_t>(d, "inp"); a.hdr = P<const uint8_t>(d, "hdr"); a.h_hdr = P<const uint8_t>(d, "h_hdr");
+  a.front = P<const uint32_t>(d, "front"); a.out = P<uint32_t>(d, "out"); a.work = P<void>(d, "work");
+  a.ldi = (d.contains("ldi") && !d["ldi"].is_none()) ? d["ldi"].cast<int64_t>() : 0;
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.quality = I(d, "quality"); a.sampling = I(d, "sampling", -1);
+  a.cap = I(d, "cap"); a.ldo = I(d, "ldo"); a.nfront = I(d, "nfront"); a.ldf = I(d, "ldf");
+  return a;
+}
 ResizeArgs resize_args(const py::dict& d) {
   ResizeArgs a{};
   a.src = P<const uint8_t>(d, "src"); a.dst = P<uint8_t>(d, "dst");
@@ -396,6 +405,18 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(heat_overlay(a, S(s)), "heat_overlay");
   });
+  // baseline JPEG encode (kernels/jpeg_encode.hip): d = the JpegEncodeArgs fields; h_hdr is a HOST address
+  m.def("jpeg_encode", [](py::dict d, uintptr_t s) {
+    const auto a = jpeg_encode_args(d);
+    py::gil_scoped_release nogil;
+    chk(jpeg_encode(a, S(s)), "jpeg_encode");
+  });
+  m.def("jpeg_encode_workspace", [](int B, int H, int W, int sampling, int cap) {
+    return jpeg_encode_workspace(B, H, W, sampling, cap);
+  });
+  m.attr("JPEG_HEADER_BYTES") = int(kJpegHeaderBytes);
+  m.attr("JPEG_ENC_MAX_SIDE") = int(kJpegEncMaxSide);
+  m.attr("JPEG_ENC_MAX_CAP") = int(kJpegEncMaxCap);
   m.attr("OVERLAY_MAX_S") = int(kOverlayMaxS);
   m.attr("OVERLAY_MAX_TAPS") = int(kOverlayMaxTaps);
   m.attr("ROLLOUT_MAX_T") = int(kRolloutMaxT);
@@ -748,6 +769,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_heat_overlay", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_HEAT_OVERLAY; op.name = name; op.ho = heat_overlay_args(d); p.add(op);
+      })
+      .def("add_jpeg_encode", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_JPEG_ENCODE; op.name = name; op.je = jpeg_encode_args(d); p.add(op);
       })
       .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);

@@ -529,6 +529,40 @@ struct HeatOverlayArgs {
 };
 hipError_t heat_overlay(const HeatOverlayArgs& a, hipStream_t s);
 
+// Baseline JPEG encode (kernels/jpeg_encode.hip): B pictures uint8 [H][W][3], picture b at inp + b * ldi
+// bytes (any alignment), each into the file Pillow's Image.save(.., "JPEG", quality, subsampling,
+// optimize=False) writes, byte for byte (kdl/serving/jpeg_encode.py encode_rule is the definition:
+// libjpeg's fixed-point colour, h2v2 average, islow DCT, Annex K tables, one interleaved scan).
+// Output row b, ldo words: nfront words copied from front[b * ldf ..] (nfront = 0: none), one word with
+// the file's length in bytes, then the file and zero bytes up to ceil(cap / 4) words. A file longer
+// than cap gives length 0 and nothing is written behind the length word of that row; other rows are
+// unaffected. Words past nfront + 1 + ceil(cap / 4) of a row and rows >= B are not written.
+// The first kJpegHeaderBytes bytes of every file are `hdr` (device), whose quantisation tables the
+// kernels use; h_hdr is the host copy, checked here against H, W, quality and sampling. Four launches:
+// coefficients per MCU row, bit offsets per picture, the bits ORed into the picture's zeroed stream
+// (the kernels clear what they OR into, every launch), byte stuffing and the row. OR is commutative
+// and every sum is an integer: launches are byte-identical.
+// inp / hdr / h_hdr / out / work null (front: only with nfront > 0), out / front / work not aligned to
+// 4 / 4 / 16 bytes, B outside 1..65535, H or W outside 1..kJpegEncMaxSide, quality outside 1..100,
+// sampling not 0 (4:4:4) or 1 (4:2:0), cap outside 1..kJpegEncMaxCap, ldi < H*W*3, nfront < 0,
+// ldf < nfront, ldo < nfront + 1 + ceil(cap / 4), or a header that is not the one of these arguments
+// are hipErrorInvalidValue, and nothing is launched.
+constexpr int kJpegHeaderBytes = 623;
+constexpr int kJpegEncMaxSide = 1024;
+constexpr int kJpegEncMaxCap = 1 << 24;
+struct JpegEncodeArgs {
+  const uint8_t* inp;     // pictures [H][W][3], packed rows; picture b at inp + b * ldi
+  const uint8_t* hdr;     // device: the kJpegHeaderBytes bytes in front of the scan
+  const uint8_t* h_hdr;   // HOST copy of hdr (checked here, never followed on the device)
+  const uint32_t* front;  // [B][ldf] words in front of each row's length word, or null
+  uint32_t* out;          // [B][ldo] words
+  void* work;             // jpeg_encode_workspace(B, H, W, sampling, cap) bytes, 16-byte aligned
+  int64_t ldi;            // bytes between pictures
+  int B, H, W, quality, sampling, cap, ldo, nfront, ldf;
+};
+size_t jpeg_encode_workspace(int B, int H, int W, int sampling, int cap);
+hipError_t jpeg_encode(const JpegEncodeArgs& a, hipStream_t s);
+
 // PIL-exact NEAREST resize of one uint8 HWC RGB image into slot `b` of a
 // [B][OH][OW][3] uint8 batch, using host-built index tables.
 struct ResizeArgs {

@@ -37,6 +37,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_ATTN_ROLLOUT: return attn_rollout(op.ar, s);
     case OP_ROLLOUT_MAP: return rollout_map(op.rm, s);
     case OP_HEAT_OVERLAY: return heat_overlay(op.ho, s);
+    case OP_JPEG_ENCODE: return jpeg_encode(op.je, s);
   }
   return hipErrorInvalidValue;
 }

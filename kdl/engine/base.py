@@ -95,6 +95,43 @@ def pack_overlay(classes, scores, heat, pictures):
     return rows
 
 
+def overlay_jpeg_cap(S: int, max_bytes: int | None = None) -> int:
+    """Bytes an overlay_jpeg row keeps for the file of an S x S picture: ``max_bytes``, or ceil(S*S*3/2)."""
+    return int(max_bytes) if max_bytes is not None else (S * S * 3 + 1) // 2
+
+
+def unpack_overlay_jpeg(rows, h: int, w: int, max_bytes: int) -> tuple:
+    """Packed overlay_jpeg rows [n, 2 + h*w + 1 + ceil(max_bytes/4)] (a torch tensor or numpy array of 32-bit
+    words) -> (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], files: a list of n bytes objects, a
+    row's length word of them; b"" for a file that did not fit)."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    front = 2 + h * w
+    assert a.ndim == 2 and a.shape[1] == front + 1 + (max_bytes + 3) // 4, (a.shape, h, w, max_bytes)
+    lens = np.ascontiguousarray(a[:, front]).view(np.int32)
+    body = np.ascontiguousarray(a[:, front + 1:]).view(np.uint8).reshape(a.shape[0], -1)
+    assert ((0 <= lens) & (lens <= max_bytes)).all(), lens
+    return unpack_explain(a[:, :front], h, w) + ([body[i, :n].tobytes() for i, n in enumerate(lens)],)
+
+
+def pack_overlay_jpeg(classes, scores, heat, files, max_bytes: int):
+    """The inverse of ``unpack_overlay_jpeg``: numpy rows of fp32 words, the bytes behind a file 0. A file
+    longer than ``max_bytes`` is an overflow row: length 0 and no bytes."""
+    import numpy as np
+    front = pack_explain(classes, scores, heat)
+    n, f = front.shape
+    rows = np.zeros((n, f + 1 + (max_bytes + 3) // 4), dtype=np.float32)
+    rows[:, :f] = front
+    by = rows.view(np.uint8)
+    for i, data in enumerate(files):
+        if len(data) > max_bytes:
+            continue
+        rows.view(np.int32)[i, f] = len(data)
+        by[i, 4 * (f + 1):4 * (f + 1) + len(data)] = np.frombuffer(bytes(data), np.uint8)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -123,14 +160,30 @@ class Overlay:
     filter: str = "bilinear"
 
 
+@dataclass(frozen=True)
+class OverlayJpeg:
+    """The rendered overlay as a baseline JPEG file (``EngineBase(overlay=..., overlay_jpeg=...)``):
+    ``quality`` 1..100, ``subsampling`` "4:4:4" | "4:2:0", at most ``max_bytes`` per file (None =
+    ceil(S*S*3/2)). kdl/serving/jpeg_encode.py defines the rule."""
+    quality: int = 85
+    subsampling: str = "4:2:0"
+    max_bytes: int | None = None
+
+
 class EngineBase:
     model_name = "model"
     # tail step kind -> the method that emits it; every other kind is the family's (_emit)
     TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
-                     "explain": "_emit_explain", "overlay": "_emit_overlay"}
+                     "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
-                 explain: bool = False, rollout: bool = False, overlay: Overlay | None = None):
+                 explain: bool = False, rollout: bool = False, overlay: Overlay | None = None,
+                 overlay_jpeg: OverlayJpeg | None = None):
+        if overlay_jpeg is not None:
+            if overlay is None:
+                raise ValueError("overlay_jpeg encodes the rendered overlay: it needs overlay=Overlay(...)")
+            from ..serving.jpeg_encode import check as check_jpeg
+            check_jpeg(overlay_jpeg)
         if overlay is not None:      # before anything touches the device
             if not (explain or rollout):
                 raise ValueError("overlay paints a heatmap: it needs explain=True or rollout=True")
@@ -179,6 +232,11 @@ class EngineBase:
         # S x S x 3 picture bytes, written by one more step behind the map's (_enable_overlay)
         self.overlay: Overlay | None = overlay
         self._overlay_tabs: dict = {}                 # overlay only: device tables and their host copies
+        # overlays as JPEG files: None = the rows carry the picture bytes; an ``OverlayJpeg`` = the steps
+        # above write those raw rows into a device-only buffer, and one more step writes narrow output rows:
+        # the raw row's front words, a length word and the encoded file (_enable_overlay_jpeg)
+        self.overlay_jpeg: OverlayJpeg | None = overlay_jpeg
+        self._jpeg: dict = {}                         # overlay_jpeg only: header, cap, per-slot raw rows and workspaces
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -190,7 +248,10 @@ class EngineBase:
         return bool(self.topk or self.embed or self.similar or self.explain or self.rollout)
 
     def _out_rows(self) -> torch.Tensor:
-        """The output rows of the slot the program being built writes."""
+        """The rows the tail steps of the program being built write: the slot's output rows, or with
+        ``overlay_jpeg`` the slot's raw overlay rows, which never leave the device."""
+        if self._jpeg:
+            return self._jpeg_slot(self._slot)[0]
         return self.outputs[self._slot] if self.outputs else self.logits
 
     def output_ptr(self) -> int:
@@ -214,6 +275,7 @@ class EngineBase:
         hw = self._enable_heatmap()
         if hw:
             self._enable_overlay(*hw)
+            self._enable_overlay_jpeg(*hw)
 
     def _enable_heatmap(self) -> tuple:
         """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
@@ -437,6 +499,58 @@ class EngineBase:
             h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
             ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], a=t["a"], blend=t["blend"]))
 
+    # ---------------------------------------------------------------- overlays as JPEG files
+    def _enable_overlay_jpeg(self, h: int, w: int) -> None:
+        """Called by ``_enable_outputs`` behind ``_enable_overlay``. With ``overlay_jpeg`` the wide rows
+        that step made stay on the device (one buffer per slot; ``class_map`` / ``rollout_map`` / ``overlay``
+        write them as before, through ``_out_rows``), and one more step "overlay_jpeg"
+        (kernels/jpeg_encode.hip) writes the output rows: the 2 + h*w front words copied from the raw row,
+        a length word, then the file in ceil(max_bytes/4) words, the bytes behind it 0
+        (``unpack_overlay_jpeg``). The file header is built here, once, and kept on the device."""
+        if self.overlay_jpeg is None:
+            return
+        assert not self.inputs, "overlay_jpeg is set at construction, before input slots exist"
+        from ..serving import jpeg_encode as J
+        lib = _lib.lib()
+        S, spec = self.inp.shape[1], self.overlay_jpeg
+        cap = overlay_jpeg_cap(S, spec.max_bytes)
+        if S > lib.JPEG_ENC_MAX_SIDE or cap > lib.JPEG_ENC_MAX_CAP:
+            raise ValueError(f"overlay_jpeg: a {S} x {S} picture in at most {cap} bytes; the kernel takes sides up "
+                             f"to {lib.JPEG_ENC_MAX_SIDE} and {lib.JPEG_ENC_MAX_CAP} bytes")
+        import numpy as np
+        host = np.frombuffer(J.header(S, S, spec.quality, spec.subsampling), np.uint8).copy()
+        sampling = J.SUBSAMPLINGS.index(spec.subsampling)
+        self._jpeg = dict(cap=cap, hw=(h, w), sampling=sampling, host=host, dev=torch.from_numpy(host).to(self.device),
+                          work=lib.jpeg_encode_workspace(self.max_batch, S, S, sampling, cap),
+                          slots=[(self.logits, None)])
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + 1 + (cap + 3) // 4), dtype=torch.float32,
+                                  device=self.device)
+        self.steps.append(Step("overlay_jpeg", "overlay_jpeg"))
+
+    def _jpeg_slot(self, slot: int) -> tuple:
+        """(raw overlay rows, encoder workspace) of a slot, both device-only."""
+        sl = self._jpeg["slots"]
+        while len(sl) <= slot:
+            sl.append((torch.zeros_like(sl[0][0]), None))
+        if sl[slot][1] is None:
+            sl[slot] = (sl[slot][0], torch.zeros(self._jpeg["work"], dtype=torch.uint8, device=self.device))
+        return sl[slot]
+
+    def overlay_raw(self, slot: int = 0) -> torch.Tensor:
+        """The raw overlay rows (``unpack_overlay``) of the last forward of an ``overlay_jpeg`` engine in ``slot``."""
+        return self._jpeg_slot(slot)[0]
+
+    def _emit_overlay_jpeg(self, prog, step: Step, b: int) -> None:
+        j, (h, w), S = self._jpeg, self._jpeg["hw"], self.inp.shape[1]
+        raw, work = self._jpeg_slot(self._slot)
+        out = self.slot_logits(self._slot)
+        front = 2 + h * w
+        prog.add_jpeg_encode(step.name, dict(
+            inp=_lib.ptr(raw) + 4 * front, ldi=4 * raw.shape[1], hdr=_lib.ptr(j["dev"]), h_hdr=j["host"].ctypes.data,
+            front=_lib.ptr(raw), ldf=raw.shape[1], nfront=front, out=_lib.ptr(out), ldo=out.shape[1],
+            work=_lib.ptr(work), B=b, H=S, W=S, quality=self.overlay_jpeg.quality, sampling=j["sampling"],
+            cap=j["cap"]))
+
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
         ``rollout`` engine."""
@@ -567,7 +681,8 @@ class EngineBase:
         """x: [n, H, W, 3] in the engine's input dtype, any device -> fp32 logits [n, classes]
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
         engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
-        [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``)."""
+        [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``, with
+        ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

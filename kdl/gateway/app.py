@@ -12,7 +12,9 @@ signature of the mode; ``/overlay`` renders the map).
 the mode: the map is the 14 x 14 attention rollout of the class token.
 ``POST /overlay {"url": ...}`` -> ``image/png``: the picture the model saw with the heatmap of whatever
 method the version has painted on it (the overlay signature of the mode), label and score in the headers
-``X-KDL-Label`` / ``X-KDL-Score``; with ``"format": "json"`` -> ``{"label", "score", "heatmap", "png": "<base64>"}``.
+``X-KDL-Label`` / ``X-KDL-Score``; with ``"format": "json"`` -> ``{"label", "score", "heatmap", "png": "<base64>"}``;
+with ``"format": "jpeg"`` -> ``image/jpeg``: the file the model server encoded (the overlay_jpeg signature of the
+mode, on a version that has it), handed on byte for byte, the same two headers.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -153,12 +155,14 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         return pp.to_uint8(img)[None]
 
     def one_image(first: str, shape, formats=None):
-        """One image URL through the trio ``first`` -> shape(PredictResponse, body), or the error answer."""
+        """One image URL through the trio ``first`` (a name, or body -> name) -> shape(PredictResponse, body),
+        or the error answer."""
         body = request.get_json(silent=True)
         ok = isinstance(body, dict) and isinstance(body.get("url"), str)
         if formats:
             if not ok or body.get("format", formats[0]) not in formats:
-                return fail(400, 'request body must be JSON {"url": "<image url>", "format"?: "png" | "json"}')
+                return fail(400, 'request body must be JSON {"url": "<image url>", "format"?: ' +
+                            " | ".join(f'"{f}"' for f in formats) + "}")
         elif not ok:
             return fail(400, 'request body must be JSON {"url": "<image url>"}')
         try:
@@ -166,7 +170,7 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
         except LookupError as e:
             return fail(502, str(e))
         try:
-            req = make_request(uint8_input(img), cfg.model_name, *trio(first))
+            req = make_request(uint8_input(img), cfg.model_name, *trio(first(body) if callable(first) else first))
             pb_result = next_stub().Predict(req, timeout=cfg.timeout)
         except grpc.RpcError as e:
             return grpc_fail(e)
@@ -195,8 +199,18 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     @app.route("/overlay", methods=["POST"])
     def overlay():
         """One image through the overlay signature -> the rendered picture as a PNG (or, with
-        "format": "json", label, score, heatmap and the PNG in base64)."""
+        "format": "json", label, score, heatmap and the PNG in base64); with "format": "jpeg" through the
+        overlay_jpeg signature -> the model server's file as it is."""
         def shape(pb_result, body):
+            if body.get("format") == "jpeg":
+                ans = process_explain_response(pb_result)[0]
+                data = bytes(pb_result.outputs["jpeg_bytes"].string_val[0])
+                if not data:
+                    return fail(502, "the model server's file did not fit the version's overlay_jpeg max_bytes")
+                resp = app.response_class(data, mimetype="image/jpeg")
+                resp.headers["X-KDL-Label"] = ans["label"]
+                resp.headers["X-KDL-Score"] = repr(ans["score"])
+                return resp
             ans = process_overlay_response(pb_result)[0]
             png = png_bytes(ans.pop("picture"))
             if body.get("format") == "json":
@@ -206,7 +220,8 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             resp.headers["X-KDL-Label"] = ans["label"]
             resp.headers["X-KDL-Score"] = repr(ans["score"])
             return resp
-        return one_image("overlay", shape, formats=("png", "json"))
+        return one_image(lambda body: "overlay_jpeg" if body.get("format") == "jpeg" else "overlay", shape,
+                         formats=("png", "json", "jpeg"))
 
     @app.route("/predict_batch", methods=["POST"])
     def predict_batch():

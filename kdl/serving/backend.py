@@ -121,6 +121,9 @@ class ModelSource:
     gallery_lock: object = field(default_factory=threading.Lock)
     # rendered overlays (serving/overlay.py): the version's engine.base.Overlay (None = no overlay signatures)
     overlay: object = None
+    # overlays as JPEG files (serving/jpeg_encode.py): the version's engine.base.OverlayJpeg (None = no
+    # overlay_jpeg signatures)
+    overlay_jpeg: object = None
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -142,7 +145,8 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      classify_top_k: int | None = None, embedding_normalize: str | None = None,
                      similar_top_k: int | None = None, gallery: bool = True,
-                     overlay_colormap: str | None = None, overlay_alpha: float | None = None) -> ModelSource:
+                     overlay_colormap: str | None = None, overlay_alpha: float | None = None,
+                     overlay_jpeg_quality: int | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
@@ -151,7 +155,9 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py);
     ``gallery=False`` leaves the version's gallery files alone (the tool that writes them);
     ``overlay_colormap`` / ``overlay_alpha`` (--overlay_colormap, --overlay_alpha) override the
-    version's "overlay" block (serving/overlay.py)."""
+    version's "overlay" block (serving/overlay.py); ``overlay_jpeg_quality`` (--overlay_jpeg_quality) turns
+    the overlay_jpeg signatures on and overrides the quality of the version's "overlay_jpeg" block
+    (serving/jpeg_encode.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -163,7 +169,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
-    from . import classify, embed, explain, overlay, rollout, similar
+    from . import classify, embed, explain, jpeg_encode, overlay, rollout, similar
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
@@ -171,6 +177,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     explain.add_signatures(src, path)
     rollout.add_signatures(src, path)
     overlay.add_signatures(src, path, overlay_colormap, overlay_alpha)
+    jpeg_encode.add_signatures(src, path, overlay_jpeg_quality)
     return src
 
 

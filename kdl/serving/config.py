@@ -102,6 +102,9 @@ class ServerConfig:
     # version's own "overlay": {"colormap": ..., "alpha": ...}, else jet and 0.5
     overlay_colormap: str | None = None
     overlay_alpha: float | None = None
+    # quality of the overlay_jpeg signatures (serving/jpeg_encode.py), 1..100; set, it also turns them on for
+    # a version without an "overlay_jpeg" block; None = the version's own block decides
+    overlay_jpeg_quality: int | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -215,6 +218,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="strength of the heat on the picture of the overlay signatures, 0..1; overrides the model "
                          "version's \"overlay\": {\"alpha\": ...} (env KDL_OVERLAY_ALPHA, default: the version's, "
                          "else 0.5)")
+    ap.add_argument("--overlay_jpeg_quality", type=int, default=None,
+                    help="JPEG quality 1..100 of the overlay_jpeg / overlay_jpeg_image / overlay_jpeg_bytes signatures; "
+                         "turns them on and overrides the model version's \"overlay_jpeg\": {\"quality\": ...} (env "
+                         "KDL_OVERLAY_JPEG_QUALITY, default: the version's block, without one no such signatures)")
     ap.add_argument("--similar_top_k", type=int, default=None,
                     help="gallery items and scores per image of the similar / similar_image / similar_bytes "
                          "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
@@ -285,6 +292,9 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         overlay_colormap=a.overlay_colormap or env.get("KDL_OVERLAY_COLORMAP") or None,
                         overlay_alpha=(a.overlay_alpha if a.overlay_alpha is not None
                                        else float(env["KDL_OVERLAY_ALPHA"]) if env.get("KDL_OVERLAY_ALPHA") else None),
+                        overlay_jpeg_quality=(a.overlay_jpeg_quality if a.overlay_jpeg_quality is not None
+                                              else int(env["KDL_OVERLAY_JPEG_QUALITY"])
+                                              if env.get("KDL_OVERLAY_JPEG_QUALITY") else None),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

@@ -291,6 +291,17 @@ def classify_outputs(s, sig, rows) -> tuple[list[list[str]], np.ndarray]:
     return labels, scores
 
 
+def _strings(values):
+    """The elements of a DT_STRING column in order: a flat list of bytes, or nested lists of str."""
+    for v in values:
+        if isinstance(v, bytes):
+            yield v
+        elif isinstance(v, str):
+            yield v.encode()
+        else:
+            yield from _strings(v)
+
+
 def predict_response(s, sig, rows, output_filter) -> bytes:
     """The PredictResponse of an answered request. A kind with named outputs (serving/outputs.py):
     every column, or the subset ``output_filter`` names, strings as ``string_val``, floats as
@@ -311,12 +322,13 @@ def predict_response(s, sig, rows, output_filter) -> bytes:
         t = resp.outputs[key]
         t.dtype = dtype
         if dtype == P.DT_STRING:
-            t.string_val.extend(v.encode() for row in values for v in row)
+            t.string_val.extend(_strings(values))
         elif dtype == P.DT_UINT8:
             t.tensor_content = values.tobytes()
         else:
             t.float_val.extend(values.reshape(-1).tolist())
-        for d in np.shape(values):
+        for d in ((len(values),) if isinstance(values, list) and values and isinstance(values[0], bytes)
+                  else np.shape(values)):
             t.tensor_shape.dim.add(size=d)
     return resp.SerializeToString()
 

@@ -1,7 +1,8 @@
 """One description per kind of result row.
 
-A signature answers with one of seven kinds of row: the fp32 ``logits``, or what the ``classify``,
-``embed``, ``similar``, ``explain``, ``attention`` and ``overlay`` trios pack into the same fp32 words.
+A signature answers with one of eight kinds of row: the fp32 ``logits``, or what the ``classify``,
+``embed``, ``similar``, ``explain``, ``attention``, ``overlay`` and ``overlay_jpeg`` trios pack into the same
+fp32 words.
 Everything that differs between the kinds is in ``KINDS``; runners, executors, answer builders and the
 loader ask the table and name no kind. Per kind:
 
@@ -15,8 +16,8 @@ loader ask the table and name no kind. Per kind:
   host_step  (sig, src, rows) -> packed rows, applied after ``_run`` where no engine packed them
              (CPU and null device); None = the executor's rows are the answer
   null_zero  the null device's rows are zeroed (class 0, score 0, an empty map)
-  columns    (src, sig, rows) -> the named outputs [(key, dtype, array or nested list of strings)];
-             None = the single fp32 output, built natively
+  columns    (src, sig, rows) -> the named outputs [(key, dtype, array, nested list of strings or flat
+             list of bytes)]; None = the single fp32 output, built natively
 """
 from __future__ import annotations
 
@@ -28,8 +29,8 @@ from typing import Callable
 import numpy as np
 import torch
 
-from ..engine.base import overlay_words
-from . import classify, embed, explain, overlay, rollout, similar
+from ..engine.base import overlay_jpeg_cap, overlay_words
+from . import classify, embed, explain, jpeg_encode, overlay, rollout, similar
 from . import protos as P
 from .jpeg import BYTES_SIGNATURE
 from .metrics import METRICS
@@ -48,6 +49,10 @@ def _similar_kw(sig, src, dev) -> dict:
 def _map_kw(sig, src, dev) -> dict:
     kw = dict(rollout=True) if sig.rollout else dict(explain=True)
     return dict(kw, overlay=src.overlay) if sig.overlay else kw
+
+
+def _jpeg_kw(sig, src, dev) -> dict:
+    return dict(_map_kw(sig, src, dev), overlay_jpeg=src.overlay_jpeg)
 
 
 # ---------------------------------------------------------------------- CPU executor rows
@@ -78,11 +83,28 @@ def _map_rows(sig, src, x):
     if not sig.overlay:
         return explain.pack_rows(k, score, heat)
     pics = [overlay.overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat)]
-    return overlay.pack_rows(k, score, heat, np.stack(pics))
+    if not _is_jpeg(sig):
+        return overlay.pack_rows(k, score, heat, np.stack(pics))
+    spec = src.overlay_jpeg
+    files = [jpeg_encode.encode_rule(p, spec.quality, spec.subsampling) for p in pics]
+    return jpeg_encode.pack_rows(k, score, heat, files, _jpeg_cap(sig, src))
 
 
 def _map_words(sig, src) -> int:
     return 2 + sig.explain[0] * sig.explain[1] + (overlay_words(sig.overlay) if sig.overlay else 0)
+
+
+def _is_jpeg(sig) -> bool:
+    """An overlay signature whose last output is a DT_STRING answers the picture as a file."""
+    return bool(sig.overlay and sig.outputs and sig.outputs[-1][1] == P.DT_STRING)
+
+
+def _jpeg_cap(sig, src) -> int:
+    return overlay_jpeg_cap(sig.overlay, src.overlay_jpeg.max_bytes)
+
+
+def _jpeg_words(sig, src) -> int:
+    return 2 + sig.explain[0] * sig.explain[1] + 1 + (_jpeg_cap(sig, src) + 3) // 4
 
 
 # ---------------------------------------------------------------------- named output columns
@@ -93,16 +115,29 @@ def _ranked(names: Callable):
     return columns
 
 
-def _map_columns(src, sig, rows) -> list:
+def _front_columns(src, classes, scores, heat) -> list:
     """A class index outside the label list (the null device's rows) is answered as its decimal."""
+    lab = src.labels
+    return [("classes", P.DT_STRING, [[lab[int(c)] if 0 <= int(c) < len(lab) else str(int(c))] for c in classes]),
+            ("scores", P.DT_FLOAT, scores.reshape(-1, 1)), ("heatmap", P.DT_FLOAT, heat)]
+
+
+def _map_columns(src, sig, rows) -> list:
     if sig.overlay:
         classes, scores, heat, pics = overlay.unpack_rows(rows, *sig.explain, sig.overlay)
     else:
         classes, scores, heat = explain.unpack_rows(rows, *sig.explain)
-    lab = src.labels
-    cols = [("classes", P.DT_STRING, [[lab[int(c)] if 0 <= int(c) < len(lab) else str(int(c))] for c in classes]),
-            ("scores", P.DT_FLOAT, scores.reshape(-1, 1)), ("heatmap", P.DT_FLOAT, heat)]
+    cols = _front_columns(src, classes, scores, heat)
     return cols + [("overlay", P.DT_UINT8, pics)] if sig.overlay else cols
+
+
+def _jpeg_columns(src, sig, rows) -> list:
+    """The map's three outputs and each row's file; a row whose file did not fit answers b""."""
+    classes, scores, heat, files = jpeg_encode.unpack_rows(rows, *sig.explain, _jpeg_cap(sig, src))
+    lost = sum(not f for f in files)
+    if lost:
+        METRICS.inc("kdl_overlay_jpeg_overflow_total", lost, signature=sig.name)
+    return _front_columns(src, classes, scores, heat) + [("jpeg_bytes", P.DT_STRING, files)]
 
 
 @dataclass(frozen=True)
@@ -139,6 +174,8 @@ KINDS = {k.name: k for k in (
     Kind("explain", explain.EXPLAIN_SIGNATURES, "kdl_explain_total", **_MAP),
     Kind("attention", rollout.ATTENTION_SIGNATURES, "kdl_attention_total", **_MAP),
     Kind("overlay", overlay.OVERLAY_SIGNATURES, "kdl_overlay_total", **_MAP),
+    Kind("overlay_jpeg", jpeg_encode.OVERLAY_JPEG_SIGNATURES, "kdl_overlay_jpeg_total",
+         **dict(_MAP, engine=_jpeg_kw, gpu_words=_jpeg_words, columns=_jpeg_columns)),
 )}
 # the second and third name of every trio -> (0 any-size image / 1 encoded file, the trio's first name)
 WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate(k.trio[1:])}
@@ -146,7 +183,7 @@ WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate
 
 def kind_of(sig) -> Kind:
     """The kind of a signature's rows, from the fields SignatureInfo has."""
-    name = ("overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
+    name = ("overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
             "explain" if sig.explain else "similar" if sig.similar else "classify" if sig.top_k else
             "embed" if sig.embed else "logits")
     return KINDS[name]

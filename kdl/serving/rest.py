@@ -50,7 +50,9 @@ def predict_body(s, sig, rows, by_row: bool) -> dict:
     if cols is None:
         O.answered(sig)
         return {"predictions" if by_row else "outputs": rows.tolist()}
-    cols = [(key, v if isinstance(v, list) else v.tolist()) for key, _, v in cols]
+    # a list of bytes (a ``_bytes`` output) is answered as TF-Serving does: {"b64": ...} per element
+    cols = [(key, [{"b64": base64.b64encode(e).decode()} if isinstance(e, bytes) else e for e in v]
+             if isinstance(v, list) else v.tolist()) for key, _, v in cols]
     if by_row:
         return {"predictions": [{key: v[i] for key, v in cols} for i in range(len(rows))]}
     return {"outputs": dict(cols)}
