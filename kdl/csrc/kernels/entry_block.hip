@@ -19,17 +19,24 @@
 // row is computed once per strip; only the 2 halo columns between strips are recomputed
 // (~6 %). A run starts with two warm-up steps (y1 only; y1 + y2 without output).
 //
-// Work split (C1 / 16 waves): wave w owns output channels 16w..16w+15 of EVERY GEMM (pw1, pw2,
-// the residual 1x1), so its weights live in registers for the whole kernel and the GEMMs read
-// only activations from LDS. The depthwise convs run on the VALU (v_dot2c_f32_bf16 over tap
-// pairs, fp32 accumulate), each lane producing the 8 channels of one pixel = exactly its MFMA
-// operand fragment, written fragment-linear to an LDS A buffer. Phases per step, separated by
-// workgroup barriers: dw1 -> GEMM1 (+ residual GEMM) -> dw2 -> GEMM2 + pool (five barriers with B0).
-// TWOPH (configs 21 and 23, block3's default: 21 with both depthwise convs on the matrix cores, the
-// block-diagonal operand of sepconv_ws.hip): the same step skewed by one stage, TWO barriers per step --
-// a DW phase (dw2 of step i, dw1 + residual GEMM of step i+1) and a GEMM phase (GEMM2 + pool + output
-// of step i, GEMM1 of step i+1, the x-row DMA of step i+2 in flight); A1 and A2 are separate buffers,
-// the horizontal pool exchanges lanes (ds_bpermute) instead of LDS rows, no register is spilled.
+// A step is four dependent stages: dw1 -> GEMM1 (+ residual GEMM) -> dw2 -> GEMM2 + pool. Two kernels:
+//   entry_block_kernel     block3 (74x74x128 -> 37x37x256, ReLU on the block input): 8 waves, wave w owns
+//                          output channels 32w..32w+31 of EVERY GEMM (pw1, pw2, the residual 1x1), so its
+//                          pointwise weights live in registers for the whole kernel and the GEMMs read only
+//                          activations from LDS. Every wave runs every stage. Two loops: the four-phase loop
+//                          (config 1: a stage per barrier interval, five barriers per step with B0; depthwise
+//                          on the VALU, v_dot2c_f32_bf16 over tap pairs with fp32 accumulate, each lane the 8
+//                          channels of one pixel = its MFMA operand fragment, written fragment-linear to an
+//                          LDS A buffer) and the two-phase loop (TWOPH, configs 21 and 23: the same step
+//                          skewed by one stage, TWO barriers per step -- a DW phase (dw2 of step i, dw1 +
+//                          residual GEMM of step i+1) and a GEMM phase (GEMM2 + pool + output of step i, GEMM1
+//                          of step i+1, the x-row DMA of step i+2 in flight); A1 and A2 are separate buffers,
+//                          the horizontal pool exchanges lanes (ds_bpermute) instead of LDS rows, no register
+//                          is spilled; 23, block3's default: both depthwise convs on the matrix cores, the
+//                          block-diagonal operand of sepconv_ws.hip).
+//   entry_block_ws_kernel  block2, 16 waves in two roles that work on different steps at the same time (see
+//                          its own comment further down).
+// The table comment at the end of the file lists the configurations and what they replaced.
 //
 // LDS activation images are channel-PLANE major (16-byte slot = 8 channels of one pixel, a
 // plane = one 8-channel chunk of a row, pitch PLP px, a multiple of 16): a depthwise / MFMA
@@ -61,8 +68,9 @@ struct EbStepRegs {
 };
 static_assert(EB_MAX_STEPS <= 128, "EbStepRegs holds two words per lane");
 
-template <int C0, int C1, int PC, int NFW, bool DWM = false, bool TWOPH = false>
+template <int C0_, int C1_, int PC_, int NFW_, bool DWM, bool TWOPH>
 struct EbGeom {
+  static constexpr int C0 = C0_, C1 = C1_, PC = PC_, NFW = NFW_;
   static constexpr int Y2C = 2 * PC + 1;            // y2 columns a strip needs
   static constexpr int Y1C = Y2C + 2;               // y1 columns
   static constexpr int XC = Y1C + 2;                // x columns
@@ -183,7 +191,7 @@ __device__ __forceinline__ void eb_dw8_n(Tap tap, const uint32_t* wq, s16x8 (&ou
 // 2j + (kb >> 1) of chunk 2g + (kb & 1); tap(g, ti) -> that 16-B input; ent(g) -> the 16-B entry
 // (pack_dw_entries) of channel 16g + p16, tap parity kb >> 1. The C fragment [16 ch][16 px] is
 // written transposed into the unit's lane-linear A fragment at dst.
-template <bool RELU, class Tap, class Ent>
+template <class Tap, class Ent>
 __device__ __forceinline__ void eb_dw_mfma_vals(Tap tap, Ent ent, int lane, const uint32_t (&sel)[2][4], u32x2 (&out)[2]) {
   const int kb = lane >> 4, par = kb >> 1;
 #pragma unroll
@@ -193,11 +201,7 @@ __device__ __forceinline__ void eb_dw_mfma_vals(Tap tap, Ent ent, int lane, cons
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
       const int ti = 2 * j + par;
-      u32x4 v = ti < 9 ? tap(g, ti) : (u32x4){0u, 0u, 0u, 0u};
-      if constexpr (RELU) {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) v[d] = relu_bf16x2(v[d]);
-      }
+      const u32x4 v = ti < 9 ? tap(g, ti) : (u32x4){0u, 0u, 0u, 0u};
       const uint32_t wd = we[j >> 1];
       u32x4 wf;
 #pragma unroll
@@ -236,7 +240,7 @@ __device__ __forceinline__ u32x4 eb_dw_wop(const u32x4 we, int j, const uint32_t
 // always in the other half-wave (profiles/entry_block_rowpair.txt: 7 reads with the k-halves of row
 // r+1 exchanged changed the sums, 8 reads with v_permlane32_swap cost more VALU than the reads saved).
 // out[0] = row r, out[1] = row r+1.
-template <bool RELU, class Addr, class Wop>
+template <class Addr, class Wop>
 __device__ __forceinline__ void eb_dw_mfma_rowpair(Addr addr, Wop wop, int lane, u32x2 (&out)[2]) {
   const bool par = (lane & 32) != 0;
   u32x4 r0[5], r1[5];                                // tap operands of row r / row r+1
@@ -244,10 +248,6 @@ __device__ __forceinline__ void eb_dw_mfma_rowpair(Addr addr, Wop wop, int lane,
   for (int j = 0; j < 5; ++j) {                      // tap 9 (j 4, parity 1): any tap, its weight is 0
     r0[j] = *(const u32x4*)(par ? addr(j < 4 ? 2 * j + 1 : 8) : addr(2 * j));
     r1[j] = *(const u32x4*)(par ? addr(j < 4 ? 2 * j + 4 : 11) : addr(2 * j + 3));
-    if constexpr (RELU) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) { r0[j][d] = relu_bf16x2(r0[j][d]); r1[j][d] = relu_bf16x2(r1[j][d]); }
-    }
   }
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -322,10 +322,16 @@ __device__ __forceinline__ s16x8 eb_frag(const uint16_t* wp, int nf, int kt, int
   return *(const s16x8*)(wp + ((long)(nf * kt + t) * 64 + lane) * 8);
 }
 
-template <int C0, int C1, int PC, int NFW, int PT, bool RELU1, bool STAMP = false, bool DWM = false, int OCC = 1,
-          bool TWOPH = false>
-__global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void entry_block_kernel(EntryBlockArgs a) {
-  using G = EbGeom<C0, C1, PC, NFW, DWM, TWOPH>;
+// Block3 (even maps: the leading pad of the TF-'same' 3x3/2 pool is 0; ReLU on the block input). STAMP: the
+// diagnostics build; TWOPH: the two-phase loop (false: the four-phase loop of config 1, VALU depthwise only);
+// DWM: depthwise on the matrix cores (two-phase only)
+template <bool DWM, bool TWOPH>
+using Eb3Geom = EbGeom<128, 256, 13, 2, DWM, TWOPH>;
+template <bool STAMP, bool DWM, bool TWOPH>
+__global__ __launch_bounds__((64 * Eb3Geom<DWM, TWOPH>::NW), (Eb3Geom<DWM, TWOPH>::NW / 4)) void entry_block_kernel(EntryBlockArgs a) {
+  using G = Eb3Geom<DWM, TWOPH>;
+  static_assert(TWOPH || !DWM, "the four-phase LDS map has no room for the MFMA depthwise entries");
+  constexpr int C0 = G::C0, C1 = G::C1, PC = G::PC, NFW = G::NFW;
   constexpr int NW = G::NW, KT0 = G::KT0, KT1 = G::KT1;
   constexpr int PLB = G::PLB, XROW = G::XROW, Y1ROW = G::Y1ROW;
   constexpr int Y1C = G::Y1C, Y2C = G::Y2C, XC = G::XC, PLP = G::PLP;
@@ -334,7 +340,6 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
   constexpr int U1W = (U1 + NW - 1) / NW, U2W = (U2 + NW - 1) / NW;
   constexpr int PCH = 16 * NFW;                      // channels per wave
   static_assert(NW % KT0 == 0 && NW % KT1 == 0, "a wave's depthwise units share one k-step");
-  static_assert(PT == 0 || PT == 1, "TF-'same' 3x3/2 pool: leading pad 1 (odd size) or 0 (even)");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -353,8 +358,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
   uint32_t* const stl = (uint32_t*)(smem + G::OFF_S);
   // the step table goes to LDS once: decoding a step from global memory put an L2 round trip
   // on every step's critical path twice (measured ~3k cycles per step, tools/ebbench.py --stamps).
-  // One word per step {image 8 | strip 6 | pooled row + 2 9 | mode 2 bits}: a 2-workgroup-per-CU
-  // config then fits its 80 KiB (int4 entries took 2 KiB of it)
+  // One word per step {image 8 | strip 6 | pooled row + 2 9 | mode 2 bits}
   for (int i = tid; i < s1 - s0; i += 64 * NW) {
     const int4 e = a.steps[s0 + i];
     stl[i] = (uint32_t)e.x | ((uint32_t)e.y << 8) | ((uint32_t)(e.z + 2) << 14) | ((uint32_t)e.w << 23);
@@ -390,38 +394,8 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
   }
   for (int i = tid; i < 3 * C1; i += 64 * NW) bl[i] = (i < C1 ? a.b1 : i < 2 * C1 ? a.b2 : a.br)[i % C1];
   // this lane's 4 accumulator channels of output slice n: bias (LDS) of GEMM g (0 pw1, 1 pw2, 2 residual)
-  // 1-slice configs keep this lane's 3 x 4 biases in registers (read once from global): in LDS a
-  // bias read that follows a y1 / pool store cannot be hoisted above it, so every fragment of
-  // P2 / P4 re-read it and waited for it
-  // 16-wave configs (NW 16: 4 waves per SIMD, <= 128 VGPRs) take none of the register-hungry forms
-  constexpr bool WIDE = NFW == 1 && OCC == 1 && NW <= 8;
-  constexpr bool BREG = WIDE;
-  float4 breg[BREG ? 3 : 1][NFW];
-  if constexpr (BREG) {
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-      for (int n = 0; n < NFW; ++n)
-        breg[g][n] = *(const float4*)((g == 0 ? a.b1 : g == 1 ? a.b2 : a.br) + PCH * w + 16 * n + 4 * q16);
-  }
-  auto bias = [&](int g, int n) {
-    if constexpr (BREG) return breg[g][n];
-    else return *(const float4*)(bl + g * C1 + PCH * w + 16 * n + 4 * q16);
-  };
+  auto bias = [&](int g, int n) { return *(const float4*)(bl + g * C1 + PCH * w + 16 * n + 4 * q16); };
   const int t1 = w % KT0, t2 = w % KT1;              // every depthwise unit of this wave uses these k-steps
-  uint32_t sel[2][4];                                // DWM: v_perm selectors of the block-diagonal operand
-  {
-    const bool wv = (p16 >> 3) == (q16 & 1);
-    const int e = p16 & 7;
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp)
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const uint32_t pair = (2u * jp) | ((2u * jp + 1u) << 8);
-        const uint32_t val = (e & 1) ? (0x0c0cu | (pair << 16)) : (0x0c0c0000u | pair);
-        sel[jp][d] = (wv && (e >> 1) == d) ? val : 0x0c0c0c0cu;
-      }
-  }
   // ---- x row DMA: row r of image b, strip columns from global col gx0, into ring slot r & 3
   // (preparing the addresses ahead, before B1, measured slower: the wave runs it in order anyway)
   auto dma_rows = [&](int b, int gx0, int r0, int nr) {
@@ -434,21 +408,17 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
       glds16(src, xr + (r & 3) * XROW + d * 1024);
     }
   };
-  // register-resident step words where the registers are free (1-slice, 1-workgroup-per-CU configs:
-  // block3's and the 2-workgroup configs' allocations already spill)
-  constexpr bool REG_STEPS = NFW == 1 && OCC == 1;
-  EbStepRegs str;                                     // loaded once the table is published (below)
   auto decode = [&](int q, int& b, int& s, int& k, int& mode) {
-    const uint32_t e = REG_STEPS ? str.get(q - s0) : stl[q - s0];
+    const uint32_t e = stl[q - s0];
     b = e & 255; s = (e >> 8) & 63; k = (int)((e >> 14) & 511) - 2; mode = (e >> 23) & 3;
   };
-  // pooled row k pools y2 rows R..R+2, R = 2k - PT; a step computes y1 rows R+2, R+3 from x rows
+  // pooled row k pools y2 rows R..R+2, R = 2k; a step computes y1 rows R+2, R+3 from x rows
   // R+1..R+4: the rows its predecessor did not load (a run's first step loads all four)
   auto dma_for = [&](int q) {
     int b, s, k, mode;
     decode(q, b, s, k, mode);
-    const int R = 2 * k - PT;
-    const int gx0 = 2 * s * PC - PT - 2;
+    const int R = 2 * k;
+    const int gx0 = 2 * s * PC - 2;
     if (mode == 0) dma_rows(b, gx0, R + 1, 4);
     else dma_rows(b, gx0, R + 3, 2);
   };
@@ -473,7 +443,6 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     }
   };
   __syncthreads();                                   // step table, weights, biases in LDS
-  if constexpr (REG_STEPS) str.load(stl, s1 - s0, lane);
   dma_for(s0);
   if constexpr (TWOPH) {
     // ---- two-phase schedule (config 21): the step skewed by one stage, two barriers per step.
@@ -488,7 +457,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     // y1 ring slots are counted by steps: step j writes its rows R+2, R+3 into pair j & 1 and reads
     // R, R+1 from the other pair (its predecessor's), so the rows of two runs walked back to back
     // never meet in a slot whatever their row numbers are.
-    static_assert(!WIDE && PT == 0 && Y2FR == 2 && U1 % NW == 0 && NW == KT1,
+    static_assert(Y2FR == 2 && U1 % NW == 0 && NW == KT1,
                   "two-phase schedule: block3's two-slice build (a wave's dw2 units: one k-step)");
     uint8_t* const A2 = Ab;
     uint8_t* const A1 = smem + G::OFF_A1;
@@ -620,7 +589,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
 #pragma unroll
             for (int j = 0; j < 5; ++j) wk[j] = eb_dw_wop(we, j, sel);
             u32x2 o[2];
-            eb_dw_mfma_two<RELU1>(ad[0], ad[1], 2 * g * PLB, [&](int j) { return wk[j]; }, o);
+            eb_dw_mfma_two<true>(ad[0], ad[1], 2 * g * PLB, [&](int j) { return wk[j]; }, o);
             dv[0][g] = o[0];
             dv[1][g] = o[1];
           }
@@ -632,7 +601,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
             return *(const u32x4*)(base[i] + ((row[i] - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
           };
           s16x8 o1[U1W];
-          eb_dw8_n<RELU1, U1W>(tap, wq, o1);
+          eb_dw8_n<true, U1W>(tap, wq, o1);
 #pragma unroll
           for (int i = 0; i < U1W; ++i) *(s16x8*)(A1 + (t1 * Y1F + (w + NW * i) / KT0) * 1024 + lane * 16) = o1[i];
         }
@@ -783,10 +752,10 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
   for (int q = s0; q < s1; ++q) {
     int b, s, k, mode;
     decode(q, b, s, k, mode);
-    const int R = 2 * k - PT;
+    const int R = 2 * k;
     const int pc0 = s * PC;
-    // the residual this step's output adds: PT 1 computes it below (x row 2k is in the ring);
-    // PT 0 computed it in the previous step (x row 2k has left the ring by now)
+    // the residual this step's output adds was computed in the previous step (x row 2k has left the ring
+    // by now)
     f32x4 acco[NFW];
 #pragma unroll
     for (int n = 0; n < NFW; ++n) acco[n] = accr[n];
@@ -795,15 +764,10 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
 
     stamp(q, 0);
 
-    // ---- P1: depthwise 1 -> A (y1 rows R+2, R+3); residual operands: pooled row k (PT 1: x row
-    // 2k = R+1) or k+1 (PT 0: x row 2k+2 = R+2; x row 2k is no longer in the ring)
+    // ---- P1: depthwise 1 -> A (y1 rows R+2, R+3); residual operands: pooled row k+1 (x row 2k+2 = R+2;
+    // x row 2k is no longer in the ring)
     {
       const uint32_t* wq = dwl + (t1 * 4 + q16) * 40;
-      u32x2 dv[U1W][2];                              // every unit's outputs, stored after the loop
-      s16x8 vv[U1W];
-      uint8_t* ddst[U1W];
-#pragma unroll
-      for (int i = 0; i < U1W; ++i) ddst[i] = nullptr;
 #pragma unroll
       for (int i = 0; i < U1W; ++i) {
         const int u = w + NW * i;
@@ -813,41 +777,17 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
           pi = pi < 2 * Y1C ? pi : 2 * Y1C - 1;
           const int rr = pi >= Y1C, col = pi - rr * Y1C;
           const int row = R + 2 + rr;
-          if constexpr (DWM) {
-            const uint8_t* base = xr + (4 * t1 + (q16 & 1)) * PLB + col * 16;
-            auto tap = [&](int g, int ti) {
-              return *(const u32x4*)(base + 2 * g * PLB + ((row - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
-            };
-            auto ent = [&](int g) {
-              return *(const u32x4*)((const uint8_t*)dwl + t1 * G::DWQ + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
-            };
-            eb_dw_mfma_vals<RELU1>(tap, ent, lane, sel, dv[i]);
-            ddst[i] = Ab + (t1 * Y1F + f) * 1024;
-          } else {
-            const uint8_t* base = xr + (4 * t1 + q16) * PLB + col * 16;
-            auto tap = [&](int ti) {
-              return *(const u32x4*)(base + ((row - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
-            };
-            // 1-slice configs store after the loop (see eb_dw_store); block3's register-bound
-            // config stores at once (the deferred form spilled 67 VGPRs there)
-            if constexpr (WIDE) {
-              vv[i] = eb_dw8<RELU1>(tap, wq);
-              ddst[i] = Ab + (t1 * Y1F + f) * 1024 + lane * 16;
-            } else {
-              *(s16x8*)(Ab + (t1 * Y1F + f) * 1024 + lane * 16) = eb_dw8<RELU1>(tap, wq);
-            }
-          }
+          const uint8_t* base = xr + (4 * t1 + q16) * PLB + col * 16;
+          auto tap = [&](int ti) {
+            return *(const u32x4*)(base + ((row - 1 + ti / 3) & 3) * XROW + (ti % 3) * 16);
+          };
+          // stored at once (the deferred form spilled 67 VGPRs)
+          *(s16x8*)(Ab + (t1 * Y1F + f) * 1024 + lane * 16) = eb_dw8<true>(tap, wq);
         }
       }
-#pragma unroll
-      for (int i = 0; i < U1W; ++i) {
-        if (!ddst[i]) continue;
-        if constexpr (DWM) eb_dw_store(ddst[i], lane, dv[i]);
-        else *(s16x8*)ddst[i] = vv[i];
-      }
     }
-    if (PT == 1 ? mode == 2 : mode >= 1) {           // residual 1x1/2 conv of its pooled row
-      const int xrow = R + 2 - PT, xcol = 2 * p16 + PT + 2;
+    if (mode >= 1) {                                 // residual 1x1/2 conv of its pooled row
+      const int xrow = R + 2, xcol = 2 * p16 + 2;
 #pragma unroll
       for (int n = 0; n < NFW; ++n) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -855,7 +795,6 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
         for (int t = 0; t < KT0; ++t)
           acc = mfma16(wr[n][t], *(const s16x8*)(xr + (xrow & 3) * XROW + (4 * t + q16) * PLB + xcol * 16), acc);
         accr[n] = acc;
-        if (PT == 1) acco[n] = acc;
       }
     }
     eb_lds_barrier();                                // B1: A (y1) complete; x ring free for the next DMA
@@ -869,18 +808,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     if (q + 1 < s1) dma_for(q + 1);
 
     // ---- P2: GEMM1 (+ bias, ReLU) -> y1 ring rows R+2, R+3; residual GEMM
-    // HOIST (1-slice configs, registers to spare): every A fragment is read before the first y1
-    // store -- the compiler cannot move a read above a store it cannot prove disjoint, which
-    // chained each fragment's LDS latency behind the previous fragment's store
-    constexpr bool HOIST = WIDE;
-    s16x8 a1h[HOIST ? Y1F : 1][KT0];
-    if constexpr (HOIST) {
-#pragma unroll
-      for (int f = 0; f < Y1F; ++f)
-#pragma unroll
-        for (int t = 0; t < KT0; ++t) a1h[f][t] = *(const s16x8*)(Ab + (t * Y1F + f) * 1024 + lane * 16);
-    }
-    float4 bz0[NFW];                                 // read before the y1 stores (see BREG)
+    float4 bz0[NFW];                                 // read before the y1 stores
 #pragma unroll
     for (int n = 0; n < NFW; ++n) bz0[n] = bias(0, n);
 #pragma unroll
@@ -888,13 +816,13 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
       const s16x8* af = (const s16x8*)(Ab + f * 1024 + lane * 16);
       const int pi = 16 * f + p16;
       const int rr = pi >= Y1C, col = pi - rr * Y1C;
-      const int row = R + 2 + rr, gcol = 2 * pc0 - PT - 1 + col;
+      const int row = R + 2 + rr, gcol = 2 * pc0 - 1 + col;
       const bool ok = (unsigned)row < (unsigned)H && (unsigned)gcol < (unsigned)W;
 #pragma unroll
       for (int n = 0; n < NFW; ++n) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int t = 0; t < KT0; ++t) acc = mfma16(w1[n][t], HOIST ? a1h[HOIST ? f : 0][t] : af[t * Y1F * 64], acc);
+        for (int t = 0; t < KT0; ++t) acc = mfma16(w1[n][t], af[t * Y1F * 64], acc);
         if (pi < 2 * Y1C) {
           const int c = PCH * w + 16 * n + 4 * q16;
           const float4 bv = bz0[n];
@@ -912,11 +840,6 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     // ---- P3: depthwise 2 -> A (y2 rows R+1, R+2: fragments [row][col / 16])
     {
       const uint32_t* wq = dwl + ((KT0 + t2) * 4 + q16) * 40;
-      u32x2 dv2[U2W][2];
-      s16x8 vv2[U2W];
-      uint8_t* ddst2[U2W];
-#pragma unroll
-      for (int i = 0; i < U2W; ++i) ddst2[i] = nullptr;
 #pragma unroll
       for (int i = 0; i < U2W; ++i) {
         const int u = w + NW * i;
@@ -924,35 +847,12 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
           const int f = u / KT1;
           const int rr = f / Y2FR, col = (f % Y2FR) * 16 + p16;
           const int row = R + 1 + rr;
-          if constexpr (DWM) {
-            const uint8_t* base = y1r + (4 * t2 + (q16 & 1)) * PLB + col * 16;
-            auto tap = [&](int g, int ti) {
-              return *(const u32x4*)(base + 2 * g * PLB + ((row - 1 + ti / 3) & 3) * Y1ROW + (ti % 3) * 16);
-            };
-            auto ent = [&](int g) {
-              return *(const u32x4*)((const uint8_t*)dwl + (KT0 + t2) * G::DWQ + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
-            };
-            eb_dw_mfma_vals<false>(tap, ent, lane, sel, dv2[i]);
-            ddst2[i] = Ab + (t2 * Y2F + f) * 1024;
-          } else {
-            const uint8_t* base = y1r + (4 * t2 + q16) * PLB + col * 16;
-            auto tap = [&](int ti) {
-              return *(const u32x4*)(base + ((row - 1 + ti / 3) & 3) * Y1ROW + (ti % 3) * 16);
-            };
-            if constexpr (WIDE) {
-              vv2[i] = eb_dw8<false>(tap, wq);
-              ddst2[i] = Ab + (t2 * Y2F + f) * 1024 + lane * 16;
-            } else {
-              *(s16x8*)(Ab + (t2 * Y2F + f) * 1024 + lane * 16) = eb_dw8<false>(tap, wq);
-            }
-          }
+          const uint8_t* base = y1r + (4 * t2 + q16) * PLB + col * 16;
+          auto tap = [&](int ti) {
+            return *(const u32x4*)(base + ((row - 1 + ti / 3) & 3) * Y1ROW + (ti % 3) * 16);
+          };
+          *(s16x8*)(Ab + (t2 * Y2F + f) * 1024 + lane * 16) = eb_dw8<false>(tap, wq);
         }
-      }
-#pragma unroll
-      for (int i = 0; i < U2W; ++i) {
-        if (!ddst2[i]) continue;
-        if constexpr (DWM) eb_dw_store(ddst2[i], lane, dv2[i]);
-        else *(s16x8*)ddst2[i] = vv2[i];
       }
     }
     eb_lds_barrier();                                // B3: A (y2) complete
@@ -961,13 +861,6 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     // ---- P4: GEMM2 + bias -> bf16 values; vertical max with the carried row
     const bool r0ok = (unsigned)R < (unsigned)H && mode == 2, r1ok = (unsigned)(R + 1) < (unsigned)H;
     const bool r2ok = (unsigned)(R + 2) < (unsigned)H;
-    s16x8 a2h[HOIST ? Y2F : 1][KT1];                 // HOIST: every fragment read before the pool stores
-    if constexpr (HOIST) {
-#pragma unroll
-      for (int f = 0; f < Y2F; ++f)
-#pragma unroll
-        for (int t = 0; t < KT1; ++t) a2h[f][t] = *(const s16x8*)(Ab + (t * Y2F + f) * 1024 + lane * 16);
-    }
     float4 bz1[NFW];                                 // read before the pool stores
 #pragma unroll
     for (int n = 0; n < NFW; ++n) bz1[n] = bias(1, n);
@@ -975,15 +868,15 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
     for (int fc = 0; fc < Y2FR; ++fc) {
       const s16x8* a0 = (const s16x8*)(Ab + fc * 1024 + lane * 16);
       const s16x8* a1 = (const s16x8*)(Ab + (Y2FR + fc) * 1024 + lane * 16);
-      const int col = fc * 16 + p16, gcol = 2 * pc0 - PT + col;
+      const int col = fc * 16 + p16, gcol = 2 * pc0 + col;
       const bool cok = col < Y2C && (unsigned)gcol < (unsigned)W;
 #pragma unroll
       for (int n = 0; n < NFW; ++n) {
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < KT1; ++t) {
-          acc0 = mfma16(w2[n][t], HOIST ? a2h[HOIST ? fc : 0][t] : a0[t * Y2F * 64], acc0);
-          acc1 = mfma16(w2[n][t], HOIST ? a2h[HOIST ? Y2FR + fc : 0][t] : a1[t * Y2F * 64], acc1);
+          acc0 = mfma16(w2[n][t], a0[t * Y2F * 64], acc0);
+          acc1 = mfma16(w2[n][t], a1[t * Y2F * 64], acc1);
         }
         float vm[4];
         const float4 b4 = bz1[n];
@@ -1007,7 +900,7 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
       }
     }
     stamp(q, 4);
-    if (mode == 1) continue;                         // warm-up 2: carry (+ PT 0: residual) only
+    if (mode == 1) continue;                         // warm-up 2: carry and residual only
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // own pool rows only: no barrier
     // horizontal 3/2 max: pooled column j reads y2 local cols 2j .. 2j+2
     const int j = p16, gj = pc0 + j;
@@ -1056,8 +949,9 @@ __global__ __launch_bounds__(64 * (C1 / (16 * NFW)), OCC * C1 / (64 * NFW)) void
 // keep the map at 142 KiB
 // (pitch 32 px, no padding). A consumer wave owns 32 output channels of every GEMM (register-resident
 // weights); a producer wave owns a quarter of each step's depthwise units.
-template <int C0, int C1, int PC, int NWAV, int NCW = NWAV / 2>
+template <int C0_, int C1_, int PC_, int NWAV_, int NCW>
 struct EbwGeom {
+  static constexpr int C0 = C0_, C1 = C1_, PC = PC_, NWAV = NWAV_;
   static constexpr int Y2C = 2 * PC + 1, Y1C = Y2C + 2, XC = Y1C + 2;
   static constexpr int PLP = (XC + 15) / 16 * 16, PLB = PLP * 16;
   static constexpr int XROW = (C0 / 8) * PLB, Y1ROW = (C1 / 8) * PLB;
@@ -1079,11 +973,6 @@ struct EbwGeom {
   static_assert(BYTES <= 160 * 1024, "LDS");
 };
 
-// producers store each depthwise unit as soon as it is computed (true) or after all of the step's
-// units (false: more loads in flight, more registers)
-#ifndef EBW_EAGER_STORE
-#define EBW_EAGER_STORE false
-#endif
 // CDW: dw2 units per step that every consumer wave computes too (the consumers idle half of an
 // iteration while the producers' depthwise is the critical path); the producers keep the rest
 // RP: row-pair depthwise (eb_dw_mfma_rowpair). A step's two y1 rows and its two y2 rows are adjacent,
@@ -1093,9 +982,13 @@ struct EbwGeom {
 // share k-step and channel group, so the producers build their weight operands once per kernel: the
 // operand perms were a third of the producers' VALU instructions, and the SIMDs' VALU issue, not the
 // LDS, bounds an iteration (10 VALU per MFMA in config 15; profiles/entry_block_rowpair.txt).
-template <int C0, int C1, int PC, int NWAV, int NCW, int PT, bool RELU1, bool STAMP, int CDW = 0, bool RP = false>
-__global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(EntryBlockArgs a) {
-  using G = EbwGeom<C0, C1, PC, NWAV, NCW>;
+// Block2 (odd maps: the leading pad PT of the TF-'same' 3x3/2 pool is 1, so the residual row 2k is x row R+1 of
+// the step; no ReLU on the block input). STAMP: the diagnostics build
+using Eb2Geom = EbwGeom<64, 128, 13, 16, 8>;
+template <bool STAMP, int CDW, bool RP>
+__global__ __launch_bounds__(64 * Eb2Geom::NWAV, Eb2Geom::NWAV / 4) void entry_block_ws_kernel(EntryBlockArgs a) {
+  using G = Eb2Geom;
+  constexpr int C0 = G::C0, PC = G::PC, NWAV = G::NWAV, PT = 1;
   constexpr int KT0 = G::KT0, KT1 = G::KT1, PLB = G::PLB, XROW = G::XROW, Y1ROW = G::Y1ROW, XDMA = G::XDMA;
   constexpr int Y1C = G::Y1C, Y2C = G::Y2C, XC = G::XC, PLP = G::PLP;
   constexpr int Y1F = G::Y1F, Y2F = G::Y2F, Y2FR = G::Y2FR, PCOLS = G::PCOLS;
@@ -1108,7 +1001,6 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   static_assert(!RP || (2 * Y1FR == Y1F && NP % (2 * KT0) == 0 && NP % (2 * KT1) == 0 && NC % (2 * KT1) == 0 &&
                         CU2 % (2 * KT1) == 0),
                 "row-pair items of a wave share one k-step and one channel group; y1 fragments [row][col / 16]");
-  static_assert(PT == 1, "the residual row 2k is x row R+1 of the step (odd map size: block2)");
   // distinct LDS objects: the compiler may reorder accesses of different regions
   __shared__ __attribute__((aligned(16))) uint8_t s_x[XR * XROW];
   __shared__ __attribute__((aligned(16))) uint8_t s_y1[YR * Y1ROW];
@@ -1243,7 +1135,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
               const int col = min(cf * 16 + p16, Y1C - 1);
               const uint8_t* base = s_x + (4 * t1 + 2 * g1 + (q16 & 1)) * PLB + col * 16;
               auto addr = [&](int ti) { return base + ((xs + ti / 3) & (XR - 1)) * XROW + (ti % 3) * 16; };
-              eb_dw_mfma_rowpair<RELU1>(addr, [&](int j) { return wk1[j]; }, lane, dv1[i]);
+              eb_dw_mfma_rowpair(addr, [&](int j) { return wk1[j]; }, lane, dv1[i]);
               d1[i] = A1 + (t1 * Y1F + cf) * 1024;
             }
           } else
@@ -1259,12 +1151,8 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
             auto ent = [&](int g) {
               return *(const u32x4*)(s_dw + t1 * 1024 + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
             };
-            eb_dw_mfma_vals<RELU1>(tap, ent, lane, sel, dv1[i]);
+            eb_dw_mfma_vals(tap, ent, lane, sel, dv1[i]);
             d1[i] = A1 + (t1 * Y1F + f) * 1024;
-            if constexpr (EBW_EAGER_STORE) {           // store at once (no deferral)
-              eb_dw_store(d1[i], lane, dv1[i]);
-              d1[i] = nullptr;
-            }
           }
         }
         if (mode == 2) {                             // x row 2k = R + 1 (slot xs), 16 strided columns, C0 channels
@@ -1278,7 +1166,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
         int b, s, k, mode, xs;
         decode(it - 2, b, s, k, mode, xs);
         if (mode >= 1) {
-          const int R = 2 * k - PT, t2 = pw % KT1;
+          const int t2 = pw % KT1;
           uint8_t* const A2 = s_a2 + (it & 1) * G::A2B;
 #pragma unroll
           for (int i = 0; i < U2W; ++i) {
@@ -1288,7 +1176,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
                 const int g2 = (pw / KT1) & 1, cf = u / (2 * KT1);
                 const uint8_t* base = s_y1 + (4 * t2 + 2 * g2 + (q16 & 1)) * PLB + (cf * 16 + p16) * 16;
                 auto addr = [&](int ti) { return base + yslot(it - 2, ti / 3) * Y1ROW + (ti % 3) * 16; };
-                eb_dw_mfma_rowpair<false>(addr, [&](int j) { return wk2[j]; }, lane, dv2[i]);
+                eb_dw_mfma_rowpair(addr, [&](int j) { return wk2[j]; }, lane, dv2[i]);
                 d2[i] = A2 + (t2 * Y2F + cf) * 1024;
               }
             } else
@@ -1302,12 +1190,8 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
               auto ent = [&](int g) {
                 return *(const u32x4*)(s_dw + (KT0 + t2) * 1024 + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
               };
-              eb_dw_mfma_vals<false>(tap, ent, lane, sel, dv2[i]);
+              eb_dw_mfma_vals(tap, ent, lane, sel, dv2[i]);
               d2[i] = A2 + (t2 * Y2F + f) * 1024;
-              if constexpr (EBW_EAGER_STORE) {
-                eb_dw_store(d2[i], lane, dv2[i]);
-                d2[i] = nullptr;
-              }
             }
           }
         }
@@ -1361,7 +1245,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
           int b, s, k, mode, xs;
           decode(it - 2, b, s, k, mode, xs);
           if (mode >= 1) {
-            const int R = 2 * k - PT, t2 = w % KT1;
+            const int t2 = w % KT1;
             auto unit = [&](int u) {
               const int f = u / KT1;
               const int rr = f / Y2FR, col = (f % Y2FR) * 16 + p16;
@@ -1373,7 +1257,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
                 return *(const u32x4*)(s_dw + (KT0 + t2) * 1024 + (((g * 16 + p16) * 2) + (q16 >> 1)) * 16);
               };
               u32x2 dv[2];
-              eb_dw_mfma_vals<false>(tap, ent, lane, sel, dv);
+              eb_dw_mfma_vals(tap, ent, lane, sel, dv);
               eb_dw_store(s_a2 + (it & 1) * G::A2B + (t2 * Y2F + f) * 1024, lane, dv);
             };
             auto item = [&](int u) {                 // RP: item (cf, g2, t2), both rows
@@ -1382,7 +1266,7 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
               auto addr = [&](int ti) { return base + yslot(it - 2, ti / 3) * Y1ROW + (ti % 3) * 16; };
               const u32x4 e = rp_ent(KT0 + t2, g2);
               u32x2 dv[2];
-              eb_dw_mfma_rowpair<false>(addr, [&](int j) { return eb_dw_wop(e, j, sel); }, lane, dv);
+              eb_dw_mfma_rowpair(addr, [&](int j) { return eb_dw_wop(e, j, sel); }, lane, dv);
               uint8_t* const dst = s_a2 + (it & 1) * G::A2B + (t2 * Y2F + cf) * 1024;
               eb_dw_store_g(dst, lane, g2, dv[0]);
               eb_dw_store_g(dst + Y2FR * 1024, lane, g2, dv[1]);
@@ -1517,26 +1401,25 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
   }
 }
 
-// (C0, C1, PC, NFW, PT, RELU1, DWM, OCC = workgroups per CU) per id: 0 = block2 (147x147x64 -> 74x74x128), 1 = block3
-// (74x74x128 -> 37x37x256, the asymmetric 74 -> 37 pool: leading pad 0); 100 + id: the same
-// with per-phase s_memtime stamps (EntryBlockArgs.stamps; diagnostics only); 2, 3: 0, 1 with the
-// depthwise convs on the matrix cores (block-diagonal operand) instead of the VALU (block2 only:
-// block3's four-phase LDS map has no room for the larger entries; the two-phase map has: config 23); 4, 5: block2
-// with 13-column strips, small enough (LDS, <= 128 VGPRs) for two workgroups per CU. Measured and removed (round 5,
+// Kernel configurations (the ids of EntryBlock(cfg=...) and KDL_ENTRY_BLOCK=block:id); 100 + id: the same
+// build with s_memtime stamps (EntryBlockArgs.stamps; diagnostics only, tools/ebbench.py --stamps). Block2
+// (147x147x64 -> 74x74x128, leading pool pad 1) runs on entry_block_ws_kernel: 15, 17, 19; block3
+// (74x74x128 -> 37x37x256, the asymmetric 74 -> 37 pool: leading pad 0) on entry_block_kernel: 1, 21, 23.
+// The engine launches 17 and 23; 15, 19, 1 and 21 are the predecessors their bit-equality tests compare
+// against (tests/test_entry_block_rowpair_gpu.py, tests/test_entry_block3_twophase_gpu.py,
+// tests/test_entry_block3_dwm_gpu.py). Any other id is refused.
+// 1 / 101: block3 on the four-phase loop, two slices per wave, VALU depthwise (the four-phase LDS map has no
+// room for the MFMA entries; the two-phase map has: config 23). Measured and removed (round 5,
 // profiles/entry_block3_r5.txt): block3 as 16 waves of one slice (VALU / MFMA depthwise: 328 / 246 us)
 // and block3 with the MFMA depthwise (378 us) against config 1's 188 us -- all spill (78 / 56 / 91 VGPRs)
-// 13 / 113: block2 warp-specialized (entry_block_ws_kernel, 16 waves: 8 producers run the depthwise of
-// later steps while 8 consumers run the GEMMs of earlier ones; 13-column strips), plain / stamped.
-// 210.5 us against config 2's 216.2 / config 5's 208.4 (profiles/entry_block_ab_r4.txt, round 5): the
-// producers' LDS-latency-bound depthwise (6,336 cycles per step) stays the critical path, consumers idle
-// 37 %. The 8-wave build (4 + 4) ran 280.4 us (producers 10,252 cycles per step) and was removed.
-// 15 / 115 (block2's default): config 13 with every consumer wave also computing one of the step's 16
-// dw2 units (CDW = 1): 191.8 vs 199.2 us, iteration 7,212 -> 6,636 cycles (consumers busy 4,700,
+// 15 / 115: the warp-specialized kernel with single-row depthwise units, every consumer wave also
+// computing one of the step's 16 dw2 units (CDW = 1; against the retired 13 without them): 191.8 vs
+// 199.2 us, iteration 7,212 -> 6,636 cycles (consumers busy 4,700,
 // producers 5,572), bench +1.0 % in 3 of 3 pairs. Measured and removed (profiles/entry_block_ab_r4.txt):
 // 4 consumer + 12 producer waves (227.0 us: the 32-channel consumers spill 32 VGPRs), two dw2 units per
 // consumer (215.8 us: consumers 6,168 busy with 14 VGPRs spilled), and the residual-row copy moved to the
 // consumers as well (iteration 6,732 vs 6,676, bench -0.2 %).
-// 17 / 117 (block2's default), 19 / 119: configs 13 / 15 with the row-pair depthwise (RP): a step's two
+// 17 / 117 (block2's default), 19 / 119: CDW 0 / 1 with the row-pair depthwise (RP): a step's two
 // rows per item, the producers' weight operands built once per kernel. Bit-identical to config 15
 // (tests/test_entry_block_rowpair_gpu.py; the bench logits equal the parent build's). One lease
 // (profiles/entry_block_rowpair.txt): config 15 iteration 6,440 cycles (producers 5,364, consumers 4,522),
@@ -1567,78 +1450,70 @@ __global__ __launch_bounds__(64 * NWAV, NWAV / 4) void entry_block_ws_kernel(Ent
 // MFMA one by one, 137 us), the reads fenced off but every address rebuilt per item (384 VALU, 133 us),
 // the residual weights fetched ahead of dw1 (12 VGPRs spilled, 140 us) or half of them (254 VGPRs, 126 us:
 // inside the noise of the simpler form).
-#define KDL_EBW_CONFIGS(X) \
-  X(13, 64, 128, 13, 16, 8, 1, false, 0, false) \
-  X(15, 64, 128, 13, 16, 8, 1, false, 1, false) \
-  X(17, 64, 128, 13, 16, 8, 1, false, 0, true) \
-  X(19, 64, 128, 13, 16, 8, 1, false, 1, true) \
-  X(113, 64, 128, 13, 16, 8, 1, false, 0, false) \
-  X(115, 64, 128, 13, 16, 8, 1, false, 1, false) \
-  X(117, 64, 128, 13, 16, 8, 1, false, 0, true) \
-  X(119, 64, 128, 13, 16, 8, 1, false, 1, true)
+//
+// Retired configurations (their ids are refused). Each lost a measured comparison to a build above:
+// 0, 2, 4, 5: block2 on the four-phase loop of entry_block_kernel; every wave ran dw1 ->
+// GEMM1 (+ residual) -> dw2 -> GEMM2 + pool one after another, one slice per wave; VALU / MFMA depthwise
+// (0 / 2, 15-column strips) and 13-column strips, small enough (LDS, <= 128 VGPRs) for two workgroups per CU
+// (4 / 5). ~2k cycles per phase, all of them LDS-throughput bound: 216.2 us (config 2) and 208.4 us
+// (config 5) against the warp-specialized kernel's 210.5 -> 191.8 -> 163.4 us (profiles/entry_block_ab_r4.txt,
+// profiles/entry_block_rowpair.txt). With them went the forms only one-slice waves had registers for: the
+// biases and step words in registers, the A fragments hoisted above a phase's stores, the deferred depthwise
+// stores.
+// 13 / 113: block2 warp-specialized (16 waves: 8 producers run the depthwise of later steps while 8
+// consumers run the GEMMs of earlier ones; 13-column strips) with no consumer dw2 unit. 210.5 us against
+// config 2's 216.2 / config 5's 208.4 (profiles/entry_block_ab_r4.txt, round 5): the producers'
+// LDS-latency-bound depthwise (6,336 cycles per step) stays the critical path, consumers idle 37 %; lost to
+// 15 above. The 8-wave build (4 + 4) ran 280.4 us (producers 10,252 cycles per step) and was removed.
+#define KDL_EB_CONFIGS(X) /* (id, DWM, TWOPH) */ \
+  X(1, false, false)      \
+  X(21, false, true)      \
+  X(23, true, true)       \
+  X(101, false, false)    \
+  X(121, false, true)     \
+  X(123, true, true)
 
-#define KDL_EB_CONFIGS(X)                          \
-  X(0, 64, 128, 15, 1, 1, false, false, 1, false)  \
-  X(1, 128, 256, 13, 2, 0, true, false, 1, false)  \
-  X(2, 64, 128, 15, 1, 1, false, true, 1, false)   \
-  X(4, 64, 128, 13, 1, 1, false, false, 2, false)  \
-  X(5, 64, 128, 13, 1, 1, false, true, 2, false)   \
-  X(21, 128, 256, 13, 2, 0, true, false, 1, true)  \
-  X(23, 128, 256, 13, 2, 0, true, true, 1, true)   \
-  X(100, 64, 128, 15, 1, 1, false, false, 1, false) \
-  X(101, 128, 256, 13, 2, 0, true, false, 1, false) \
-  X(102, 64, 128, 15, 1, 1, false, true, 1, false) \
-  X(104, 64, 128, 13, 1, 1, false, false, 2, false) \
-  X(105, 64, 128, 13, 1, 1, false, true, 2, false) \
-  X(121, 128, 256, 13, 2, 0, true, false, 1, true) \
-  X(123, 128, 256, 13, 2, 0, true, true, 1, true)
+#define KDL_EBW_CONFIGS(X) /* (id, CDW, RP) */ \
+  X(15, 1, false)          \
+  X(17, 0, true)           \
+  X(19, 1, true)           \
+  X(115, 1, false)         \
+  X(117, 0, true)          \
+  X(119, 1, true)
 
-int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds, int* occ) {
+int entry_block_config(int cfg, int* c0, int* c1, int* pc, int* lds) {
   switch (cfg) {
-#define KDL_EBINFO(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp) \
-  case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbGeom<c0_, c1_, pc_, nfw, dwm, tp>::BYTES; *occ = occ_; return 0;
+#define KDL_EBINFO(id, dwm, tp) \
+  case id: { using G = Eb3Geom<dwm, tp>; *c0 = G::C0; *c1 = G::C1; *pc = G::PC; *lds = G::BYTES; return 0; }
     KDL_EB_CONFIGS(KDL_EBINFO)
 #undef KDL_EBINFO
-#define KDL_EBWINFO(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) \
-  case id: *c0 = c0_; *c1 = c1_; *pc = pc_; *lds = EbwGeom<c0_, c1_, pc_, nw, nc>::BYTES; *occ = 1; return 0;
+#define KDL_EBWINFO(id, cdw, rp) \
+  case id: *c0 = Eb2Geom::C0; *c1 = Eb2Geom::C1; *pc = Eb2Geom::PC; *lds = Eb2Geom::BYTES; return 0;
     KDL_EBW_CONFIGS(KDL_EBWINFO)
 #undef KDL_EBWINFO
     default: return -1;
   }
 }
 
-static int eb_pad(int cfg) {
-  switch (cfg) {
-#define KDL_EBPAD(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp) case id: return pt;
-    KDL_EB_CONFIGS(KDL_EBPAD)
-#undef KDL_EBPAD
-#define KDL_EBWPAD(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp) case id: return pt;
-    KDL_EBW_CONFIGS(KDL_EBWPAD)
-#undef KDL_EBWPAD
-    default: return -1;
-  }
-}
-
 hipError_t entry_block(int cfg, const EntryBlockArgs& a, hipStream_t s) {
-  int c0, c1, pc, lds, occ;
-  if (entry_block_config(cfg, &c0, &c1, &pc, &lds, &occ) != 0 || a.ldx != c0 || a.ldy != c1 || a.grid < 1 ||
+  int c0, c1, pc, lds;
+  if (entry_block_config(cfg, &c0, &c1, &pc, &lds) != 0 || a.ldx != c0 || a.ldy != c1 || a.grid < 1 ||
       a.OH != (a.H - 1) / 2 + 1 || a.OW != (a.W - 1) / 2 + 1 || a.H % 2 != a.W % 2 || !a.steps || !a.step_off ||
       a.B > 256)                                     // the packed LDS step word holds an 8-bit image index
     return hipErrorInvalidValue;
-  if (eb_pad(cfg) != (a.H % 2)) return hipErrorInvalidValue;   // TF 'same': leading pad 1 iff odd size
+  // TF 'same': leading pool pad 1 iff the size is odd; block2's kernel is built for odd maps, block3's for even ones
+  if ((c0 == Eb2Geom::C0) != (a.H % 2 == 1)) return hipErrorInvalidValue;
   switch (cfg) {
-#define KDL_EBCASE(id, c0_, c1_, pc_, nfw, pt, r_, dwm, occ_, tp)                                                \
-  case id:                                                                                                      \
-    hipLaunchKernelGGL((entry_block_kernel<c0_, c1_, pc_, nfw, pt, r_, (id >= 100), dwm, occ_, tp>), dim3(a.grid), \
-                       dim3(64 * EbGeom<c0_, c1_, pc_, nfw, dwm, tp>::NW), lds, s, a);                             \
+#define KDL_EBCASE(id, dwm, tp)                                                                       \
+  case id:                                                                                            \
+    hipLaunchKernelGGL((entry_block_kernel<(id >= 100), dwm, tp>), dim3(a.grid), dim3(64 * Eb3Geom<dwm, tp>::NW), lds, s, a); \
     break;
     KDL_EB_CONFIGS(KDL_EBCASE)
 #undef KDL_EBCASE
-#define KDL_EBWCASE(id, c0_, c1_, pc_, nw, nc, pt, r_, cdw, rp)                                                  \
+#define KDL_EBWCASE(id, cdw, rp)                                                                      \
   case id:                                                                                            \
-    hipLaunchKernelGGL((entry_block_ws_kernel<c0_, c1_, pc_, nw, nc, pt, r_, (id >= 100), cdw, rp>), dim3(a.grid), \
-                       dim3(64 * nw), 0, s, a);   /* static LDS */                                   \
-    break;
+    hipLaunchKernelGGL((entry_block_ws_kernel<(id >= 100), cdw, rp>), dim3(a.grid), dim3(64 * Eb2Geom::NWAV), 0, s, a); \
+    break;   /* static LDS */
     KDL_EBW_CONFIGS(KDL_EBWCASE)
 #undef KDL_EBWCASE
   }

@@ -51,17 +51,20 @@ class XceptionEngine(EngineBase):
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.
-        # KDL_ENTRY_BLOCK: a list "2,3" / "2:4,3" (block[:kernel config]), "1" = blocks 2 and 3,
-        # "0" = none. Default "2:17,3:23": block2 on the warp-specialized kernel (producer waves run the
+        # KDL_ENTRY_BLOCK: a list "2,3" / "2:15,3" (block[:kernel config]), "1" = blocks 2 and 3,
+        # "0" = none; a block without a config takes the served one (kdl/ops/entry_block.py CONFIGS:
+        # 17, 23). The configs that exist: 15, 17, 19 (block2) and 1, 21, 23 (block3).
+        # Default "2:17,3:23": block2 on the warp-specialized kernel (producer waves run the
         # depthwise of later rows while consumer waves run the GEMMs of earlier ones; config 13 +0.8 %
-        # over the round-4 default 2:2 in 4 of 4 interleaved pairs, config 15 +1.0 % over 13 in 3 of 3,
-        # profiles/entry_block_ab_r4.txt; config 17, the row-pair depthwise with register-resident
-        # weight operands: profiles/entry_block_rowpair.txt) and block3, whose lighter stage 1 moves
-        # the stage cut to block8_sepconv3; block3 on config 23: the two-phase schedule (two barriers
-        # per step, no spilled registers: config 21, profiles/entry_block3_twophase.txt) with both
-        # depthwise convs on the matrix cores (148 -> 128 us per launch, bench +1.25 % over 3:21 in 8 of 8
-        # interleaved pairs; not bit-identical to 21, bench logits within 7.7e-3;
-        # profiles/entry_block3_dwm.txt, which also lists the forms measured and dropped)
+        # over the round-4 default 2:2 in 4 of 4 interleaved pairs, both since retired, config 15
+        # +1.0 % over 13 in 3 of 3, profiles/entry_block_ab_r4.txt; config 17, the row-pair depthwise
+        # with register-resident weight operands: profiles/entry_block_rowpair.txt) and block3, whose
+        # lighter stage 1 moves the stage cut to block8_sepconv3; block3 on config 23: the two-phase
+        # schedule (two barriers per step, no spilled registers: config 21,
+        # profiles/entry_block3_twophase.txt) with both depthwise convs on the matrix cores (148 ->
+        # 128 us per launch, bench +1.25 % over 3:21 in 8 of 8 interleaved pairs; not bit-identical to
+        # 21, bench logits within 7.7e-3; profiles/entry_block3_dwm.txt, which also lists the forms
+        # measured and dropped)
         eb = os.environ.get("KDL_ENTRY_BLOCK", "2:17,3:23")
         spec = "2,3" if eb == "1" else ("" if eb == "0" else eb)
         self.fused_blocks = {}

@@ -24,16 +24,17 @@ WARM_Y1, WARM_Y2, OUT = 0, 1, 2
 MAX_STEPS = 128          # entry_block.hip EB_MAX_STEPS: a workgroup's step table lives in LDS
 
 
-def entry_block_config(cfg: int) -> tuple[int, int, int, int, int]:
-    """(C0, C1, PC, LDS bytes, workgroups per CU) of a kernel config (mirror of KDL_EB_CONFIGS)."""
+def entry_block_config(cfg: int) -> tuple[int, int, int, int]:
+    """(C0, C1, PC, LDS bytes) of a kernel config (entry_block.hip's table comment); IndexError for an id
+    that does not exist."""
     return tuple(_lib.lib().entry_block_config(cfg))
 
 
-# kernel config per (block input channels, block output channels): entry_block.hip KDL_EB_CONFIGS
-# (the four-phase builds, any map parity they were built for; the engine's default for block3 is config 23,
-# the two-phase schedule of config 1 (config 21) with the depthwise on the matrix cores:
-# kdl/engine/xception.py KDL_ENTRY_BLOCK)
-CONFIGS = {(64, 128): 0, (128, 256): 1}
+# served kernel config per (block input channels, block output channels), the ones the engine launches by
+# default (kdl/engine/xception.py KDL_ENTRY_BLOCK): 17 = block2, warp-specialized with the row-pair
+# depthwise (odd maps); 23 = block3, two-phase schedule with the depthwise on the matrix cores (even
+# maps). Their predecessors that are still built (15, 19; 1, 21) are selected by id only
+CONFIGS = {(64, 128): 17, (128, 256): 23}
 
 
 def supported(cin: int, cout: int) -> bool:
@@ -84,11 +85,11 @@ class EntryBlock:
                  device="cuda", grid: int | None = None):
         """``grid``: workgroups (default: one per CU); ``cfg``: kernel config (default: by channels)."""
         cfg = CONFIGS[(sep1.cin_pad, sep1.n)] if cfg is None else cfg
-        c0, c1, pc, lds, occ = entry_block_config(cfg)
+        c0, c1, pc, lds = entry_block_config(cfg)
         assert sep1.mode == MODE_DW and sep2.mode == MODE_DW and res.mode == MODE_PW and res.stride == 2, name
         assert sep1.cin_pad == c0 and sep1.n == c1 and sep2.cin_pad == c1 and sep2.n == c1, (name, c0, c1)
         assert res.cin_pad == c0 and res.n == c1 and not sep2.relu_in and sep1.relu_out == 1 and sep2.relu_out == 0
-        self.name, self.cfg, self.c0, self.c1, self.pc, self.lds, self.occ = name, cfg, c0, c1, pc, lds, occ
+        self.name, self.cfg, self.c0, self.c1, self.pc, self.lds = name, cfg, c0, c1, pc, lds
         self.relu_in = bool(sep1.relu_in)
         assert self.relu_in == (c0 == 128), "block2 (64 -> 128): no pre-activation; block3 (128 -> 256): ReLU first"
         self.sep1, self.sep2, self.res = sep1, sep2, res
@@ -102,7 +103,7 @@ class EntryBlock:
             if self.grid:                    # an explicit grid must fit as given
                 steps, off = plan_steps(B, OH, OW, self.pc, self.grid)
             else:                            # default: resident waves of workgroups, as many as fit
-                steps, off = fit_plan(B, OH, OW, self.pc, self.occ * _lib.num_cus(self.device))
+                steps, off = fit_plan(B, OH, OW, self.pc, _lib.num_cus(self.device))
             assert max(b - a for a, b in zip(off, off[1:])) <= MAX_STEPS, "workgroup step table > EB_MAX_STEPS"
             st = torch.tensor(steps, dtype=torch.int32).reshape(-1, 4).to(self.device)
             of = torch.tensor(off, dtype=torch.int32).to(self.device)

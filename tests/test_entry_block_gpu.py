@@ -40,9 +40,15 @@ GEOM = {2: (147, 64, 74, 128), 3: (74, 128, 37, 256)}
 # (block, batch, grid): grids small enough that workgroups run many pooled rows, but whose step
 # lists still fit the kernel's LDS step table (EB_MAX_STEPS)
 CASES = [(2, 2, None), (2, 2, 9), (2, 3, 97), (2, 1, 8), (3, 2, None), (3, 3, 7), (3, 1, 1)]
-# kernel configs per block (entry_block.hip KDL_EB_CONFIGS): VALU / MFMA depthwise, 1 or 2 WGs per CU
-# 13 / 15: block2 warp-specialized, 16 waves (8 consumers + 8 producers; 15: the consumers also run one dw2 unit each)
-BLOCK_CFGS = {2: [0, 2, 4, 5, 13, 15], 3: [1]}
+# kernel configs per block (entry_block.hip's table comment): the served geometry on the served kernels (17,
+# 23) and on the predecessors that are still built.
+# 15 / 17: block2 warp-specialized, 16 waves (8 consumers + 8 producers; 15: single-row depthwise, the consumers
+# also run one dw2 unit each; 17: row-pair depthwise); 1: block3 four-phase; 21 / 23: block3 two-phase, depthwise
+# on the VALU / on the matrix cores
+BLOCK_CFGS = {2: [15, 17], 3: [1, 21, 23]}
+KEPT_CFGS = {15: (64, 128, 13), 17: (64, 128, 13), 19: (64, 128, 13), 1: (128, 256, 13), 21: (128, 256, 13),
+             23: (128, 256, 13)}
+RETIRED_CFGS = [0, 2, 4, 5, 13]
 
 
 @pytest.mark.parametrize("blk,B,grid,cfg", [c + (g,) for c in CASES for g in BLOCK_CFGS[c[0]]])
@@ -68,7 +74,7 @@ def test_entry_block_matches_oracle(xparams, blk, B, grid, cfg):
     assert err < 2e-2, err
 
 
-@pytest.mark.parametrize("B,cfg", [(96, 2), (128, 2), (128, 0), (128, 13), (128, 15)])
+@pytest.mark.parametrize("B,cfg", [(96, 17), (128, 17), (128, 15)])
 def test_entry_block2_large_bucket_runs_in_two_waves(xparams, B, cfg):
     """batch >= ~85 overflowed a one-wave plan's step table (EB_MAX_STEPS); the default
     plan now adds whole waves of workgroups. The fp32 oracle runs on the GPU at this size."""
@@ -100,10 +106,10 @@ def test_entry_block_refuses_a_step_table_over_the_lds_limit(xparams):
         eb.plan(2, 74, 74)
 
 
-@pytest.mark.parametrize("cfg", [0, 2, 13, 15])
+@pytest.mark.parametrize("cfg", [15, 17])
 def test_entry_block2_replays_bit_identical(xparams, cfg):
     """Persistent kernel, host step table: two launches give identical bytes (an LDS / DMA ordering
-    bug would show as run-to-run noise; VALU and MFMA depthwise configs)."""
+    bug would show as run-to-run noise)."""
     from kdl.ops.entry_block import EntryBlock
     s1, s2, r = _layers(xparams, 2)
     eb = EntryBlock("block2", s1, s2, r, device=DEV, cfg=cfg)
@@ -115,6 +121,38 @@ def test_entry_block2_replays_bit_identical(xparams, cfg):
     eb.emit(None, x.data_ptr(), y2.data_ptr(), 4, 147, 147)
     torch.cuda.synchronize()
     assert torch.equal(y1, y2)
+
+
+def test_entry_block3_replays_bit_identical(xparams):
+    """The same for block3's served kernel (config 23) on a (74, 74, 4) input."""
+    from kdl.ops.entry_block import EntryBlock
+    s1, s2, r = _layers(xparams, 3)
+    eb = EntryBlock("block3", s1, s2, r, device=DEV, cfg=23)
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(4, 74, 74, 128, generator=gen).to(torch.bfloat16).to(DEV)
+    y1 = torch.empty((4, 37, 37, 256), dtype=torch.bfloat16, device=DEV)
+    y2 = torch.empty_like(y1)
+    eb.emit(None, x.data_ptr(), y1.data_ptr(), 4, 74, 74)
+    eb.emit(None, x.data_ptr(), y2.data_ptr(), 4, 74, 74)
+    torch.cuda.synchronize()
+    assert torch.equal(y1, y2)
+
+
+def test_entry_block_config_lists_the_kept_ids_and_refuses_the_retired(xparams):
+    """entry_block_config(id) -> (c0, c1, pc, lds) for the builds that exist (the plain ones and their stamped
+    100 + id twins); a retired id raises, as does its stamped twin, and so does a launch with one."""
+    from kdl.ops.entry_block import CONFIGS, EntryBlock, entry_block_config
+    for cfg, (c0, c1, pc) in KEPT_CFGS.items():
+        got = entry_block_config(cfg)
+        assert len(got) == 4 and got[:3] == (c0, c1, pc) and 0 < got[3] <= 160 * 1024, (cfg, got)
+        assert entry_block_config(100 + cfg) == got                 # stamped twin: same geometry, same LDS
+    assert sorted(CONFIGS.values()) == [17, 23]
+    for cfg in RETIRED_CFGS + [100 + c for c in RETIRED_CFGS]:
+        with pytest.raises(IndexError):
+            entry_block_config(cfg)
+    s1, s2, r = _layers(xparams, 2)
+    with pytest.raises(IndexError):
+        EntryBlock("block2", s1, s2, r, device=DEV, cfg=13)
 
 
 def test_engine_with_fused_block2_matches_oracle(xparams):

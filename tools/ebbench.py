@@ -24,7 +24,7 @@ def stamps(p, blocks, B, only=None):
         s1, s2, r = XE._sep(p, b.main[0], "cuda"), XE._sep(p, b.main[1], "cuda"), XE._pw(p, b.res_conv, "cuda")
         H, C0 = geom[blk]
         # 17 / 19: 13 / 15 with the row-pair depthwise; 21: two-phase; 23: 21 with the depthwise on the matrix cores
-        cfgs = [2, 13, 15, 17, 19] if blk == 2 else [1, 21, 23]
+        cfgs = [15, 17, 19] if blk == 2 else [1, 21, 23]
         cfgs = [c for c in cfgs if only is None or c in only]
         for cfg in [c for b in cfgs for c in (b, 100 + b)]:
             eb = EntryBlock(f"block{blk}", s1, s2, r, cfg=cfg)
@@ -47,7 +47,7 @@ def stamps(p, blocks, B, only=None):
             if cfg < 100:
                 continue
             v = st.view(8, 64, 5).cpu().tolist()
-            if cfg in (113, 115, 117, 119):      # warp-specialized: [consumer start, consumer end, producer start, producer end]
+            if cfg in (115, 117, 119):      # warp-specialized: [consumer start, consumer end, producer start, producer end]
                 ph = {n: [] for n in ("iteration", "consumers busy", "producers busy")}
                 for wg in range(8):
                     for k in range(3, 62):
@@ -78,6 +78,7 @@ def stamps(p, blocks, B, only=None):
                     if xs:
                         print(f"    {n:20s} {statistics.median(xs):8.0f}", flush=True)
                 continue
+            # four-phase (101): [B0, B1, B2, B3, end]
             ph = {n: [] for n in ("P1 dw1", "P2 gemm1", "P3 dw2", "P4 gemm2+pool", "out+B0")}
             steps_ = 0
             for wg in range(8):
