@@ -529,6 +529,48 @@ struct HeatOverlayArgs {
 };
 hipError_t heat_overlay(const HeatOverlayArgs& a, hipStream_t s);
 
+// Dominant colours (kernels/palette.hip): behind class_map / rollout_map, two launches answer each
+// image's K dominant colours, the picture's histogram weighted by its own heatmap and clustered, in
+// integers throughout (kdl/serving/palette.py palette_rule is the definition):
+//   w     = u >> 4 with u the map upsampled as heat_overlay does (weight 1), or 15 (weight 0, uniform)
+//   bin   = (r >> 4) << 8 | (g >> 4) << 4 | (b >> 4); per bin n = sum w, sr / sg / sb = sum w * channel
+//   W     = sum n; m = (s + n / 2) / n per live bin; K start centres by largest n, then largest
+//           n * (squared distance to the nearest centre chosen), ties to the lowest bin; T rounds of
+//           assign (ties to the lowest centre) and c = (S + N / 2) / N from the clusters' true sums;
+//           sorted by N descending, ties to the lower centre
+// heat is read from the image's own output row, out[b][2 .. 2 + h*w), and 1 + 2K words are written
+// behind it: W, then K x (r | g << 8 | b << 16, N); centres that do not exist are 0, 0. Nothing else
+// is written: the words before and after them up to ldo and rows >= B stay as they were. `work` is
+// palette_workspace(B) bytes, all zero before the first launch; the second launch leaves it zero
+// again. Every sum is an integer, so launches are bit-identical whatever the order of the atomics.
+// inp / out / work / xb / xk / yb / yk / h_xb / h_yb null, out, work or a device table not 16-byte
+// aligned, B outside 1..65535, h < 1, w < 1, h*w > kClassMapMaxHW, S < max(h, w), S > kOverlayMaxS
+// (the uint32 bound: 15 * 255 * S*S + 15 * S*S / 2 < 2^32), ldo < 2 + h*w + 1 + 2K, K outside
+// 1..kPaletteMaxK, T outside 1..kPaletteMaxT, weight not 0 or 1, xks / yks outside
+// 1..kOverlayMaxTaps, and bounds tables (checked from the host copies) whose taps leave the map, step
+// back, or need more than kOverlayMaxRows map rows for kOverlayBand output rows are
+// hipErrorInvalidValue, and nothing is launched.
+constexpr int kPaletteBins = 4096;
+constexpr int kPaletteMaxK = 8;
+constexpr int kPaletteMaxT = 16;
+struct PaletteArgs {
+  const uint8_t* inp;     // [B][S][S][3] uint8, packed
+  float* out;             // [B][ldo] words: class, score, h*w heat values (read), W and K x (colour, N) (written)
+  uint32_t* work;         // [B][kPaletteBins][4] sums, zero on entry and on exit
+  const int32_t* xb;      // device: bounds [S][2] of the columns, {first map column, taps}
+  const int32_t* xk;      // device: coefficients [S][xks]
+  const int32_t* yb;      // device: the same of the rows
+  const int32_t* yk;      // device: [S][yks]
+  const int32_t* h_xb;    // HOST copies of the bounds (checked here, never followed on the device)
+  const int32_t* h_yb;
+  int B, S, h, w, ldo;
+  int xks, yks;           // taps per column / row of the tables
+  int K, T;               // colours, rounds
+  int weight;             // 0 uniform (15), 1 the map (u >> 4)
+};
+size_t palette_workspace(int B);
+hipError_t palette(const PaletteArgs& a, hipStream_t s);
+
 // Baseline JPEG encode (kernels/jpeg_encode.hip): B pictures uint8 [H][W][3], picture b at inp + b * ldi
 // bytes (any alignment), each into the file Pillow's Image.save(.., "JPEG", quality, subsampling,
 // optimize=False) writes, byte for byte (kdl/serving/jpeg_encode.py encode_rule is the definition:

@@ -23,10 +23,11 @@
 // v_alignbyte again. Only the first and last chunk of an image can be partial: those go byte by
 // byte, so the pad bytes of the last word and everything past them stay untouched. A dword of the
 // photograph that is not wholly inside [inp, inp + B*S*S*3) is read by bytes.
+// Steps 1 and 2 are the device code of heat_upsample.h, which kernels/palette.hip runs as well.
 // Accumulators: uint32 from 1 << 21, += k * value, (int32) >> 22 clamped to 0..255 (Pillow's clip8).
 #include "common.h"
+#include "heat_upsample.h"
 #include "launch.h"
-#include "runtime/resample.h"
 
 namespace kdl {
 
@@ -35,13 +36,6 @@ namespace {
 constexpr int kYRows = kOverlayBand + 6;          // rows whose tables a band stages: a chunk reaches 15 bytes
                                                   // = at most 5 rows + 1 (S = 1) past the band's last row
 constexpr int kTmpRows = kOverlayMaxRows + kOverlayMaxTaps;   // the taps behind a row's own (weight 0) stay in LDS
-
-__device__ __forceinline__ uint32_t clip8(uint32_t acc) {
-  const int32_t v = (int32_t)acc >> kResampleBits;
-  return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // one aligned dword at address q of an input whose bytes are [beg, end): whole where it lies
 // inside, by bytes (the rest 0) at the two ends
@@ -103,59 +97,18 @@ __global__ __launch_bounds__(256) void heat_overlay_kernel(HeatOverlayArgs a) {
     load_stream(img + (size_t)(i0 - ch0), in_beg, in_end, v);
   }
 
-  // the tables live in device memory: the host checked its copies, every value read here is
-  // clamped to what is staged all the same
-  const int row0 = clampi(a.yb[2 * r0], 0, a.h);
-  int nrow = clampi(a.yb[2 * (r1e - 1)] + a.yb[2 * (r1e - 1) + 1], row0, a.h) - row0;
-  nrow = nrow < kOverlayMaxRows ? nrow : kOverlayMaxRows;
-  const float* heat = orow + 2;
-  for (int p = row0 * w + tid; p < (row0 + nrow) * w; p += 256) {
-    float f = heat[p];
-    f = f > 0.f ? f : 0.f;                                       // NaN -> 0
-    f = f < 1.f ? f : 1.f;
-    q[p] = (uint8_t)__builtin_rintf(f * 255.0f);
-  }
+  // steps 1 and 2 of the rule for the band's rows: heat_upsample.h
+  int row0, nrow;
+  upsample_stage(orow + 2, a.yb, a.yk, yks, a.h, w, r0, r1e, tid, q, ykk, ymn, row0, nrow);
   tab[tid] = (uint32_t)a.tab[3 * tid] | ((uint32_t)a.tab[3 * tid + 1] << 8) | ((uint32_t)a.tab[3 * tid + 2] << 16);
-  if (tid < (r1e - r0) * kOverlayMaxTaps) {
-    const int i = tid / kOverlayMaxTaps, t = tid - i * kOverlayMaxTaps, yy = r0 + i;
-    const int mn = clampi(a.yb[2 * yy], row0, row0 + nrow) - row0;
-    int n = clampi(a.yb[2 * yy + 1], 0, yks);
-    n = n < nrow - mn ? n : nrow - mn;
-    ykk[tid] = t < n ? a.yk[(size_t)yy * yks + t] : 0;
-    if (t == 0) ymn[i] = mn;
-  }
   __syncthreads();
-
-  for (int xx = tid; xx < S; xx += 256) {
-    const int mn = clampi(a.xb[2 * xx], 0, w);
-    int n = clampi(a.xb[2 * xx + 1], 0, a.xks);
-    n = n < w - mn ? n : w - mn;
-    uint32_t k[kOverlayMaxTaps];
-#pragma unroll
-    for (int t = 0; t < kOverlayMaxTaps; ++t) k[t] = t < n ? (uint32_t)a.xk[(size_t)xx * a.xks + t] : 0u;
-    for (int r = 0; r < nrow; ++r) {
-      const uint8_t* qr = q + (row0 + r) * w + mn;
-      uint32_t acc = 1u << (kResampleBits - 1);
-#pragma unroll
-      for (int t = 0; t < kOverlayMaxTaps; ++t)
-        if (t < n) acc += k[t] * qr[t];
-      tmp[r * S + xx] = (uint8_t)clip8(acc);
-    }
-  }
+  upsample_hpass(a.xb, a.xk, a.xks, S, w, row0, nrow, tid, q, tmp);
   __syncthreads();
 
   const uint32_t A = (uint32_t)a.a;
-  // the vertical pass of pixel (yy, xx) of the band: mn + t < kOverlayMaxRows + kOverlayMaxTaps, and
-  // a tap behind the row's own has weight 0
+  // the vertical pass of pixel (yy, xx) of the band
   auto pixel = [&](int yy, int xx, uint32_t& col, uint32_t& ap) {
-    const int yi = yy - r0;                                      // < r1e - r0: see `reach`
-    const uint8_t* t0 = tmp + ymn[yi] * S + xx;
-    const int32_t* kk = ykk + yi * kOverlayMaxTaps;
-    uint32_t acc = 1u << (kResampleBits - 1);
-#pragma unroll
-    for (int t = 0; t < kOverlayMaxTaps; ++t)
-      if (t < yks) acc += (uint32_t)kk[t] * t0[t * S];           // yks is uniform: no divergence
-    const uint32_t u = clip8(acc);
+    const uint32_t u = upsample_pixel(tmp, ykk, ymn, yy - r0, xx, S, yks);   // yy - r0 < r1e - r0: see `reach`
     col = tab[u];
     ap = a.blend ? (A * u + 127u) / 255u : A;
   };
@@ -222,23 +175,6 @@ __global__ __launch_bounds__(256) void heat_overlay_kernel(HeatOverlayArgs a) {
   }
 }
 
-// bounds [S][2] of one axis against a map of `in` samples: every tap inside the map, at most
-// `ks` of them, and neither end stepping back (Pillow's rule: a run of outputs then needs the
-// samples [bounds[first].min, bounds[last].min + n))
-bool valid_bounds(const int32_t* bd, int S, int in, int ks) {
-  int32_t pmn = 0, pend = 0;
-  for (int i = 0; i < S; ++i) {
-    const int32_t mn = bd[2 * i], n = bd[2 * i + 1];
-    if (mn < 0 || n < 0 || n > ks || mn > in || n > in - mn) return false;
-    if (mn < pmn || mn + n < pend) return false;
-    pmn = mn;
-    pend = mn + n;
-  }
-  return true;
-}
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 bool valid(const HeatOverlayArgs& a) {
   if (!a.inp || !a.out || !a.tab || !a.xb || !a.xk || !a.yb || !a.yk || !a.h_xb || !a.h_yb) return false;
   if (!aligned16(a.out) || !aligned16(a.tab) || !aligned16(a.xb) || !aligned16(a.xk) || !aligned16(a.yb) ||
@@ -251,13 +187,7 @@ bool valid(const HeatOverlayArgs& a) {
   if (a.a < 0 || a.a > 256 || (a.blend != 0 && a.blend != 1)) return false;
   if (a.xks < 1 || a.xks > kOverlayMaxTaps || a.yks < 1 || a.yks > kOverlayMaxTaps) return false;
   if (!valid_bounds(a.h_xb, a.S, a.w, a.xks) || !valid_bounds(a.h_yb, a.S, a.h, a.yks)) return false;
-  const int reach = 15 / (a.S * 3) + 1;
-  for (int r0 = 0; r0 < a.S; r0 += kOverlayBand) {               // the map rows one workgroup stages
-    int r1 = r0 + kOverlayBand + reach;
-    r1 = r1 < a.S ? r1 : a.S;
-    if (a.h_yb[2 * (r1 - 1)] + a.h_yb[2 * (r1 - 1) + 1] - a.h_yb[2 * r0] > kOverlayMaxRows) return false;
-  }
-  return true;
+  return valid_band_rows(a.h_yb, a.S, kOverlayBand, 15 / (a.S * 3) + 1);   // the map rows one workgroup stages
 }
 
 }  // namespace

@@ -132,6 +132,38 @@ def pack_overlay_jpeg(classes, scores, heat, files, max_bytes: int):
     return rows
 
 
+def unpack_palette(rows, h: int, w: int, K: int) -> tuple:
+    """Packed palette rows [n, 2 + h*w + 1 + 2K] (a torch tensor or numpy array of 32-bit words) ->
+    (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], W uint32 [n], colours uint8 [n, K, 3],
+    weights uint32 [n, K])."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    front = 2 + h * w
+    assert a.ndim == 2 and a.shape[1] == front + 1 + 2 * K, (a.shape, h, w, K)
+    tail = np.ascontiguousarray(a[:, front:]).view(np.uint32)
+    packed = tail[:, 1::2]
+    cols = np.stack([packed & 255, (packed >> 8) & 255, (packed >> 16) & 255], axis=-1).astype(np.uint8)
+    return unpack_explain(a[:, :front], h, w) + (tail[:, 0].copy(), cols, tail[:, 2::2].copy())
+
+
+def pack_palette(classes, scores, heat, totals, colours, weights):
+    """The inverse of ``unpack_palette``: numpy rows of fp32 words; the integers are copied as bits, never
+    through a float."""
+    import numpy as np
+    front = pack_explain(classes, scores, heat)
+    n, f = front.shape
+    c = np.asarray(colours, dtype=np.uint32).reshape(n, -1, 3)
+    K = c.shape[1]
+    rows = np.zeros((n, f + 1 + 2 * K), dtype=np.float32)
+    rows[:, :f] = front
+    tail = rows.view(np.uint32)[:, f:]
+    tail[:, 0] = np.asarray(totals, dtype=np.uint32).reshape(n)
+    tail[:, 1::2] = c[..., 0] | (c[..., 1] << 8) | (c[..., 2] << 16)
+    tail[:, 2::2] = np.asarray(weights, dtype=np.uint32).reshape(n, K)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -170,15 +202,36 @@ class OverlayJpeg:
     max_bytes: int | None = None
 
 
+@dataclass(frozen=True)
+class Palette:
+    """Dominant-colour outputs of an ``explain`` / ``rollout`` engine (``EngineBase(palette=...)``): the
+    ``colors`` (1..8) dominant colours of the input picture after ``rounds`` (1..16) clustering rounds over
+    its 4096-bin histogram, every pixel weighted by the heatmap upsampled with ``filter`` ("bilinear" |
+    "bicubic", Pillow's) when ``weight`` is "map", or all alike when it is "uniform".
+    kdl/serving/palette.py defines the rule."""
+    colors: int = 5
+    weight: str = "map"
+    filter: str = "bilinear"
+    rounds: int = 8
+
+
 class EngineBase:
     model_name = "model"
     # tail step kind -> the method that emits it; every other kind is the family's (_emit)
     TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
-                     "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg"}
+                     "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg",
+                     "palette": "_emit_palette"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
                  explain: bool = False, rollout: bool = False, overlay: Overlay | None = None,
-                 overlay_jpeg: OverlayJpeg | None = None):
+                 overlay_jpeg: OverlayJpeg | None = None, palette: Palette | None = None):
+        if palette is not None:      # before anything touches the device
+            if not (explain or rollout):
+                raise ValueError("palette weighs the picture by a heatmap: it needs explain=True or rollout=True")
+            if overlay is not None:
+                raise ValueError("palette and overlay both extend the heatmap rows: set one of them")
+            from ..serving.palette import check as check_palette
+            check_palette(palette)
         if overlay_jpeg is not None:
             if overlay is None:
                 raise ValueError("overlay_jpeg encodes the rendered overlay: it needs overlay=Overlay(...)")
@@ -237,6 +290,10 @@ class EngineBase:
         # the raw row's front words, a length word and the encoded file (_enable_overlay_jpeg)
         self.overlay_jpeg: OverlayJpeg | None = overlay_jpeg
         self._jpeg: dict = {}                         # overlay_jpeg only: header, cap, per-slot raw rows and workspaces
+        # dominant colours: None = the rows end with the map; a ``Palette`` = the rows also carry W and K x
+        # (colour, weight), written by one more step behind the map's (_enable_palette)
+        self.palette: Palette | None = palette
+        self._palette_tabs: dict = {}                 # palette only: device tables, their host copies, per-slot histograms
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -276,6 +333,7 @@ class EngineBase:
         if hw:
             self._enable_overlay(*hw)
             self._enable_overlay_jpeg(*hw)
+            self._enable_palette(*hw)
 
     def _enable_heatmap(self) -> tuple:
         """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
@@ -551,6 +609,53 @@ class EngineBase:
             work=_lib.ptr(work), B=b, H=S, W=S, quality=self.overlay_jpeg.quality, sampling=j["sampling"],
             cap=j["cap"]))
 
+    # ---------------------------------------------------------------- dominant colours
+    def _enable_palette(self, h: int, w: int) -> None:
+        """Called by ``_enable_outputs`` behind the heatmap tail. With ``palette`` the output rows grow to
+        2 + h*w + 1 + 2K words: ``class_map`` / ``rollout_map`` take ``ldo`` and write the front of the wider
+        row unchanged, and one more step "palette" (kernels/palette.hip) reads the map from the row and the
+        slot's uint8 input (``src="input"``, through ``_ptr``, with the lifetime ``_enable_overlay``
+        describes) and writes W and the K (colour, weight) pairs behind the map (``unpack_palette``). Each
+        slot has its own histogram workspace, which the step leaves zeroed."""
+        if self.palette is None:
+            return
+        assert not self.inputs, "palette is set at construction, before input slots exist"
+        from ..serving import overlay as O
+        from ..serving import palette as PL
+        lib = _lib.lib()
+        S, pal = self.inp.shape[1], self.palette
+        if self.inp.dtype != torch.uint8:
+            raise ValueError("palette reads the uint8 picture the model saw: a float-input engine has none")
+        if self.inp.shape[2] != S or S < max(h, w) or S > lib.OVERLAY_MAX_S:
+            raise ValueError(f"palette: a {h} x {w} map on a {tuple(self.inp.shape[1:3])} input; the kernel "
+                             f"upsamples onto square inputs up to {lib.OVERLAY_MAX_S}")
+        xb, xk = O.axis_tables(w, S, pal.filter)
+        yb, yk = O.axis_tables(h, S, pal.filter)
+        host = dict(xb=xb, xk=xk, yb=yb, yk=yk)
+        self._palette_tabs = dict(host=host, dev={k: torch.from_numpy(v).to(self.device) for k, v in host.items()},
+                                  hw=(h, w), weight=PL.WEIGHTS.index(pal.weight), work=[])
+        assert self.logits.shape[1] == 2 + h * w, (self.logits.shape, h, w)
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + 1 + 2 * pal.colors), dtype=torch.float32,
+                                  device=self.device)
+        self.steps.append(Step("palette", "palette", src="input"))
+
+    def _palette_workspace(self, slot: int) -> torch.Tensor:
+        work = self._palette_tabs["work"]
+        while len(work) <= slot:
+            work.append(torch.zeros(_lib.lib().palette_workspace(self.max_batch), dtype=torch.uint8,
+                                    device=self.device))
+        return work[slot]
+
+    def _emit_palette(self, prog, step: Step, b: int) -> None:
+        t = self._palette_tabs
+        host, dev, (h, w), out = t["host"], t["dev"], t["hw"], self._out_rows()
+        prog.add_palette(step.name, dict(
+            inp=self._ptr(step.src), out=_lib.ptr(out), work=_lib.ptr(self._palette_workspace(self._slot)),
+            xb=_lib.ptr(dev["xb"]), xk=_lib.ptr(dev["xk"]), yb=_lib.ptr(dev["yb"]), yk=_lib.ptr(dev["yk"]),
+            h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
+            ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], K=self.palette.colors,
+            T=self.palette.rounds, weight=t["weight"]))
+
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
         ``rollout`` engine."""
@@ -682,7 +787,7 @@ class EngineBase:
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
         engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
         [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``, with
-        ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``)."""
+        ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``, with ``palette`` the rows of ``unpack_palette``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

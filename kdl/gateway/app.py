@@ -15,6 +15,9 @@ method the version has painted on it (the overlay signature of the mode), label 
 ``X-KDL-Label`` / ``X-KDL-Score``; with ``"format": "json"`` -> ``{"label", "score", "heatmap", "png": "<base64>"}``;
 with ``"format": "jpeg"`` -> ``image/jpeg``: the file the model server encoded (the overlay_jpeg signature of the
 mode, on a version that has it), handed on byte for byte, the same two headers.
+``POST /colors {"url": ...}`` -> ``{"label", "score", "colors": [{"rgb": [r, g, b], "hex": "#rrggbb", "name",
+"fraction"}, ...]}``: the predicted class and the garment's dominant colours, heaviest first (the palette signature
+of the mode, on a version that has it); colours of weight 0 are left out.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -49,7 +52,7 @@ from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
                      process_embed_response, process_explain_response, process_overlay_response,
-                     process_response, process_similar_response, png_bytes)
+                     process_palette_response, process_response, process_similar_response, png_bytes)
 
 
 class GatewayConfig:
@@ -195,6 +198,10 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     @app.route("/attention", methods=["POST"])
     def attention():
         return one_image("attention", lambda pb, _: jsonify(process_explain_response(pb)[0]))
+
+    @app.route("/colors", methods=["POST"])
+    def colors():
+        return one_image("palette", lambda pb, _: jsonify(process_palette_response(pb)[0]))
 
     @app.route("/overlay", methods=["POST"])
     def overlay():

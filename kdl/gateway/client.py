@@ -103,6 +103,22 @@ def process_explain_response(pb_result) -> list[dict]:
              "heatmap": [[float(v) for v in row] for row in maps[i]]} for i in range(n)]
 
 
+def process_palette_response(pb_result) -> list[dict]:
+    """A palette signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT [n, 1],
+    ``colors`` DT_UINT8 [n, K, 3] as ``tensor_content``, ``fractions`` DT_FLOAT [n, K], ``names`` DT_STRING
+    [n, K]) -> per image ``{"label", "score", "colors": [{"rgb", "hex", "name", "fraction"}, ...]}``, heaviest
+    first, the colours of fraction 0 dropped."""
+    o = pb_result.outputs
+    cl, sc, fr, nm = o["classes"], o["scores"], o["fractions"], o["names"]
+    n, K = [d.size for d in fr.tensor_shape.dim]
+    rgb = np.frombuffer(o["colors"].tensor_content, dtype=np.uint8).reshape(n, K, 3)
+    frac = np.asarray(fr.float_val, dtype=np.float32).reshape(n, K)
+    return [{"label": cl.string_val[i].decode(), "score": float(sc.float_val[i]),
+             "colors": [{"rgb": [int(v) for v in rgb[i, j]], "hex": "#%02x%02x%02x" % tuple(int(v) for v in rgb[i, j]),
+                         "name": nm.string_val[i * K + j].decode(), "fraction": float(frac[i, j])}
+                        for j in range(K) if frac[i, j] > 0]} for i in range(n)]
+
+
 def process_overlay_response(pb_result) -> list[dict]:
     """An overlay signature's PredictResponse (explain's three outputs and ``overlay`` DT_UINT8
     [n, S, S, 3] as ``tensor_content``) -> per image ``{"label", "score", "heatmap", "picture"}``, the

@@ -1,8 +1,8 @@
 """One description per kind of result row.
 
-A signature answers with one of eight kinds of row: the fp32 ``logits``, or what the ``classify``,
-``embed``, ``similar``, ``explain``, ``attention``, ``overlay`` and ``overlay_jpeg`` trios pack into the same
-fp32 words.
+A signature answers with one of nine kinds of row: the fp32 ``logits``, or what the ``classify``,
+``embed``, ``similar``, ``explain``, ``attention``, ``overlay``, ``overlay_jpeg`` and ``palette`` trios pack
+into the same fp32 words.
 Everything that differs between the kinds is in ``KINDS``; runners, executors, answer builders and the
 loader ask the table and name no kind. Per kind:
 
@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from ..engine.base import overlay_jpeg_cap, overlay_words
-from . import classify, embed, explain, jpeg_encode, overlay, rollout, similar
+from . import classify, embed, explain, jpeg_encode, overlay, palette, rollout, similar
 from . import protos as P
 from .jpeg import BYTES_SIGNATURE
 from .metrics import METRICS
@@ -53,6 +53,10 @@ def _map_kw(sig, src, dev) -> dict:
 
 def _jpeg_kw(sig, src, dev) -> dict:
     return dict(_map_kw(sig, src, dev), overlay_jpeg=src.overlay_jpeg)
+
+
+def _palette_kw(sig, src, dev) -> dict:
+    return dict(_map_kw(sig, src, dev), palette=src.palette)
 
 
 # ---------------------------------------------------------------------- CPU executor rows
@@ -80,6 +84,9 @@ def _map_rows(sig, src, x):
     oracle = _info(src).rollout_oracle if sig.rollout else _info(src).cam_oracle
     kw = dict(head=src.head) if src.family == "xception" and src.head is not None else {}
     k, score, heat = (t.numpy() for t in oracle(src.params, x, **kw))
+    if _is_palette(sig):
+        ans = [palette.palette_rule(img, m, src.palette) for img, m in zip(x.numpy(), heat)]
+        return palette.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(3)))
     if not sig.overlay:
         return explain.pack_rows(k, score, heat)
     pics = [overlay.overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat)]
@@ -92,6 +99,19 @@ def _map_rows(sig, src, x):
 
 def _map_words(sig, src) -> int:
     return 2 + sig.explain[0] * sig.explain[1] + (overlay_words(sig.overlay) if sig.overlay else 0)
+
+
+def _is_palette(sig) -> bool:
+    """An explain-kind signature with a ``fractions`` output answers colours."""
+    return bool(sig.explain and any(o[0] == "fractions" for o in sig.outputs))
+
+
+def _palette_k(sig) -> int:
+    return next(o[2][1] for o in sig.outputs if o[0] == "fractions")
+
+
+def _palette_words(sig, src) -> int:
+    return 2 + sig.explain[0] * sig.explain[1] + 1 + 2 * _palette_k(sig)
 
 
 def _is_jpeg(sig) -> bool:
@@ -140,6 +160,13 @@ def _jpeg_columns(src, sig, rows) -> list:
     return _front_columns(src, classes, scores, heat) + [("jpeg_bytes", P.DT_STRING, files)]
 
 
+def _palette_columns(src, sig, rows) -> list:
+    classes, scores, heat, totals, colours, weights = palette.unpack_rows(rows, *sig.explain, _palette_k(sig))
+    return _front_columns(src, classes, scores, heat)[:2] + [
+        ("colors", P.DT_UINT8, colours), ("fractions", P.DT_FLOAT, palette.fractions_of(weights, totals)),
+        ("names", P.DT_STRING, palette.names_of(colours))]
+
+
 @dataclass(frozen=True)
 class Kind:
     name: str
@@ -176,6 +203,8 @@ KINDS = {k.name: k for k in (
     Kind("overlay", overlay.OVERLAY_SIGNATURES, "kdl_overlay_total", **_MAP),
     Kind("overlay_jpeg", jpeg_encode.OVERLAY_JPEG_SIGNATURES, "kdl_overlay_jpeg_total",
          **dict(_MAP, engine=_jpeg_kw, gpu_words=_jpeg_words, columns=_jpeg_columns)),
+    Kind("palette", palette.PALETTE_SIGNATURES, "kdl_palette_total",
+         **dict(_MAP, engine=_palette_kw, gpu_words=_palette_words, columns=_palette_columns)),
 )}
 # the second and third name of every trio -> (0 any-size image / 1 encoded file, the trio's first name)
 WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate(k.trio[1:])}
@@ -183,7 +212,7 @@ WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate
 
 def kind_of(sig) -> Kind:
     """The kind of a signature's rows, from the fields SignatureInfo has."""
-    name = ("overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
+    name = ("palette" if _is_palette(sig) else "overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
             "explain" if sig.explain else "similar" if sig.similar else "classify" if sig.top_k else
             "embed" if sig.embed else "logits")
     return KINDS[name]
