@@ -261,6 +261,15 @@ PaletteArgs palette_args(const py::dict& d) {
   a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.K = I(d, "K"); a.T = I(d, "T"); a.weight = I(d, "weight", -1);
   return a;
 }
+LocateArgs locate_args(const py::dict& d) {
+  LocateArgs a{};
+  a.out = P<float>(d, "out"); a.work = P<uint8_t>(d, "work");
+  a.xb = P<const int32_t>(d, "xb"); a.xk = P<const int32_t>(d, "xk"); a.yb = P<const int32_t>(d, "yb");
+  a.yk = P<const int32_t>(d, "yk"); a.h_xb = P<const int32_t>(d, "h_xb"); a.h_yb = P<const int32_t>(d, "h_yb");
+  a.B = I(d, "B"); a.S = I(d, "S"); a.h = I(d, "h"); a.w = I(d, "w"); a.ldo = I(d, "ldo");
+  a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.K = I(d, "K"); a.threshold = I(d, "threshold");
+  return a;
+}
 JpegEncodeArgs jpeg_encode_args(const py::dict& d) {
   JpegEncodeArgs a{};
   a.inp = P<const uint8_t>(d, "inp"); a.hdr = P<const uint8_t>(d, "hdr"); a.h_hdr = P<const uint8_t>(d, "h_hdr");
@@ -423,6 +432,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("palette_workspace", [](int B) { return palette_workspace(B); });
   m.attr("PALETTE_MAX_K") = int(kPaletteMaxK);
   m.attr("PALETTE_MAX_T") = int(kPaletteMaxT);
+  // garment boxes (kernels/locate.hip): d = the LocateArgs fields; h_xb / h_yb are HOST addresses
+  m.def("locate", [](py::dict d, uintptr_t s) {
+    const auto a = locate_args(d);
+    py::gil_scoped_release nogil;
+    chk(locate(a, S(s)), "locate");
+  });
+  m.def("locate_workspace", [](int B, int S) { return locate_workspace(B, S); });
+  m.attr("LOCATE_MAX_K") = int(kLocateMaxK);
+  m.attr("LOCATE_LDS_RUNS") = int(kLocateLdsRuns);
   // baseline JPEG encode (kernels/jpeg_encode.hip): d = the JpegEncodeArgs fields; h_hdr is a HOST address
   m.def("jpeg_encode", [](py::dict d, uintptr_t s) {
     const auto a = jpeg_encode_args(d);
@@ -790,6 +808,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_palette", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_PALETTE; op.name = name; op.pal = palette_args(d); p.add(op);
+      })
+      .def("add_locate", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_LOCATE; op.name = name; op.loc = locate_args(d); p.add(op);
       })
       .def("add_jpeg_encode", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_JPEG_ENCODE; op.name = name; op.je = jpeg_encode_args(d); p.add(op);

@@ -571,6 +571,46 @@ struct PaletteArgs {
 size_t palette_workspace(int B);
 hipError_t palette(const PaletteArgs& a, hipStream_t s);
 
+// Garment boxes (kernels/locate.hip): behind class_map / rollout_map, two launches answer each image's K
+// largest connected regions of its own heatmap, in integers throughout (kdl/serving/locate.py
+// locate_rule is the definition):
+//   mask  = u >= threshold with u the map upsampled as heat_overlay does
+//   8-connected components; a component's identity is its first pixel in raster order
+//   count = all components; the K largest by pixel count, ties to the earlier first pixel
+// heat is read from the image's own output row, out[b][2 .. 2 + h*w), and 1 + 3K words are written
+// behind it: count, then K x (y0 | x0 << 16, y1 | x1 << 16, area), y1 and x1 exclusive; boxes that do
+// not exist are 0, 0, 0. Nothing else is written: the words before and after them up to ldo and rows
+// >= B stay as they were. The picture is never read. `work` is locate_workspace(B, S) bytes; every
+// launch writes all it reads of it first (the bitmask whole, the run tables up to the image's run
+// count), so a replay needs nothing from the host and the content before a launch does not matter.
+// Per image it holds the bitmask, S rows of ceil(S / 64) 64-bit words, and, where S * ceil(S / 2) >
+// kLocateLdsRuns, three uint32 tables of S * ceil(S / 2) runs: S*S/8 + 6*S*S bytes, 6.2 per pixel.
+// The result does not depend on the order of the atomics or on the schedule.
+// out / work / xb / xk / yb / yk / h_xb / h_yb null, out, work or a device table not 16-byte aligned,
+// B outside 1..65535, h < 1, w < 1, h*w > kClassMapMaxHW, S < max(h, w), S > kOverlayMaxS (coordinates
+// in 16 bits), ldo < 2 + h*w + 1 + 3K, K outside 1..kLocateMaxK, threshold outside 1..255, xks / yks
+// outside 1..kOverlayMaxTaps, and bounds tables (checked from the host copies) whose taps leave the
+// map, step back, or need more than kOverlayMaxRows map rows for kOverlayBand output rows are
+// hipErrorInvalidValue, and nothing is launched.
+constexpr int kLocateMaxK = 8;
+constexpr int kLocateLdsRuns = 1920;   // an image with more runs keeps its run tables in `work`, not in LDS
+struct LocateArgs {
+  float* out;             // [B][ldo] words: class, score, h*w heat values (read), count and K x (corner, corner, area) (written)
+  uint8_t* work;          // locate_workspace(B, S) bytes
+  const int32_t* xb;      // device: bounds [S][2] of the columns, {first map column, taps}
+  const int32_t* xk;      // device: coefficients [S][xks]
+  const int32_t* yb;      // device: the same of the rows
+  const int32_t* yk;      // device: [S][yks]
+  const int32_t* h_xb;    // HOST copies of the bounds (checked here, never followed on the device)
+  const int32_t* h_yb;
+  int B, S, h, w, ldo;
+  int xks, yks;           // taps per column / row of the tables
+  int K;                  // boxes
+  int threshold;          // 1..255 of the upsampled map
+};
+size_t locate_workspace(int B, int S);
+hipError_t locate(const LocateArgs& a, hipStream_t s);
+
 // Baseline JPEG encode (kernels/jpeg_encode.hip): B pictures uint8 [H][W][3], picture b at inp + b * ldi
 // bytes (any alignment), each into the file Pillow's Image.save(.., "JPEG", quality, subsampling,
 // optimize=False) writes, byte for byte (kdl/serving/jpeg_encode.py encode_rule is the definition:

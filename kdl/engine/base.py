@@ -164,6 +164,39 @@ def pack_palette(classes, scores, heat, totals, colours, weights):
     return rows
 
 
+def unpack_locate(rows, h: int, w: int, K: int) -> tuple:
+    """Packed locate rows [n, 2 + h*w + 1 + 3K] (a torch tensor or numpy array of 32-bit words) ->
+    (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], counts uint32 [n], boxes int32 [n, K, 4] as
+    (y0, x0, y1, x1), areas uint32 [n, K])."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    front = 2 + h * w
+    assert a.ndim == 2 and a.shape[1] == front + 1 + 3 * K, (a.shape, h, w, K)
+    tail = np.ascontiguousarray(a[:, front:]).view(np.uint32)
+    lo, hi = tail[:, 1::3], tail[:, 2::3]
+    boxes = np.stack([lo & 0xFFFF, lo >> 16, hi & 0xFFFF, hi >> 16], axis=-1).astype(np.int32)
+    return unpack_explain(a[:, :front], h, w) + (tail[:, 0].copy(), boxes, tail[:, 3::3].copy())
+
+
+def pack_locate(classes, scores, heat, counts, boxes, areas):
+    """The inverse of ``unpack_locate``: numpy rows of fp32 words; the integers are copied as bits, never
+    through a float."""
+    import numpy as np
+    front = pack_explain(classes, scores, heat)
+    n, f = front.shape
+    bx = np.asarray(boxes, dtype=np.uint32).reshape(n, -1, 4)
+    K = bx.shape[1]
+    rows = np.zeros((n, f + 1 + 3 * K), dtype=np.float32)
+    rows[:, :f] = front
+    tail = rows.view(np.uint32)[:, f:]
+    tail[:, 0] = np.asarray(counts, dtype=np.uint32).reshape(n)
+    tail[:, 1::3] = bx[..., 0] | (bx[..., 1] << 16)
+    tail[:, 2::3] = bx[..., 2] | (bx[..., 3] << 16)
+    tail[:, 3::3] = np.asarray(areas, dtype=np.uint32).reshape(n, K)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -215,16 +248,35 @@ class Palette:
     rounds: int = 8
 
 
+@dataclass(frozen=True)
+class Locate:
+    """Garment-box outputs of an ``explain`` / ``rollout`` engine (``EngineBase(locate=...)``): the ``boxes``
+    (1..8) largest 8-connected regions of the heatmap upsampled with ``filter`` ("bilinear" | "bicubic",
+    Pillow's) and cut at ``threshold`` (1..255 of the quantised map; 51 is 20 % of the peak).
+    kdl/serving/locate.py defines the rule."""
+    boxes: int = 3
+    threshold: int = 51
+    filter: str = "bilinear"
+
+
 class EngineBase:
     model_name = "model"
     # tail step kind -> the method that emits it; every other kind is the family's (_emit)
     TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
                      "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg",
-                     "palette": "_emit_palette"}
+                     "palette": "_emit_palette", "locate": "_emit_locate"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
                  explain: bool = False, rollout: bool = False, overlay: Overlay | None = None,
-                 overlay_jpeg: OverlayJpeg | None = None, palette: Palette | None = None):
+                 overlay_jpeg: OverlayJpeg | None = None, palette: Palette | None = None,
+                 locate: Locate | None = None):
+        if locate is not None:       # before anything touches the device
+            if not (explain or rollout):
+                raise ValueError("locate cuts boxes out of a heatmap: it needs explain=True or rollout=True")
+            if overlay is not None or palette is not None:
+                raise ValueError("locate, palette and overlay each extend the heatmap rows: set one of them")
+            from ..serving.locate import check as check_locate
+            check_locate(locate)
         if palette is not None:      # before anything touches the device
             if not (explain or rollout):
                 raise ValueError("palette weighs the picture by a heatmap: it needs explain=True or rollout=True")
@@ -294,6 +346,10 @@ class EngineBase:
         # (colour, weight), written by one more step behind the map's (_enable_palette)
         self.palette: Palette | None = palette
         self._palette_tabs: dict = {}                 # palette only: device tables, their host copies, per-slot histograms
+        # garment boxes: None = the rows end with the map; a ``Locate`` = the rows also carry the region count
+        # and K x (corner, corner, area), written by one more step behind the map's (_enable_locate)
+        self.locate: Locate | None = locate
+        self._locate_tabs: dict = {}                  # locate only: device tables, their host copies, per-slot workspaces
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -334,6 +390,7 @@ class EngineBase:
             self._enable_overlay(*hw)
             self._enable_overlay_jpeg(*hw)
             self._enable_palette(*hw)
+            self._enable_locate(*hw)
 
     def _enable_heatmap(self) -> tuple:
         """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
@@ -656,6 +713,50 @@ class EngineBase:
             ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], K=self.palette.colors,
             T=self.palette.rounds, weight=t["weight"]))
 
+    # ---------------------------------------------------------------- garment boxes
+    def _enable_locate(self, h: int, w: int) -> None:
+        """Called by ``_enable_outputs`` behind the heatmap tail. With ``locate`` the output rows grow to
+        2 + h*w + 1 + 3K words: ``class_map`` / ``rollout_map`` take ``ldo`` and write the front of the wider
+        row unchanged, and one more step "locate" (kernels/locate.hip) reads the map from the row, never the
+        picture, and writes the region count and the K (corner, corner, area) triples behind the map
+        (``unpack_locate``). Each slot has its own workspace (the bitmask and the run tables), which every
+        launch initialises before it reads it."""
+        if self.locate is None:
+            return
+        assert not self.inputs, "locate is set at construction, before input slots exist"
+        from ..serving import overlay as O
+        lib = _lib.lib()
+        S, loc = self.inp.shape[1], self.locate
+        if self.inp.shape[2] != S or S < max(h, w) or S > lib.OVERLAY_MAX_S:
+            raise ValueError(f"locate: a {h} x {w} map on a {tuple(self.inp.shape[1:3])} input; the kernel "
+                             f"upsamples onto square inputs up to {lib.OVERLAY_MAX_S}")
+        xb, xk = O.axis_tables(w, S, loc.filter)
+        yb, yk = O.axis_tables(h, S, loc.filter)
+        host = dict(xb=xb, xk=xk, yb=yb, yk=yk)
+        self._locate_tabs = dict(host=host, dev={k: torch.from_numpy(v).to(self.device) for k, v in host.items()},
+                                 hw=(h, w), work=[])
+        assert self.logits.shape[1] == 2 + h * w, (self.logits.shape, h, w)
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + 1 + 3 * loc.boxes), dtype=torch.float32,
+                                  device=self.device)
+        self.steps.append(Step("locate", "locate"))
+
+    def _locate_workspace(self, slot: int) -> torch.Tensor:
+        work = self._locate_tabs["work"]
+        while len(work) <= slot:
+            work.append(torch.zeros(_lib.lib().locate_workspace(self.max_batch, self.inp.shape[1]), dtype=torch.uint8,
+                                    device=self.device))
+        return work[slot]
+
+    def _emit_locate(self, prog, step: Step, b: int) -> None:
+        t = self._locate_tabs
+        host, dev, (h, w), out = t["host"], t["dev"], t["hw"], self._out_rows()
+        prog.add_locate(step.name, dict(
+            out=_lib.ptr(out), work=_lib.ptr(self._locate_workspace(self._slot)),
+            xb=_lib.ptr(dev["xb"]), xk=_lib.ptr(dev["xk"]), yb=_lib.ptr(dev["yb"]), yk=_lib.ptr(dev["yk"]),
+            h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
+            ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], K=self.locate.boxes,
+            threshold=self.locate.threshold))
+
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
         ``rollout`` engine."""
@@ -787,7 +888,8 @@ class EngineBase:
         (a ``topk`` or ``similar`` engine: the packed rows [n, 2K], see ``unpack_topk``; an ``embed``
         engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
         [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``, with
-        ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``, with ``palette`` the rows of ``unpack_palette``)."""
+        ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``, with ``palette`` the rows of ``unpack_palette``,
+        with ``locate`` the rows of ``unpack_locate``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

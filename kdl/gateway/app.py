@@ -18,6 +18,10 @@ mode, on a version that has it), handed on byte for byte, the same two headers.
 ``POST /colors {"url": ...}`` -> ``{"label", "score", "colors": [{"rgb": [r, g, b], "hex": "#rrggbb", "name",
 "fraction"}, ...]}``: the predicted class and the garment's dominant colours, heaviest first (the palette signature
 of the mode, on a version that has it); colours of weight 0 are left out.
+``POST /locate {"url": ...}`` -> ``{"label", "score", "count", "boxes": [{"box": [ymin, xmin, ymax, xmax], "area"},
+...]}``: the predicted class and the garment's boxes, largest first, as fractions of the picture the model saw (the
+locate signature of the mode, on a version that has it); ``count`` is the number of all regions, boxes of area 0 are
+left out.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -51,7 +55,8 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_embed_response, process_explain_response, process_overlay_response,
+                     process_embed_response, process_explain_response, process_locate_response,
+                     process_overlay_response,
                      process_palette_response, process_response, process_similar_response, png_bytes)
 
 
@@ -202,6 +207,10 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     @app.route("/colors", methods=["POST"])
     def colors():
         return one_image("palette", lambda pb, _: jsonify(process_palette_response(pb)[0]))
+
+    @app.route("/locate", methods=["POST"])
+    def locate():
+        return one_image("locate", lambda pb, _: jsonify(process_locate_response(pb)[0]))
 
     @app.route("/overlay", methods=["POST"])
     def overlay():

@@ -119,6 +119,21 @@ def process_palette_response(pb_result) -> list[dict]:
                         for j in range(K) if frac[i, j] > 0]} for i in range(n)]
 
 
+def process_locate_response(pb_result) -> list[dict]:
+    """A locate signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT [n, 1], ``boxes``
+    DT_FLOAT [n, K, 4], ``areas`` DT_FLOAT [n, K], ``num_boxes`` DT_INT32 [n, 1]) -> per image ``{"label",
+    "score", "count", "boxes": [{"box": [ymin, xmin, ymax, xmax], "area"}, ...]}``, largest first, the boxes
+    of area 0 dropped. The coordinates are fractions of the picture the model saw."""
+    o = pb_result.outputs
+    cl, sc, ar = o["classes"], o["scores"], o["areas"]
+    n, K = [d.size for d in ar.tensor_shape.dim]
+    box = np.asarray(o["boxes"].float_val, dtype=np.float32).reshape(n, K, 4)
+    area = np.asarray(ar.float_val, dtype=np.float32).reshape(n, K)
+    return [{"label": cl.string_val[i].decode(), "score": float(sc.float_val[i]), "count": int(o["num_boxes"].int_val[i]),
+             "boxes": [{"box": [float(v) for v in box[i, j]], "area": float(area[i, j])}
+                       for j in range(K) if area[i, j] > 0]} for i in range(n)]
+
+
 def process_overlay_response(pb_result) -> list[dict]:
     """An overlay signature's PredictResponse (explain's three outputs and ``overlay`` DT_UINT8
     [n, S, S, 3] as ``tensor_content``) -> per image ``{"label", "score", "heatmap", "picture"}``, the

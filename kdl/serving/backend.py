@@ -126,6 +126,8 @@ class ModelSource:
     overlay_jpeg: object = None
     # dominant colours (serving/palette.py): the version's engine.base.Palette (None = no palette signatures)
     palette: object = None
+    # garment boxes (serving/locate.py): the version's engine.base.Locate (None = no locate signatures)
+    locate: object = None
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -148,7 +150,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      classify_top_k: int | None = None, embedding_normalize: str | None = None,
                      similar_top_k: int | None = None, gallery: bool = True,
                      overlay_colormap: str | None = None, overlay_alpha: float | None = None,
-                     overlay_jpeg_quality: int | None = None, palette_colors: int | None = None) -> ModelSource:
+                     overlay_jpeg_quality: int | None = None, palette_colors: int | None = None,
+                     locate_boxes: int | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
@@ -160,7 +163,9 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     version's "overlay" block (serving/overlay.py); ``overlay_jpeg_quality`` (--overlay_jpeg_quality) turns
     the overlay_jpeg signatures on and overrides the quality of the version's "overlay_jpeg" block
     (serving/jpeg_encode.py); ``palette_colors`` (--palette_colors) turns the palette signatures on and
-    overrides the colour count of the version's "palette" block (serving/palette.py)."""
+    overrides the colour count of the version's "palette" block (serving/palette.py); ``locate_boxes``
+    (--locate_boxes) turns the locate signatures on and overrides the box count of the version's "locate"
+    block (serving/locate.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -172,7 +177,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
-    from . import classify, embed, explain, jpeg_encode, overlay, palette, rollout, similar
+    from . import classify, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
@@ -182,6 +187,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     overlay.add_signatures(src, path, overlay_colormap, overlay_alpha)
     jpeg_encode.add_signatures(src, path, overlay_jpeg_quality)
     palette.add_signatures(src, path, palette_colors)
+    locate.add_signatures(src, path, locate_boxes)
     return src
 
 

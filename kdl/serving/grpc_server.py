@@ -305,7 +305,7 @@ def _strings(values):
 def predict_response(s, sig, rows, output_filter) -> bytes:
     """The PredictResponse of an answered request. A kind with named outputs (serving/outputs.py):
     every column, or the subset ``output_filter`` names, strings as ``string_val``, floats as
-    ``float_val``, uint8 as ``tensor_content``. The single fp32 output of the logits and embed
+    ``float_val``, int32 as ``int_val``, uint8 as ``tensor_content``. The single fp32 output of the logits and embed
     signatures is built natively (the hot path; the native front-end's learned route counts its
     own in kdl_requests_total only)."""
     cols = O.columns(s.source, sig, rows)
@@ -325,6 +325,8 @@ def predict_response(s, sig, rows, output_filter) -> bytes:
             t.string_val.extend(_strings(values))
         elif dtype == P.DT_UINT8:
             t.tensor_content = values.tobytes()
+        elif dtype == P.DT_INT32:
+            t.int_val.extend(values.reshape(-1).tolist())
         else:
             t.float_val.extend(values.reshape(-1).tolist())
         for d in ((len(values),) if isinstance(values, list) and values and isinstance(values[0], bytes)

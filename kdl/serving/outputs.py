@@ -1,8 +1,8 @@
 """One description per kind of result row.
 
-A signature answers with one of nine kinds of row: the fp32 ``logits``, or what the ``classify``,
-``embed``, ``similar``, ``explain``, ``attention``, ``overlay``, ``overlay_jpeg`` and ``palette`` trios pack
-into the same fp32 words.
+A signature answers with one of ten kinds of row: the fp32 ``logits``, or what the ``classify``,
+``embed``, ``similar``, ``explain``, ``attention``, ``overlay``, ``overlay_jpeg``, ``palette`` and ``locate``
+trios pack into the same fp32 words.
 Everything that differs between the kinds is in ``KINDS``; runners, executors, answer builders and the
 loader ask the table and name no kind. Per kind:
 
@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from ..engine.base import overlay_jpeg_cap, overlay_words
-from . import classify, embed, explain, jpeg_encode, overlay, palette, rollout, similar
+from . import classify, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
 from . import protos as P
 from .jpeg import BYTES_SIGNATURE
 from .metrics import METRICS
@@ -57,6 +57,10 @@ def _jpeg_kw(sig, src, dev) -> dict:
 
 def _palette_kw(sig, src, dev) -> dict:
     return dict(_map_kw(sig, src, dev), palette=src.palette)
+
+
+def _locate_kw(sig, src, dev) -> dict:
+    return dict(_map_kw(sig, src, dev), locate=src.locate)
 
 
 # ---------------------------------------------------------------------- CPU executor rows
@@ -87,6 +91,9 @@ def _map_rows(sig, src, x):
     if _is_palette(sig):
         ans = [palette.palette_rule(img, m, src.palette) for img, m in zip(x.numpy(), heat)]
         return palette.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(3)))
+    if _is_locate(sig):
+        ans = [locate.locate_rule(m, src.input_size, src.locate) for m in heat]
+        return locate.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(3)))
     if not sig.overlay:
         return explain.pack_rows(k, score, heat)
     pics = [overlay.overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat)]
@@ -112,6 +119,19 @@ def _palette_k(sig) -> int:
 
 def _palette_words(sig, src) -> int:
     return 2 + sig.explain[0] * sig.explain[1] + 1 + 2 * _palette_k(sig)
+
+
+def _is_locate(sig) -> bool:
+    """An explain-kind signature with a ``boxes`` output answers regions."""
+    return bool(sig.explain and any(o[0] == "boxes" for o in sig.outputs))
+
+
+def _locate_k(sig) -> int:
+    return next(o[2][1] for o in sig.outputs if o[0] == "boxes")
+
+
+def _locate_words(sig, src) -> int:
+    return 2 + sig.explain[0] * sig.explain[1] + 1 + 3 * _locate_k(sig)
 
 
 def _is_jpeg(sig) -> bool:
@@ -167,6 +187,14 @@ def _palette_columns(src, sig, rows) -> list:
         ("names", P.DT_STRING, palette.names_of(colours))]
 
 
+def _locate_columns(src, sig, rows) -> list:
+    classes, scores, heat, counts, boxes, areas = locate.unpack_rows(rows, *sig.explain, _locate_k(sig))
+    S = src.input_size
+    return _front_columns(src, classes, scores, heat)[:2] + [
+        ("boxes", P.DT_FLOAT, locate.boxes_of(boxes, S)), ("areas", P.DT_FLOAT, locate.areas_of(areas, S)),
+        ("num_boxes", P.DT_INT32, counts.astype(np.int32).reshape(-1, 1))]
+
+
 @dataclass(frozen=True)
 class Kind:
     name: str
@@ -205,6 +233,8 @@ KINDS = {k.name: k for k in (
          **dict(_MAP, engine=_jpeg_kw, gpu_words=_jpeg_words, columns=_jpeg_columns)),
     Kind("palette", palette.PALETTE_SIGNATURES, "kdl_palette_total",
          **dict(_MAP, engine=_palette_kw, gpu_words=_palette_words, columns=_palette_columns)),
+    Kind("locate", locate.LOCATE_SIGNATURES, "kdl_locate_total",
+         **dict(_MAP, engine=_locate_kw, gpu_words=_locate_words, columns=_locate_columns)),
 )}
 # the second and third name of every trio -> (0 any-size image / 1 encoded file, the trio's first name)
 WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate(k.trio[1:])}
@@ -212,7 +242,7 @@ WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate
 
 def kind_of(sig) -> Kind:
     """The kind of a signature's rows, from the fields SignatureInfo has."""
-    name = ("palette" if _is_palette(sig) else "overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
+    name = ("locate" if _is_locate(sig) else "palette" if _is_palette(sig) else "overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
             "explain" if sig.explain else "similar" if sig.similar else "classify" if sig.top_k else
             "embed" if sig.embed else "logits")
     return KINDS[name]
