@@ -270,6 +270,16 @@ LocateArgs locate_args(const py::dict& d) {
   a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.K = I(d, "K"); a.threshold = I(d, "threshold");
   return a;
 }
+CutoutArgs cutout_args(const py::dict& d) {
+  CutoutArgs a{};
+  a.inp = P<const uint8_t>(d, "inp"); a.out = P<float>(d, "out"); a.work = P<uint8_t>(d, "work");
+  a.xb = P<const int32_t>(d, "xb"); a.xk = P<const int32_t>(d, "xk"); a.yb = P<const int32_t>(d, "yb");
+  a.yk = P<const int32_t>(d, "yk"); a.h_xb = P<const int32_t>(d, "h_xb"); a.h_yb = P<const int32_t>(d, "h_yb");
+  a.B = I(d, "B"); a.S = I(d, "S"); a.h = I(d, "h"); a.w = I(d, "w"); a.ldo = I(d, "ldo");
+  a.xks = I(d, "xks"); a.yks = I(d, "yks"); a.gate = I(d, "gate"); a.rounds = I(d, "rounds", -1);
+  a.smooth = I(d, "smooth", -1); a.feather = I(d, "feather", -1);
+  return a;
+}
 JpegEncodeArgs jpeg_encode_args(const py::dict& d) {
   JpegEncodeArgs a{};
   a.inp = P<const uint8_t>(d, "inp"); a.hdr = P<const uint8_t>(d, "hdr"); a.h_hdr = P<const uint8_t>(d, "h_hdr");
@@ -441,6 +451,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("locate_workspace", [](int B, int S) { return locate_workspace(B, S); });
   m.attr("LOCATE_MAX_K") = int(kLocateMaxK);
   m.attr("LOCATE_LDS_RUNS") = int(kLocateLdsRuns);
+  // garment cutouts (kernels/cutout.hip): d = the CutoutArgs fields; h_xb / h_yb are HOST addresses
+  m.def("cutout", [](py::dict d, uintptr_t s) {
+    const auto a = cutout_args(d);
+    py::gil_scoped_release nogil;
+    chk(cutout(a, S(s)), "cutout");
+  });
+  m.def("cutout_workspace", [](int B, int S) { return cutout_workspace(B, S); });
+  m.attr("CUTOUT_MAX_ROUNDS") = int(kCutoutMaxRounds);
+  m.attr("CUTOUT_MAX_SMOOTH") = int(kCutoutMaxSmooth);
   // baseline JPEG encode (kernels/jpeg_encode.hip): d = the JpegEncodeArgs fields; h_hdr is a HOST address
   m.def("jpeg_encode", [](py::dict d, uintptr_t s) {
     const auto a = jpeg_encode_args(d);
@@ -811,6 +830,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_locate", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_LOCATE; op.name = name; op.loc = locate_args(d); p.add(op);
+      })
+      .def("add_cutout", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_CUTOUT; op.name = name; op.cut = cutout_args(d); p.add(op);
       })
       .def("add_jpeg_encode", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_JPEG_ENCODE; op.name = name; op.je = jpeg_encode_args(d); p.add(op);

@@ -611,6 +611,50 @@ struct LocateArgs {
 size_t locate_workspace(int B, int S);
 hipError_t locate(const LocateArgs& a, hipStream_t s);
 
+// Garment cutouts (kernels/cutout.hip): behind class_map / rollout_map, three launches answer each image's
+// picture with an alpha channel, in integers throughout (kdl/serving/cutout.py cutout_rule is the
+// definition):
+//   u = the map upsampled as heat_overlay does; ok = u >= gate
+//   N, G, F over the 4096 colour bins of palette: pixels, gated pixels, the sum of u
+//   rounds + 1 times: bin b is garment-coloured iff N > 0 and F * TB >= (255 N - F) * TF with TF = sum F,
+//   TB = 255 S^2 - TF (64-bit products); F <- 255 G where it is, else 0
+//   mask = fg[bin] & ok, then `smooth` 3 x 3 majority rounds (outside the picture counts as unset)
+//   alpha = feather ? (255 c + 4) / 9 with c the set pixels of the 3 x 3 window : 255 mask
+// heat is read from the image's own output row, out[b][2 .. 2 + h*w), and 1 + S*S words are written behind
+// it: the garment's pixel count, then r | g << 8 | b << 16 | alpha << 24 per pixel. Nothing else is
+// written: the words before and after them up to ldo and rows >= B stay as they were. `work` is
+// cutout_workspace(B, S) bytes: per image the three tables (zero on entry and on exit), the 4096 colour
+// bits and the gate's bitmask, S rows of ceil(S / 64) 64-bit words; the bits and the mask are written whole
+// by every launch before they are read, so a replay needs nothing from the host. The result does not depend
+// on the order of the atomics or on the schedule.
+// inp / out / work / xb / xk / yb / yk / h_xb / h_yb null, out, work or a device table not 16-byte aligned,
+// B outside 1..65535, h < 1, w < 1, h*w > kClassMapMaxHW, S < max(h, w), S > kOverlayMaxS (the uint32
+// tables), ldo < 2 + h*w + 1 + S*S, gate outside 1..255, rounds outside 0..kCutoutMaxRounds, smooth outside
+// 0..kCutoutMaxSmooth, feather not 0 or 1, xks / yks outside 1..kOverlayMaxTaps, and bounds tables (checked
+// from the host copies) whose taps leave the map, step back, or need more than kOverlayMaxRows map rows
+// for kOverlayBand output rows are hipErrorInvalidValue, and nothing is launched.
+constexpr int kCutoutMaxRounds = 8;
+constexpr int kCutoutMaxSmooth = 4;
+struct CutoutArgs {
+  const uint8_t* inp;     // [B][S][S][3] the pictures the model saw
+  float* out;             // [B][ldo] words: class, score, h*w heat values (read), count and S*S RGBA words (written)
+  uint8_t* work;          // cutout_workspace(B, S) bytes, the tables of every image zero
+  const int32_t* xb;      // device: bounds [S][2] of the columns, {first map column, taps}
+  const int32_t* xk;      // device: coefficients [S][xks]
+  const int32_t* yb;      // device: the same of the rows
+  const int32_t* yk;      // device: [S][yks]
+  const int32_t* h_xb;    // HOST copies of the bounds (checked here, never followed on the device)
+  const int32_t* h_yb;
+  int B, S, h, w, ldo;
+  int xks, yks;           // taps per column / row of the tables
+  int gate;               // 1..255 of the upsampled map
+  int rounds;             // re-estimates of the colour model behind the first
+  int smooth;             // majority rounds
+  int feather;            // 1 = alpha is the 3 x 3 mean of the mask
+};
+size_t cutout_workspace(int B, int S);
+hipError_t cutout(const CutoutArgs& a, hipStream_t s);
+
 // Baseline JPEG encode (kernels/jpeg_encode.hip): B pictures uint8 [H][W][3], picture b at inp + b * ldi
 // bytes (any alignment), each into the file Pillow's Image.save(.., "JPEG", quality, subsampling,
 // optimize=False) writes, byte for byte (kdl/serving/jpeg_encode.py encode_rule is the definition:

@@ -40,6 +40,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_JPEG_ENCODE: return jpeg_encode(op.je, s);
     case OP_PALETTE: return palette(op.pal, s);
     case OP_LOCATE: return locate(op.loc, s);
+    case OP_CUTOUT: return cutout(op.cut, s);
   }
   return hipErrorInvalidValue;
 }

@@ -19,7 +19,7 @@ enum OpKind { OP_CONV_GEMM = 0, OP_STEM = 1, OP_POOL_ADD = 2, OP_HEAD = 3, OP_RE
               OP_PATCHIFY = 10, OP_EMBED = 11, OP_LN = 12, OP_ATTN = 13,
               OP_DWK = 14, OP_SE = 15, OP_CHSCALE = 16, OP_GEMM_F8 = 17,
               OP_ENTRY_BLOCK = 21, OP_STEM_CONV = 22, OP_SOFTMAX_TOPK = 23, OP_EMBED_ROWS = 24, OP_GALLERY_TOPK = 25, OP_CLASS_MAP = 26,
-              OP_ATTN_ROLLOUT = 27, OP_ROLLOUT_MAP = 28, OP_HEAT_OVERLAY = 29, OP_JPEG_ENCODE = 30, OP_PALETTE = 31, OP_LOCATE = 32 };   // 18: retired (round 6: the SE weight scale, replaced by the project
+              OP_ATTN_ROLLOUT = 27, OP_ROLLOUT_MAP = 28, OP_HEAT_OVERLAY = 29, OP_JPEG_ENCODE = 30, OP_PALETTE = 31, OP_LOCATE = 32, OP_CUTOUT = 33 };   // 18: retired (round 6: the SE weight scale, replaced by the project
                                        // GEMM's A-operand scales); 19: retired (the round-3 chained
                                        // middle-flow launch); 20: retired (round 5: the vendor GEMM node
                                        // left the product, tools/probes/blaslt)
@@ -57,6 +57,7 @@ struct Op {
   JpegEncodeArgs je{};
   PaletteArgs pal{};
   LocateArgs loc{};
+  CutoutArgs cut{};
   void* mem_ptr = nullptr;
   size_t mem_bytes = 0;
 };

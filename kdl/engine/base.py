@@ -197,6 +197,35 @@ def pack_locate(classes, scores, heat, counts, boxes, areas):
     return rows
 
 
+def unpack_cutout(rows, h: int, w: int, S: int) -> tuple:
+    """Packed cutout rows [n, 2 + h*w + 1 + S*S] (a torch tensor or numpy array of 32-bit words) ->
+    (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], counts uint32 [n], rgba uint8 [n, S, S, 4])."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    front = 2 + h * w
+    assert a.ndim == 2 and a.shape[1] == front + 1 + S * S, (a.shape, h, w, S)
+    tail = np.ascontiguousarray(a[:, front:]).view(np.uint32)
+    pics = np.ascontiguousarray(tail[:, 1:]).view(np.uint8).reshape(-1, S, S, 4).copy()   # r | g << 8 | b << 16 | a << 24
+    return unpack_explain(a[:, :front], h, w) + (tail[:, 0].copy(), pics)
+
+
+def pack_cutout(classes, scores, heat, counts, pictures):
+    """The inverse of ``unpack_cutout``: numpy rows of fp32 words; the pixel bytes and the count are copied as
+    bits, never through a float."""
+    import numpy as np
+    pics = np.ascontiguousarray(pictures, dtype=np.uint8)
+    n, S = pics.shape[0], pics.shape[1]
+    assert pics.shape == (n, S, S, 4), pics.shape
+    front = pack_explain(classes, scores, heat)
+    f = front.shape[1]
+    rows = np.zeros((n, f + 1 + S * S), dtype=np.float32)
+    rows[:, :f] = front
+    rows.view(np.uint32)[:, f] = np.asarray(counts, dtype=np.uint32).reshape(n)
+    rows.view(np.uint8)[:, 4 * (f + 1):] = pics.reshape(n, -1)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -259,17 +288,39 @@ class Locate:
     filter: str = "bilinear"
 
 
+@dataclass(frozen=True)
+class Cutout:
+    """Garment-cutout outputs of an ``explain`` / ``rollout`` engine (``EngineBase(cutout=...)``): the input
+    picture with an alpha channel. The heatmap, upsampled with ``filter`` ("bilinear" | "bicubic", Pillow's),
+    seeds a two-histogram colour model over the picture's 4096 colour bins that is re-estimated ``rounds``
+    (0..8) times; a pixel below ``gate`` (1..255 of the upsampled map) is never garment; the mask takes
+    ``smooth`` (0..4) 3 x 3 majority rounds and, with ``feather``, its alpha is the 3 x 3 mean of the mask.
+    kdl/serving/cutout.py defines the rule."""
+    gate: int = 26
+    rounds: int = 2
+    smooth: int = 1
+    feather: bool = True
+    filter: str = "bilinear"
+
+
 class EngineBase:
     model_name = "model"
     # tail step kind -> the method that emits it; every other kind is the family's (_emit)
     TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
                      "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg",
-                     "palette": "_emit_palette", "locate": "_emit_locate"}
+                     "palette": "_emit_palette", "locate": "_emit_locate", "cutout": "_emit_cutout"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
                  explain: bool = False, rollout: bool = False, overlay: Overlay | None = None,
                  overlay_jpeg: OverlayJpeg | None = None, palette: Palette | None = None,
-                 locate: Locate | None = None):
+                 locate: Locate | None = None, cutout: Cutout | None = None):
+        if cutout is not None:       # before anything touches the device
+            if not (explain or rollout):
+                raise ValueError("cutout seeds its colour model with a heatmap: it needs explain=True or rollout=True")
+            if overlay is not None or palette is not None or locate is not None:
+                raise ValueError("cutout, locate, palette and overlay each extend the heatmap rows: set one of them")
+            from ..serving.cutout import check as check_cutout
+            check_cutout(cutout)
         if locate is not None:       # before anything touches the device
             if not (explain or rollout):
                 raise ValueError("locate cuts boxes out of a heatmap: it needs explain=True or rollout=True")
@@ -350,6 +401,10 @@ class EngineBase:
         # and K x (corner, corner, area), written by one more step behind the map's (_enable_locate)
         self.locate: Locate | None = locate
         self._locate_tabs: dict = {}                  # locate only: device tables, their host copies, per-slot workspaces
+        # garment cutouts: None = the rows end with the map; a ``Cutout`` = the rows also carry the garment's
+        # pixel count and the S x S RGBA words, written by one more step behind the map's (_enable_cutout)
+        self.cutout: Cutout | None = cutout
+        self._cutout_tabs: dict = {}                  # cutout only: device tables, their host copies, per-slot workspaces
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -391,6 +446,7 @@ class EngineBase:
             self._enable_overlay_jpeg(*hw)
             self._enable_palette(*hw)
             self._enable_locate(*hw)
+            self._enable_cutout(*hw)
 
     def _enable_heatmap(self) -> tuple:
         """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
@@ -757,6 +813,52 @@ class EngineBase:
             ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], K=self.locate.boxes,
             threshold=self.locate.threshold))
 
+    # ---------------------------------------------------------------- garment cutouts
+    def _enable_cutout(self, h: int, w: int) -> None:
+        """Called by ``_enable_outputs`` behind the heatmap tail. With ``cutout`` the output rows grow to
+        2 + h*w + 1 + S*S words: ``class_map`` / ``rollout_map`` take ``ldo`` and write the front of the wider
+        row unchanged, and one more step "cutout" (kernels/cutout.hip) reads the map from the row and the
+        slot's uint8 input (``src="input"``, through ``_ptr``, with the lifetime ``_enable_overlay``
+        describes) and writes the garment's pixel count and the RGBA words behind the map
+        (``unpack_cutout``). Each slot has its own workspace: the colour tables, which the step leaves zeroed,
+        and the colour bits and the gate's bitmask, which every launch writes before it reads them."""
+        if self.cutout is None:
+            return
+        assert not self.inputs, "cutout is set at construction, before input slots exist"
+        from ..serving import overlay as O
+        lib = _lib.lib()
+        S, cut = self.inp.shape[1], self.cutout
+        if self.inp.dtype != torch.uint8:
+            raise ValueError("cutout reads the uint8 picture the model saw: a float-input engine has none")
+        if self.inp.shape[2] != S or S < max(h, w) or S > lib.OVERLAY_MAX_S:
+            raise ValueError(f"cutout: a {h} x {w} map on a {tuple(self.inp.shape[1:3])} input; the kernel "
+                             f"upsamples onto square inputs up to {lib.OVERLAY_MAX_S}")
+        xb, xk = O.axis_tables(w, S, cut.filter)
+        yb, yk = O.axis_tables(h, S, cut.filter)
+        host = dict(xb=xb, xk=xk, yb=yb, yk=yk)
+        self._cutout_tabs = dict(host=host, dev={k: torch.from_numpy(v).to(self.device) for k, v in host.items()},
+                                 hw=(h, w), work=[])
+        assert self.logits.shape[1] == 2 + h * w, (self.logits.shape, h, w)
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + 1 + S * S), dtype=torch.float32, device=self.device)
+        self.steps.append(Step("cutout", "cutout", src="input"))
+
+    def _cutout_workspace(self, slot: int) -> torch.Tensor:
+        work = self._cutout_tabs["work"]
+        while len(work) <= slot:
+            work.append(torch.zeros(_lib.lib().cutout_workspace(self.max_batch, self.inp.shape[1]), dtype=torch.uint8,
+                                    device=self.device))
+        return work[slot]
+
+    def _emit_cutout(self, prog, step: Step, b: int) -> None:
+        t = self._cutout_tabs
+        host, dev, (h, w), out, cut = t["host"], t["dev"], t["hw"], self._out_rows(), self.cutout
+        prog.add_cutout(step.name, dict(
+            inp=self._ptr(step.src), out=_lib.ptr(out), work=_lib.ptr(self._cutout_workspace(self._slot)),
+            xb=_lib.ptr(dev["xb"]), xk=_lib.ptr(dev["xk"]), yb=_lib.ptr(dev["yb"]), yk=_lib.ptr(dev["yk"]),
+            h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
+            ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], gate=cut.gate, rounds=cut.rounds,
+            smooth=cut.smooth, feather=int(bool(cut.feather))))
+
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or
         ``rollout`` engine."""
@@ -889,7 +991,7 @@ class EngineBase:
         engine: the fp32 feature rows [n, F]; an ``explain`` or ``rollout`` engine: the packed rows
         [n, 2 + h*w], see ``unpack_explain``; with ``overlay`` the wider rows of ``unpack_overlay``, with
         ``overlay_jpeg`` the rows of ``unpack_overlay_jpeg``, with ``palette`` the rows of ``unpack_palette``,
-        with ``locate`` the rows of ``unpack_locate``)."""
+        with ``locate`` the rows of ``unpack_locate``, with ``cutout`` the rows of ``unpack_cutout``)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == tuple(self.inp.shape[1:]), (x.shape, self.inp.shape)
         assert x.dtype == self.inp.dtype, (x.dtype, self.inp.dtype)

@@ -54,9 +54,9 @@ class EfficientNetEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  buckets=None, tune_file: str | Path | None = None, size: int = E.INPUT_SIZE,
                  topk: int = 0, embed: str = "", similar=None, explain: bool = False, overlay=None,
-                 overlay_jpeg=None, palette=None, locate=None):
+                 overlay_jpeg=None, palette=None, locate=None, cutout=None):
         super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay,
-                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate)
+                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate, cutout=cutout)
         self.size = size
         self.sefold = os.environ.get("KDL_SEFOLD", "1") != "0"   # SE scale on the project GEMM's A operand
         self.classes = params["classifier.1.bias"].numel()

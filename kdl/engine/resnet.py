@@ -47,11 +47,11 @@ class ResNetEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
                  dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None, explain: bool = False,
-                 overlay=None, overlay_jpeg=None, palette=None, locate=None):
+                 overlay=None, overlay_jpeg=None, palette=None, locate=None, cutout=None):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
         activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
         super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay,
-                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate)
+                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate, cutout=cutout)
         assert in_kind in ("u8", "f32")
         assert dtype in ("fp16", "bf16"), dtype
         self.in_kind = in_kind

@@ -53,12 +53,12 @@ class ViTEngine(EngineBase):
                  buckets=None, tune_file: str | Path | None = None, fp8: bool = False,
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
                  topk: int = 0, embed: str = "", similar=None, explain: bool = False, rollout: bool = False,
-                 overlay=None, overlay_jpeg=None, palette=None, locate=None):
+                 overlay=None, overlay_jpeg=None, palette=None, locate=None, cutout=None):
         if explain:      # before anything touches the device: the class token has no spatial map
             raise ValueError("ViT-B/16 has no spatial feature map in front of its head: no explain outputs "
                              "(its heatmaps are attention rollout: rollout=True)")
         super().__init__(device, max_batch, buckets, topk, embed, similar, rollout=rollout, overlay=overlay,
-                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate)
+                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate, cutout=cutout)
         self.fp8 = fp8
         if fp8:
             self.model_name = "vit_b16_fp8"

@@ -45,9 +45,9 @@ class XceptionEngine(EngineBase):
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", head: X.Head = X.DEFAULT_HEAD, buckets=None,
                  tune_file: str | Path | None = None, topk: int = 0, embed: str = "", similar=None,
-                 explain: bool = False, overlay=None, overlay_jpeg=None, palette=None, locate=None):
+                 explain: bool = False, overlay=None, overlay_jpeg=None, palette=None, locate=None, cutout=None):
         super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay,
-                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate)
+                         overlay_jpeg=overlay_jpeg, palette=palette, locate=locate, cutout=cutout)
         self.in_kind = in_kind
         self.head = head
         # fused entry blocks (entry_block.hip): block numbers lowered to one launch each.

@@ -22,6 +22,10 @@ of the mode, on a version that has it); colours of weight 0 are left out.
 ...]}``: the predicted class and the garment's boxes, largest first, as fractions of the picture the model saw (the
 locate signature of the mode, on a version that has it); ``count`` is the number of all regions, boxes of area 0 are
 left out.
+``POST /cutout {"url": ...}`` -> ``image/png`` with an alpha channel: the picture the model saw, the backdrop made
+transparent (the cutout signature of the mode, on a version that has it), label, score and the garment's share of
+the picture in the headers ``X-KDL-Label`` / ``X-KDL-Score`` / ``X-KDL-Coverage``; with ``"format": "json"`` ->
+``{"label", "score", "coverage", "png": "<base64>"}``.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -55,6 +59,7 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
+                     process_cutout_response,
                      process_embed_response, process_explain_response, process_locate_response,
                      process_overlay_response,
                      process_palette_response, process_response, process_similar_response, png_bytes)
@@ -211,6 +216,23 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     @app.route("/locate", methods=["POST"])
     def locate():
         return one_image("locate", lambda pb, _: jsonify(process_locate_response(pb)[0]))
+
+    @app.route("/cutout", methods=["POST"])
+    def cutout():
+        """One image through the cutout signature -> the picture with its alpha as a PNG (or, with
+        "format": "json", label, score, coverage and the PNG in base64)."""
+        def shape(pb_result, body):
+            ans = process_cutout_response(pb_result)[0]
+            png = png_bytes(ans.pop("picture"))
+            if body.get("format") == "json":
+                import base64
+                return jsonify(dict(ans, png=base64.b64encode(png).decode()))
+            resp = app.response_class(png, mimetype="image/png")
+            resp.headers["X-KDL-Label"] = ans["label"]
+            resp.headers["X-KDL-Score"] = repr(ans["score"])
+            resp.headers["X-KDL-Coverage"] = repr(ans["coverage"])
+            return resp
+        return one_image("cutout", shape, formats=("png", "json"))
 
     @app.route("/overlay", methods=["POST"])
     def overlay():

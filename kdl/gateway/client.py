@@ -134,6 +134,17 @@ def process_locate_response(pb_result) -> list[dict]:
                        for j in range(K) if area[i, j] > 0]} for i in range(n)]
 
 
+def process_cutout_response(pb_result) -> list[dict]:
+    """A cutout signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT [n, 1], ``cutout``
+    DT_UINT8 [n, S, S, 4] as ``tensor_content``, ``coverage`` DT_FLOAT [n, 1]) -> per image ``{"label", "score",
+    "coverage", "picture"}``, the picture a uint8 array [S, S, 4]: the picture the model saw with its alpha."""
+    o = pb_result.outputs
+    t = o["cutout"]
+    pics = np.frombuffer(t.tensor_content, dtype=np.uint8).reshape([d.size for d in t.tensor_shape.dim])
+    return [{"label": o["classes"].string_val[i].decode(), "score": float(o["scores"].float_val[i]),
+             "coverage": float(o["coverage"].float_val[i]), "picture": pics[i]} for i in range(len(pics))]
+
+
 def process_overlay_response(pb_result) -> list[dict]:
     """An overlay signature's PredictResponse (explain's three outputs and ``overlay`` DT_UINT8
     [n, S, S, 3] as ``tensor_content``) -> per image ``{"label", "score", "heatmap", "picture"}``, the
@@ -148,16 +159,17 @@ def process_overlay_response(pb_result) -> list[dict]:
 
 
 def png_bytes(picture) -> bytes:
-    """uint8 [H, W, 3] -> an 8-bit RGB PNG file, written with zlib and struct alone (the gateway's
-    ``bytes`` mode needs no image library)."""
+    """uint8 [H, W, 3] -> an 8-bit RGB PNG file, [H, W, 4] -> an 8-bit RGBA one, written with zlib and struct
+    alone (the gateway's ``bytes`` mode needs no image library)."""
     import struct
     import zlib
     a = np.ascontiguousarray(picture, dtype=np.uint8)
-    H, W, _ = a.shape
+    H, W, C = a.shape
+    assert C in (3, 4), a.shape
 
     def chunk(tag: bytes, data: bytes) -> bytes:
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
-    rows = np.concatenate([np.zeros((H, 1), dtype=np.uint8), a.reshape(H, W * 3)], axis=1)   # filter type 0 per row
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+    rows = np.concatenate([np.zeros((H, 1), dtype=np.uint8), a.reshape(H, W * C)], axis=1)   # filter type 0 per row
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2 if C == 3 else 6, 0, 0, 0))
             + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))

@@ -128,6 +128,8 @@ class ModelSource:
     palette: object = None
     # garment boxes (serving/locate.py): the version's engine.base.Locate (None = no locate signatures)
     locate: object = None
+    # garment cutouts (serving/cutout.py): the version's engine.base.Cutout (None = no cutout signatures)
+    cutout: object = None
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -151,7 +153,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      similar_top_k: int | None = None, gallery: bool = True,
                      overlay_colormap: str | None = None, overlay_alpha: float | None = None,
                      overlay_jpeg_quality: int | None = None, palette_colors: int | None = None,
-                     locate_boxes: int | None = None) -> ModelSource:
+                     locate_boxes: int | None = None, cutout_gate: int | None = None) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
@@ -165,7 +167,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     (serving/jpeg_encode.py); ``palette_colors`` (--palette_colors) turns the palette signatures on and
     overrides the colour count of the version's "palette" block (serving/palette.py); ``locate_boxes``
     (--locate_boxes) turns the locate signatures on and overrides the box count of the version's "locate"
-    block (serving/locate.py)."""
+    block (serving/locate.py); ``cutout_gate`` (--cutout_gate) turns the cutout signatures on and overrides
+    the gate of the version's "cutout" block (serving/cutout.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -177,7 +180,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
-    from . import classify, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
+    from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
@@ -188,6 +191,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     jpeg_encode.add_signatures(src, path, overlay_jpeg_quality)
     palette.add_signatures(src, path, palette_colors)
     locate.add_signatures(src, path, locate_boxes)
+    cutout.add_signatures(src, path, cutout_gate)
     return src
 
 

@@ -111,6 +111,9 @@ class ServerConfig:
     # K of the locate signatures (serving/locate.py), 1..8; set, it also turns them on for a version
     # without a "locate" block; None = the version's own block decides
     locate_boxes: int | None = None
+    # gate of the cutout signatures (serving/cutout.py), 1..255; set, it also turns them on for a version
+    # without a "cutout" block; None = the version's own block decides
+    cutout_gate: int | None = None
     f32_exact_u8: bool = True    # f32 requests that are exactly x/127.5-1 of 8-bit pixels ride the uint8 path
     # --scatter rccl: ONE front-end (rank 0) + one process per GPU, batches scattered / logits
     # gathered over RCCL (serving/dp.py); host = every process ingests its own requests
@@ -236,6 +239,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="boxes per image of the locate / locate_image / locate_bytes signatures, 1..8; "
                          "turns them on and overrides the model version's \"locate\": {\"boxes\": ...} (env "
                          "KDL_LOCATE_BOXES, default: the version's block, without one no such signatures)")
+    ap.add_argument("--cutout_gate", type=int, default=None,
+                    help="gate (1..255 of the upsampled heatmap) of the cutout / cutout_image / cutout_bytes "
+                         "signatures; turns them on and overrides the model version's \"cutout\": {\"gate\": ...} (env "
+                         "KDL_CUTOUT_GATE, default: the version's block, without one no such signatures)")
     ap.add_argument("--similar_top_k", type=int, default=None,
                     help="gallery items and scores per image of the similar / similar_image / similar_bytes "
                          "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
@@ -313,6 +320,8 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                                         else int(env["KDL_PALETTE_COLORS"]) if env.get("KDL_PALETTE_COLORS") else None),
                         locate_boxes=(a.locate_boxes if a.locate_boxes is not None
                                       else int(env["KDL_LOCATE_BOXES"]) if env.get("KDL_LOCATE_BOXES") else None),
+                        cutout_gate=(a.cutout_gate if a.cutout_gate is not None
+                                     else int(env["KDL_CUTOUT_GATE"]) if env.get("KDL_CUTOUT_GATE") else None),
                         f32_exact_u8=(a.f32_exact_u8 or env.get("KDL_F32_EXACT_U8", "true")).lower() != "false",
                         scatter=a.scatter, dp_world=a.dp_world, dp_rank=a.dp_rank, dp_signature=a.dp_signature,
                         log_format=a.log_format or env.get("KDL_LOG_FORMAT", "text"),

@@ -41,7 +41,8 @@ def latest_version_source(cfg: ServerConfig):
                             classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize,
                             similar_top_k=cfg.similar_top_k, overlay_colormap=cfg.overlay_colormap,
                             overlay_alpha=cfg.overlay_alpha, overlay_jpeg_quality=cfg.overlay_jpeg_quality,
-                            palette_colors=cfg.palette_colors, locate_boxes=cfg.locate_boxes)
+                            palette_colors=cfg.palette_colors, locate_boxes=cfg.locate_boxes,
+                            cutout_gate=cfg.cutout_gate)
 
 
 class ModelManager:
@@ -84,7 +85,7 @@ class ModelManager:
                                    overlay_colormap=self.cfg.overlay_colormap, overlay_alpha=self.cfg.overlay_alpha,
                                    overlay_jpeg_quality=self.cfg.overlay_jpeg_quality,
                                    palette_colors=self.cfg.palette_colors,
-                                   locate_boxes=self.cfg.locate_boxes)
+                                   locate_boxes=self.cfg.locate_boxes, cutout_gate=self.cfg.cutout_gate)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

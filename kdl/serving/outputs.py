@@ -2,9 +2,10 @@
 
 A signature answers with one of ten kinds of row: the fp32 ``logits``, or what the ``classify``,
 ``embed``, ``similar``, ``explain``, ``attention``, ``overlay``, ``overlay_jpeg``, ``palette`` and ``locate``
-trios pack into the same fp32 words.
-Everything that differs between the kinds is in ``KINDS``; runners, executors, answer builders and the
-loader ask the table and name no kind. Per kind:
+trios pack into the same fp32 words. An eleventh, what the ``cutout`` trio packs, is ``CUTOUT`` beside the
+table: the picture itself with an alpha channel, a word per pixel.
+Everything that differs between the kinds is in ``KINDS`` and ``CUTOUT``; runners, executors, answer builders
+and the loader ask ``kind_of`` and name no kind. Per kind:
 
   trio       its three signature names: uint8 pixels, any-size image, encoded file
   counter    what an answered request bumps (``signature=`` label)
@@ -30,7 +31,7 @@ import numpy as np
 import torch
 
 from ..engine.base import overlay_jpeg_cap, overlay_words
-from . import classify, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
+from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
 from . import protos as P
 from .jpeg import BYTES_SIGNATURE
 from .metrics import METRICS
@@ -61,6 +62,10 @@ def _palette_kw(sig, src, dev) -> dict:
 
 def _locate_kw(sig, src, dev) -> dict:
     return dict(_map_kw(sig, src, dev), locate=src.locate)
+
+
+def _cutout_kw(sig, src, dev) -> dict:
+    return dict(_map_kw(sig, src, dev), cutout=src.cutout)
 
 
 # ---------------------------------------------------------------------- CPU executor rows
@@ -94,6 +99,9 @@ def _map_rows(sig, src, x):
     if _is_locate(sig):
         ans = [locate.locate_rule(m, src.input_size, src.locate) for m in heat]
         return locate.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(3)))
+    if _is_cutout(sig):
+        ans = [cutout.cutout_rule(img, m, src.cutout) for img, m in zip(x.numpy(), heat)]
+        return cutout.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(2)))
     if not sig.overlay:
         return explain.pack_rows(k, score, heat)
     pics = [overlay.overlay_rule(img, m, src.overlay) for img, m in zip(x.numpy(), heat)]
@@ -132,6 +140,19 @@ def _locate_k(sig) -> int:
 
 def _locate_words(sig, src) -> int:
     return 2 + sig.explain[0] * sig.explain[1] + 1 + 3 * _locate_k(sig)
+
+
+def _is_cutout(sig) -> bool:
+    """An explain-kind signature with a ``coverage`` output answers the picture with an alpha channel."""
+    return bool(sig.explain and any(o[0] == "coverage" for o in sig.outputs))
+
+
+def _cutout_s(sig) -> int:
+    return next(o[2][1] for o in sig.outputs if o[0] == "cutout")
+
+
+def _cutout_words(sig, src) -> int:
+    return 2 + sig.explain[0] * sig.explain[1] + 1 + _cutout_s(sig) ** 2
 
 
 def _is_jpeg(sig) -> bool:
@@ -195,6 +216,13 @@ def _locate_columns(src, sig, rows) -> list:
         ("num_boxes", P.DT_INT32, counts.astype(np.int32).reshape(-1, 1))]
 
 
+def _cutout_columns(src, sig, rows) -> list:
+    S = _cutout_s(sig)
+    classes, scores, heat, counts, pics = cutout.unpack_rows(rows, *sig.explain, S)
+    return _front_columns(src, classes, scores, heat)[:2] + [
+        ("cutout", P.DT_UINT8, pics), ("coverage", P.DT_FLOAT, cutout.coverage_of(counts, S).reshape(-1, 1))]
+
+
 @dataclass(frozen=True)
 class Kind:
     name: str
@@ -236,12 +264,16 @@ KINDS = {k.name: k for k in (
     Kind("locate", locate.LOCATE_SIGNATURES, "kdl_locate_total",
          **dict(_MAP, engine=_locate_kw, gpu_words=_locate_words, columns=_locate_columns)),
 )}
+CUTOUT = Kind("cutout", cutout.CUTOUT_SIGNATURES, "kdl_cutout_total",
+              **dict(_MAP, engine=_cutout_kw, gpu_words=_cutout_words, columns=_cutout_columns))
 # the second and third name of every trio -> (0 any-size image / 1 encoded file, the trio's first name)
-WRAPPED = {name: (i, k.trio[0]) for k in KINDS.values() for i, name in enumerate(k.trio[1:])}
+WRAPPED = {name: (i, k.trio[0]) for k in (*KINDS.values(), CUTOUT) for i, name in enumerate(k.trio[1:])}
 
 
 def kind_of(sig) -> Kind:
     """The kind of a signature's rows, from the fields SignatureInfo has."""
+    if _is_cutout(sig):
+        return CUTOUT
     name = ("locate" if _is_locate(sig) else "palette" if _is_palette(sig) else "overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
             "explain" if sig.explain else "similar" if sig.similar else "classify" if sig.top_k else
             "embed" if sig.embed else "logits")
