@@ -280,6 +280,16 @@ CutoutArgs cutout_args(const py::dict& d) {
   a.smooth = I(d, "smooth", -1); a.feather = I(d, "feather", -1);
   return a;
 }
+PngEncodeArgs png_encode_args(const py::dict& d) {
+  PngEncodeArgs a{};
+  a.inp = P<const uint8_t>(d, "inp"); a.front = P<const uint32_t>(d, "front"); a.out = P<uint32_t>(d, "out");
+  a.work = P<void>(d, "work");
+  a.ldi = (d.contains("ldi") && !d["ldi"].is_none()) ? d["ldi"].cast<int64_t>() : 0;
+  a.row_stride = (d.contains("row_stride") && !d["row_stride"].is_none()) ? d["row_stride"].cast<int64_t>() : 0;
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.C = I(d, "C"); a.cap = I(d, "cap"); a.ldo = I(d, "ldo");
+  a.nfront = I(d, "nfront"); a.ldf = I(d, "ldf");
+  return a;
+}
 JpegEncodeArgs jpeg_encode_args(const py::dict& d) {
   JpegEncodeArgs a{};
   a.inp = P<const uint8_t>(d, "inp"); a.hdr = P<const uint8_t>(d, "hdr"); a.h_hdr = P<const uint8_t>(d, "h_hdr");
@@ -460,6 +470,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("cutout_workspace", [](int B, int S) { return cutout_workspace(B, S); });
   m.attr("CUTOUT_MAX_ROUNDS") = int(kCutoutMaxRounds);
   m.attr("CUTOUT_MAX_SMOOTH") = int(kCutoutMaxSmooth);
+  // PNG encode (kernels/png_encode.hip): d = the PngEncodeArgs fields; work is zero at its first use
+  m.def("png_encode", [](py::dict d, uintptr_t s) {
+    const auto a = png_encode_args(d);
+    py::gil_scoped_release nogil;
+    chk(png_encode(a, S(s)), "png_encode");
+  });
+  m.def("png_encode_workspace", [](int B, int H, int W, int C, int cap) { return png_encode_workspace(B, H, W, C, cap); });
+  m.attr("PNG_ENC_MAX_SIDE") = int(kPngEncMaxSide);
+  m.attr("PNG_ENC_MAX_CAP") = int(kPngEncMaxCap);
+  m.attr("PNG_ENC_BAND") = int(kPngBand);
   // baseline JPEG encode (kernels/jpeg_encode.hip): d = the JpegEncodeArgs fields; h_hdr is a HOST address
   m.def("jpeg_encode", [](py::dict d, uintptr_t s) {
     const auto a = jpeg_encode_args(d);
@@ -830,6 +850,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_locate", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_LOCATE; op.name = name; op.loc = locate_args(d); p.add(op);
+      })
+      .def("add_png_encode", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_PNG_ENCODE; op.name = name; op.pe = png_encode_args(d); p.add(op);
       })
       .def("add_cutout", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_CUTOUT; op.name = name; op.cut = cutout_args(d); p.add(op);

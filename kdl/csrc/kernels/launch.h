@@ -655,6 +655,38 @@ struct CutoutArgs {
 size_t cutout_workspace(int B, int S);
 hipError_t cutout(const CutoutArgs& a, hipStream_t s);
 
+// PNG encode (kernels/png_encode.hip): B pictures uint8 [H][W][C], C = 3 (RGB) or 4 (RGBA), picture b at
+// inp + b * ldi bytes, its rows row_stride bytes apart (any alignment), each into the file of
+// kdl/serving/png_encode.py png_rule, byte for byte: min-sum filters, a greedy parse per row over the
+// distances 1 and C, one deflate block with a 15-bit limited code or the fixed code, zlib and PNG framing.
+// Output row b, ldo words: nfront words copied from front[b * ldf ..] (nfront = 0: none), one word with the
+// file's length in bytes, then the file and zero bytes up to ceil(cap / 4) words. A file longer than cap
+// gives length 0 and an all-zero file area; other rows are unaffected. Words past nfront + 1 + ceil(cap / 4)
+// of a row and rows >= B are not written. Five launches (filter and tokens per band of kPngBand rows, the
+// code per picture, bit lengths per row, the bits ORed into the picture's zeroed stream, the file); every
+// sum is an integer and OR commutes: launches are byte-identical. `work` is png_encode_workspace(B, H, W, C,
+// cap) bytes (a 16-bit token for every filtered byte, B * H * (W*C + 8) * 2, plus the stream, B * (cap + 8):
+// 3.6 MB a picture at 600 x 600 x 4), ZERO when first used; every launch leaves what it accumulates into zero again.
+// inp / out / work null (front: only with nfront > 0), out / front / work not aligned to 4 / 4 / 16 bytes,
+// B outside 1..65535, H or W outside 1..kPngEncMaxSide, C not 3 or 4, cap outside 1..kPngEncMaxCap,
+// row_stride < W*C, ldi < H * row_stride, nfront < 0, ldf < nfront or ldo < nfront + 1 + ceil(cap / 4) are
+// hipErrorInvalidValue, and nothing is launched.
+constexpr int kPngEncMaxSide = 1024;
+constexpr int kPngEncMaxCap = 1 << 24;
+constexpr int kPngBand = 8;
+struct PngEncodeArgs {
+  const uint8_t* inp;     // pictures [H][W][C]; picture b at inp + b * ldi, row y at + y * row_stride
+  const uint32_t* front;  // [B][ldf] words in front of each row's length word, or null
+  uint32_t* out;          // [B][ldo] words
+  void* work;             // png_encode_workspace(B, H, W, C, cap) bytes, 16-byte aligned, zero at first use
+  int64_t ldi;            // bytes between pictures
+  int64_t row_stride;     // bytes between rows of a picture
+  int B, H, W, C, cap, ldo, nfront, ldf;
+  uint8_t head[36];       // filled by png_encode: the signature and IHDR, 33 bytes
+};
+size_t png_encode_workspace(int B, int H, int W, int C, int cap);
+hipError_t png_encode(const PngEncodeArgs& a, hipStream_t s);
+
 // Baseline JPEG encode (kernels/jpeg_encode.hip): B pictures uint8 [H][W][3], picture b at inp + b * ldi
 // bytes (any alignment), each into the file Pillow's Image.save(.., "JPEG", quality, subsampling,
 // optimize=False) writes, byte for byte (kdl/serving/jpeg_encode.py encode_rule is the definition:

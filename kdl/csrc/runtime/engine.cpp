@@ -41,6 +41,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_PALETTE: return palette(op.pal, s);
     case OP_LOCATE: return locate(op.loc, s);
     case OP_CUTOUT: return cutout(op.cut, s);
+    case OP_PNG_ENCODE: return png_encode(op.pe, s);
   }
   return hipErrorInvalidValue;
 }

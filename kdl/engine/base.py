@@ -226,6 +226,45 @@ def pack_cutout(classes, scores, heat, counts, pictures):
     return rows
 
 
+def cutout_png_cap(S: int, max_bytes: int | None = None) -> int:
+    """Bytes a cutout_png row keeps for the file of an S x S RGBA picture: ``max_bytes``, or ceil(S*S*4/2)."""
+    return int(max_bytes) if max_bytes is not None else (S * S * 4 + 1) // 2
+
+
+def unpack_cutout_png(rows, h: int, w: int, max_bytes: int) -> tuple:
+    """Packed cutout_png rows [n, 2 + h*w + 1 + 1 + ceil(max_bytes/4)] (a torch tensor or numpy array of 32-bit
+    words) -> (classes int32 [n], scores fp32 [n], heat fp32 [n, h, w], counts uint32 [n], files: a list of n
+    bytes objects, a row's length word of them; b"" for a file that did not fit)."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    front = 2 + h * w
+    assert a.ndim == 2 and a.shape[1] == front + 2 + (max_bytes + 3) // 4, (a.shape, h, w, max_bytes)
+    counts = np.ascontiguousarray(a[:, front]).view(np.uint32).copy()
+    lens = np.ascontiguousarray(a[:, front + 1]).view(np.int32)
+    body = np.ascontiguousarray(a[:, front + 2:]).view(np.uint8).reshape(a.shape[0], -1)
+    assert ((0 <= lens) & (lens <= max_bytes)).all(), lens
+    return unpack_explain(a[:, :front], h, w) + (counts, [body[i, :n].tobytes() for i, n in enumerate(lens)])
+
+
+def pack_cutout_png(classes, scores, heat, counts, files, max_bytes: int):
+    """The inverse of ``unpack_cutout_png``: numpy rows of fp32 words, the bytes behind a file 0. A file longer
+    than ``max_bytes`` is an overflow row: length 0 and no bytes."""
+    import numpy as np
+    front = pack_explain(classes, scores, heat)
+    n, f = front.shape
+    rows = np.zeros((n, f + 2 + (max_bytes + 3) // 4), dtype=np.float32)
+    rows[:, :f] = front
+    rows.view(np.uint32)[:, f] = np.asarray(counts, dtype=np.uint32).reshape(n)
+    by = rows.view(np.uint8)
+    for i, data in enumerate(files):
+        if len(data) > max_bytes:
+            continue
+        rows.view(np.int32)[i, f + 1] = len(data)
+        by[i, 4 * (f + 2):4 * (f + 2) + len(data)] = np.frombuffer(bytes(data), np.uint8)
+    return rows
+
+
 EMBED_MODES = ("", "raw", "l2")
 SIMILAR_METRICS = ("cosine", "dot")
 
@@ -303,17 +342,30 @@ class Cutout:
     filter: str = "bilinear"
 
 
+@dataclass(frozen=True)
+class CutoutPng:
+    """The cutout as a PNG file (``EngineBase(cutout=..., cutout_png=...)``): at most ``max_bytes`` per file
+    (None = ceil(S*S*4/2)). kdl/serving/png_encode.py defines the rule."""
+    max_bytes: int | None = None
+
+
 class EngineBase:
     model_name = "model"
     # tail step kind -> the method that emits it; every other kind is the family's (_emit)
     TAIL_EMITTERS = {"topk": "_emit_topk", "similar": "_emit_similar", "top1": "_emit_top1",
                      "explain": "_emit_explain", "overlay": "_emit_overlay", "overlay_jpeg": "_emit_overlay_jpeg",
-                     "palette": "_emit_palette", "locate": "_emit_locate", "cutout": "_emit_cutout"}
+                     "palette": "_emit_palette", "locate": "_emit_locate", "cutout": "_emit_cutout",
+                     "cutout_png": "_emit_cutout_png"}
 
     def __init__(self, device, max_batch: int, buckets=None, topk: int = 0, embed: str = "", similar=None,
                  explain: bool = False, rollout: bool = False, overlay: Overlay | None = None,
                  overlay_jpeg: OverlayJpeg | None = None, palette: Palette | None = None,
-                 locate: Locate | None = None, cutout: Cutout | None = None):
+                 locate: Locate | None = None, cutout: Cutout | None = None, cutout_png: CutoutPng | None = None):
+        if cutout_png is not None:   # before anything touches the device
+            if cutout is None:
+                raise ValueError("cutout_png encodes the cutout: it needs cutout=Cutout(...)")
+            from ..serving.png_encode import check as check_png
+            check_png(cutout_png)
         if cutout is not None:       # before anything touches the device
             if not (explain or rollout):
                 raise ValueError("cutout seeds its colour model with a heatmap: it needs explain=True or rollout=True")
@@ -405,6 +457,11 @@ class EngineBase:
         # pixel count and the S x S RGBA words, written by one more step behind the map's (_enable_cutout)
         self.cutout: Cutout | None = cutout
         self._cutout_tabs: dict = {}                  # cutout only: device tables, their host copies, per-slot workspaces
+        # cutouts as PNG files: None = the rows carry the RGBA words; a ``CutoutPng`` = the steps above write
+        # those raw rows into a device-only buffer, and one more step writes narrow output rows: the raw row's
+        # front words and count, a length word and the encoded file (_enable_cutout_png)
+        self.cutout_png: CutoutPng | None = cutout_png
+        self._png: dict = {}                          # cutout_png only: cap, per-slot raw rows and workspaces
 
     # ---------------------------------------------------------------- input slots
     def input_ptr(self) -> int:
@@ -420,6 +477,8 @@ class EngineBase:
         ``overlay_jpeg`` the slot's raw overlay rows, which never leave the device."""
         if self._jpeg:
             return self._jpeg_slot(self._slot)[0]
+        if self._png:
+            return self._png_slot(self._slot)[0]
         return self.outputs[self._slot] if self.outputs else self.logits
 
     def output_ptr(self) -> int:
@@ -447,6 +506,7 @@ class EngineBase:
             self._enable_palette(*hw)
             self._enable_locate(*hw)
             self._enable_cutout(*hw)
+            self._enable_cutout_png(*hw)
 
     def _enable_heatmap(self) -> tuple:
         """The family's heatmap tail: (h, w) of the map it appended, () without one. Grad-CAM here;
@@ -858,6 +918,53 @@ class EngineBase:
             h_xb=host["xb"].ctypes.data, h_yb=host["yb"].ctypes.data, B=b, S=self.inp.shape[1], h=h, w=w,
             ldo=out.shape[1], xks=host["xk"].shape[1], yks=host["yk"].shape[1], gate=cut.gate, rounds=cut.rounds,
             smooth=cut.smooth, feather=int(bool(cut.feather))))
+
+    # ---------------------------------------------------------------- cutouts as PNG files
+    def _enable_cutout_png(self, h: int, w: int) -> None:
+        """Called by ``_enable_outputs`` behind ``_enable_cutout``. With ``cutout_png`` the wide rows that step
+        made stay on the device (one buffer per slot; ``class_map`` / ``rollout_map`` / ``cutout`` write them as
+        before, through ``_out_rows``), and one more step "cutout_png" (kernels/png_encode.hip) writes the
+        output rows: the 2 + h*w + 1 front words copied from the raw row, a length word, then the file in
+        ceil(max_bytes/4) words, the bytes behind it 0 (``unpack_cutout_png``). The picture is read where it
+        sits in the raw row. Each slot has its own workspace, zero when made; the step leaves what it adds into
+        zero again."""
+        if self.cutout_png is None:
+            return
+        assert not self.inputs, "cutout_png is set at construction, before input slots exist"
+        lib = _lib.lib()
+        S = self.inp.shape[1]
+        cap = cutout_png_cap(S, self.cutout_png.max_bytes)
+        if S > lib.PNG_ENC_MAX_SIDE or not 1 <= cap <= lib.PNG_ENC_MAX_CAP:
+            raise ValueError(f"cutout_png: a {S} x {S} picture in at most {cap} bytes; the kernel takes sides up "
+                             f"to {lib.PNG_ENC_MAX_SIDE} and 1..{lib.PNG_ENC_MAX_CAP} bytes")
+        self._png = dict(cap=cap, hw=(h, w), work=lib.png_encode_workspace(self.max_batch, S, S, 4, cap),
+                         slots=[(self.logits, None)])
+        self.logits = torch.zeros((self.max_batch, 2 + h * w + 2 + (cap + 3) // 4), dtype=torch.float32,
+                                  device=self.device)
+        self.steps.append(Step("cutout_png", "cutout_png"))
+
+    def _png_slot(self, slot: int) -> tuple:
+        """(raw cutout rows, encoder workspace) of a slot, both device-only."""
+        sl = self._png["slots"]
+        while len(sl) <= slot:
+            sl.append((torch.zeros_like(sl[0][0]), None))
+        if sl[slot][1] is None:
+            sl[slot] = (sl[slot][0], torch.zeros(self._png["work"], dtype=torch.uint8, device=self.device))
+        return sl[slot]
+
+    def cutout_raw(self, slot: int = 0) -> torch.Tensor:
+        """The raw cutout rows (``unpack_cutout``) of the last forward of a ``cutout_png`` engine in ``slot``."""
+        return self._png_slot(slot)[0]
+
+    def _emit_cutout_png(self, prog, step: Step, b: int) -> None:
+        (h, w), S = self._png["hw"], self.inp.shape[1]
+        raw, work = self._png_slot(self._slot)
+        out = self.slot_logits(self._slot)
+        front = 2 + h * w + 1
+        prog.add_png_encode(step.name, dict(
+            inp=_lib.ptr(raw) + 4 * front, ldi=4 * raw.shape[1], row_stride=4 * S, front=_lib.ptr(raw),
+            ldf=raw.shape[1], nfront=front, out=_lib.ptr(out), ldo=out.shape[1], work=_lib.ptr(work), B=b, H=S, W=S,
+            C=4, cap=self._png["cap"]))
 
     def top1_slot(self, slot: int = 0) -> torch.Tensor:
         """[max_batch, 2] class (int32 bits) and score of the last forward of an ``explain`` or

@@ -25,7 +25,9 @@ left out.
 ``POST /cutout {"url": ...}`` -> ``image/png`` with an alpha channel: the picture the model saw, the backdrop made
 transparent (the cutout signature of the mode, on a version that has it), label, score and the garment's share of
 the picture in the headers ``X-KDL-Label`` / ``X-KDL-Score`` / ``X-KDL-Coverage``; with ``"format": "json"`` ->
-``{"label", "score", "coverage", "png": "<base64>"}``.
+``{"label", "score", "coverage", "png": "<base64>"}``; with ``"format": "png_server"`` -> ``image/png``: the file
+the model server encoded (the cutout_png signature of the mode, on a version that has it), handed on byte for
+byte, the same three headers.
 
 Same contract as the reference Flask gateway (`model_server.py:59-70`, SURVEY.md
 §2.9.1): Flask app named 'clothing-model', backend address from
@@ -59,7 +61,7 @@ from flask import Flask, jsonify, request
 from ..labels import LABELS as DEFAULT_LABELS
 from . import preprocess as pp
 from .client import (PredictionStub, make_request, process_batch_response, process_classify_response,
-                     process_cutout_response,
+                     process_cutout_png_response, process_cutout_response,
                      process_embed_response, process_explain_response, process_locate_response,
                      process_overlay_response,
                      process_palette_response, process_response, process_similar_response, png_bytes)
@@ -220,10 +222,17 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
     @app.route("/cutout", methods=["POST"])
     def cutout():
         """One image through the cutout signature -> the picture with its alpha as a PNG (or, with
-        "format": "json", label, score, coverage and the PNG in base64)."""
+        "format": "json", label, score, coverage and the PNG in base64); with "format": "png_server" through the
+        cutout_png signature -> the model server's file as it is."""
         def shape(pb_result, body):
-            ans = process_cutout_response(pb_result)[0]
-            png = png_bytes(ans.pop("picture"))
+            if body.get("format") == "png_server":
+                ans = process_cutout_png_response(pb_result)[0]
+                png = ans.pop("png")
+                if not png:
+                    return fail(502, "the model server's file did not fit the version's cutout_png max_bytes")
+            else:
+                ans = process_cutout_response(pb_result)[0]
+                png = png_bytes(ans.pop("picture"))
             if body.get("format") == "json":
                 import base64
                 return jsonify(dict(ans, png=base64.b64encode(png).decode()))
@@ -232,7 +241,8 @@ def create_app(cfg: GatewayConfig | None = None, channel: grpc.Channel | None = 
             resp.headers["X-KDL-Score"] = repr(ans["score"])
             resp.headers["X-KDL-Coverage"] = repr(ans["coverage"])
             return resp
-        return one_image("cutout", shape, formats=("png", "json"))
+        return one_image(lambda body: "cutout_png" if body.get("format") == "png_server" else "cutout", shape,
+                         formats=("png", "json", "png_server"))
 
     @app.route("/overlay", methods=["POST"])
     def overlay():

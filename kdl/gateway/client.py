@@ -134,6 +134,16 @@ def process_locate_response(pb_result) -> list[dict]:
                        for j in range(K) if area[i, j] > 0]} for i in range(n)]
 
 
+def process_cutout_png_response(pb_result) -> list[dict]:
+    """A cutout_png signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT [n, 1],
+    ``coverage`` DT_FLOAT [n, 1], ``png_bytes`` DT_STRING [n]) -> per image ``{"label", "score", "coverage", "png"}``,
+    the PNG file the model server encoded, untouched; b"" where it did not fit the version's ``max_bytes``."""
+    o = pb_result.outputs
+    return [{"label": o["classes"].string_val[i].decode(), "score": float(o["scores"].float_val[i]),
+             "coverage": float(o["coverage"].float_val[i]), "png": bytes(f)}
+            for i, f in enumerate(o["png_bytes"].string_val)]
+
+
 def process_cutout_response(pb_result) -> list[dict]:
     """A cutout signature's PredictResponse (``classes`` DT_STRING [n, 1], ``scores`` DT_FLOAT [n, 1], ``cutout``
     DT_UINT8 [n, S, S, 4] as ``tensor_content``, ``coverage`` DT_FLOAT [n, 1]) -> per image ``{"label", "score",

@@ -130,6 +130,9 @@ class ModelSource:
     locate: object = None
     # garment cutouts (serving/cutout.py): the version's engine.base.Cutout (None = no cutout signatures)
     cutout: object = None
+    # cutouts as PNG files (serving/png_encode.py): the version's engine.base.CutoutPng (None = no cutout_png
+    # signatures)
+    cutout_png: object = None
 
 
 def _family_source(family: str, params: dict | None, seed: int, origin: str) -> ModelSource:
@@ -153,7 +156,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      similar_top_k: int | None = None, gallery: bool = True,
                      overlay_colormap: str | None = None, overlay_alpha: float | None = None,
                      overlay_jpeg_quality: int | None = None, palette_colors: int | None = None,
-                     locate_boxes: int | None = None, cutout_gate: int | None = None) -> ModelSource:
+                     locate_boxes: int | None = None, cutout_gate: int | None = None,
+                     cutout_png: bool = False) -> ModelSource:
     """SavedModel (saved_model.pb + variables/), packed kdl safetensors, or synthetic. The
     version's resize spec is ``preprocess`` (the server's --preprocess) when given, else the
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
@@ -168,7 +172,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     overrides the colour count of the version's "palette" block (serving/palette.py); ``locate_boxes``
     (--locate_boxes) turns the locate signatures on and overrides the box count of the version's "locate"
     block (serving/locate.py); ``cutout_gate`` (--cutout_gate) turns the cutout signatures on and overrides
-    the gate of the version's "cutout" block (serving/cutout.py)."""
+    the gate of the version's "cutout" block (serving/cutout.py); ``cutout_png`` (--cutout_png) turns the
+    cutout_png signatures on for a version without a "cutout_png" block (serving/png_encode.py)."""
     path = Path(path)
     src = _load_version_dir(path, synthetic)
     declared = ""
@@ -180,7 +185,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
         src.preprocess = ResizeSpec.parse(preprocess or declared, src.input_size)
     except ValueError as e:
         raise ValueError(f"{path}: {e}") from e
-    from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
+    from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, png_encode, rollout, similar
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
@@ -192,6 +197,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     palette.add_signatures(src, path, palette_colors)
     locate.add_signatures(src, path, locate_boxes)
     cutout.add_signatures(src, path, cutout_gate)
+    png_encode.add_signatures(src, path, cutout_png)
     return src
 
 

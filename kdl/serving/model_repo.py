@@ -42,7 +42,7 @@ def latest_version_source(cfg: ServerConfig):
                             similar_top_k=cfg.similar_top_k, overlay_colormap=cfg.overlay_colormap,
                             overlay_alpha=cfg.overlay_alpha, overlay_jpeg_quality=cfg.overlay_jpeg_quality,
                             palette_colors=cfg.palette_colors, locate_boxes=cfg.locate_boxes,
-                            cutout_gate=cfg.cutout_gate)
+                            cutout_gate=cfg.cutout_gate, cutout_png=cfg.cutout_png)
 
 
 class ModelManager:
@@ -85,7 +85,8 @@ class ModelManager:
                                    overlay_colormap=self.cfg.overlay_colormap, overlay_alpha=self.cfg.overlay_alpha,
                                    overlay_jpeg_quality=self.cfg.overlay_jpeg_quality,
                                    palette_colors=self.cfg.palette_colors,
-                                   locate_boxes=self.cfg.locate_boxes, cutout_gate=self.cfg.cutout_gate)
+                                   locate_boxes=self.cfg.locate_boxes, cutout_gate=self.cfg.cutout_gate,
+                                   cutout_png=self.cfg.cutout_png)
             s = Servable(self.name, v, src, self.cfg, self.devices)
         except Exception as e:  # noqa: BLE001
             log.exception("loading %s version %d failed", self.name, v)

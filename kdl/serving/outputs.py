@@ -2,7 +2,7 @@
 
 A signature answers with one of ten kinds of row: the fp32 ``logits``, or what the ``classify``,
 ``embed``, ``similar``, ``explain``, ``attention``, ``overlay``, ``overlay_jpeg``, ``palette`` and ``locate``
-trios pack into the same fp32 words. An eleventh, what the ``cutout`` trio packs, is ``CUTOUT`` beside the
+trios pack into the same fp32 words. An eleventh and a twelfth, what the ``cutout`` and ``cutout_png`` trios pack, are ``CUTOUT`` and ``CUTOUT_PNG`` beside the
 table: the picture itself with an alpha channel, a word per pixel.
 Everything that differs between the kinds is in ``KINDS`` and ``CUTOUT``; runners, executors, answer builders
 and the loader ask ``kind_of`` and name no kind. Per kind:
@@ -30,8 +30,8 @@ from typing import Callable
 import numpy as np
 import torch
 
-from ..engine.base import overlay_jpeg_cap, overlay_words
-from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, rollout, similar
+from ..engine.base import cutout_png_cap, overlay_jpeg_cap, overlay_words
+from . import classify, cutout, embed, explain, jpeg_encode, locate, overlay, palette, png_encode, rollout, similar
 from . import protos as P
 from .jpeg import BYTES_SIGNATURE
 from .metrics import METRICS
@@ -68,6 +68,10 @@ def _cutout_kw(sig, src, dev) -> dict:
     return dict(_map_kw(sig, src, dev), cutout=src.cutout)
 
 
+def _cutout_png_kw(sig, src, dev) -> dict:
+    return dict(_cutout_kw(sig, src, dev), cutout_png=src.cutout_png)
+
+
 # ---------------------------------------------------------------------- CPU executor rows
 def _info(src):
     from ..engine import registry
@@ -101,6 +105,10 @@ def _map_rows(sig, src, x):
         return locate.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(3)))
     if _is_cutout(sig):
         ans = [cutout.cutout_rule(img, m, src.cutout) for img, m in zip(x.numpy(), heat)]
+        if _is_cutout_png(sig):
+            cap = _cutout_png_cap(sig, src)
+            files = png_encode.png_rule(np.stack([a[1] for a in ans]), cap)
+            return png_encode.pack_rows(k, score, heat, np.stack([a[0] for a in ans]), files, cap)
         return cutout.pack_rows(k, score, heat, *(np.stack([a[i] for a in ans]) for i in range(2)))
     if not sig.overlay:
         return explain.pack_rows(k, score, heat)
@@ -145,6 +153,19 @@ def _locate_words(sig, src) -> int:
 def _is_cutout(sig) -> bool:
     """An explain-kind signature with a ``coverage`` output answers the picture with an alpha channel."""
     return bool(sig.explain and any(o[0] == "coverage" for o in sig.outputs))
+
+
+def _is_cutout_png(sig) -> bool:
+    """A cutout signature whose last output is a DT_STRING answers the picture as a file."""
+    return bool(_is_cutout(sig) and sig.outputs[-1][1] == P.DT_STRING)
+
+
+def _cutout_png_cap(sig, src) -> int:
+    return cutout_png_cap(src.input_size, src.cutout_png.max_bytes)
+
+
+def _cutout_png_words(sig, src) -> int:
+    return 2 + sig.explain[0] * sig.explain[1] + 2 + (_cutout_png_cap(sig, src) + 3) // 4
 
 
 def _cutout_s(sig) -> int:
@@ -223,6 +244,17 @@ def _cutout_columns(src, sig, rows) -> list:
         ("cutout", P.DT_UINT8, pics), ("coverage", P.DT_FLOAT, cutout.coverage_of(counts, S).reshape(-1, 1))]
 
 
+def _cutout_png_columns(src, sig, rows) -> list:
+    """The cutout's classes, scores and coverage and each row's file; a row whose file did not fit answers b""."""
+    classes, scores, heat, counts, files = png_encode.unpack_rows(rows, *sig.explain, _cutout_png_cap(sig, src))
+    lost = sum(not f for f in files)
+    if lost:
+        METRICS.inc("kdl_cutout_png_overflow_total", lost, signature=sig.name)
+    return _front_columns(src, classes, scores, heat)[:2] + [
+        ("coverage", P.DT_FLOAT, cutout.coverage_of(counts, src.input_size).reshape(-1, 1)),
+        ("png_bytes", P.DT_STRING, files)]
+
+
 @dataclass(frozen=True)
 class Kind:
     name: str
@@ -266,14 +298,16 @@ KINDS = {k.name: k for k in (
 )}
 CUTOUT = Kind("cutout", cutout.CUTOUT_SIGNATURES, "kdl_cutout_total",
               **dict(_MAP, engine=_cutout_kw, gpu_words=_cutout_words, columns=_cutout_columns))
+CUTOUT_PNG = Kind("cutout_png", png_encode.CUTOUT_PNG_SIGNATURES, "kdl_cutout_png_total",
+                  **dict(_MAP, engine=_cutout_png_kw, gpu_words=_cutout_png_words, columns=_cutout_png_columns))
 # the second and third name of every trio -> (0 any-size image / 1 encoded file, the trio's first name)
-WRAPPED = {name: (i, k.trio[0]) for k in (*KINDS.values(), CUTOUT) for i, name in enumerate(k.trio[1:])}
+WRAPPED = {name: (i, k.trio[0]) for k in (*KINDS.values(), CUTOUT, CUTOUT_PNG) for i, name in enumerate(k.trio[1:])}
 
 
 def kind_of(sig) -> Kind:
     """The kind of a signature's rows, from the fields SignatureInfo has."""
     if _is_cutout(sig):
-        return CUTOUT
+        return CUTOUT_PNG if _is_cutout_png(sig) else CUTOUT
     name = ("locate" if _is_locate(sig) else "palette" if _is_palette(sig) else "overlay_jpeg" if _is_jpeg(sig) else "overlay" if sig.overlay else "attention" if sig.explain and sig.rollout else
             "explain" if sig.explain else "similar" if sig.similar else "classify" if sig.top_k else
             "embed" if sig.embed else "logits")
