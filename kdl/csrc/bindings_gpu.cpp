@@ -217,6 +217,7 @@ EmbedRowsArgs embed_rows_args(const py::dict& d) {
 GalleryTopkArgs gallery_topk_args(const py::dict& d) {
   GalleryTopkArgs a{};
   a.q = P<const float>(d, "q"); a.g = P<const uint16_t>(d, "g"); a.out = P<int32_t>(d, "out");
+  a.g8 = P<const uint8_t>(d, "g8"); a.scale = P<const float>(d, "scale");
   a.work = P<void>(d, "work");
   a.B = I(d, "B"); a.N = I(d, "N"); a.F = I(d, "F"); a.K = I(d, "K"); a.ldq = I(d, "ldq"); a.ldg = I(d, "ldg");
   return a;

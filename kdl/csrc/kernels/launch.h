@@ -395,11 +395,20 @@ hipError_t embed_rows(const EmbedRowsArgs& a, hipStream_t s);
 // F % 8 == 0, 8 <= F <= kEmbedMaxF, ldg % 8 == 0, ldg >= F, ldq >= F, 1 <= K <= min(N, kTopkMaxK),
 // 1 <= N <= kGalleryMaxN, 1 <= B <= 1024, g and work 16-byte aligned; anything else is
 // hipErrorInvalidValue and nothing is launched. NaN in q gives unspecified rows.
+// An fp8 gallery (kernels/similar_f8.hip) is given as g8 + scale instead of g: OCP e4m3 codes, one
+// byte per value, and one fp32 scale per row; score[b][j] = scale[j] * sum_i q[b][i] * val(g8[j][i]).
+// Every e4m3 value is a bf16 value, so the sum is the bf16 scan's and the scale one more rounding:
+// |score - exact| <= (F + 17) * 2^-23 * scale[j] * sum_i |q_i| * |val(g8_ji)|; equal rows with equal
+// scales give bit-equal scores. NaN codes (0x7F, 0xFF) in the F used columns give unspecified rows.
+// Then F % 16 == 0, 16 <= F, ldg % 16 == 0, g8 16-byte and scale 4-byte aligned, g null; the
+// workspace, `out` and every other condition are the bf16 gallery's.
 constexpr int kGalleryMaxN = 1 << 24;
 constexpr int kGalleryChunk = 256;   // gallery rows per workgroup of the scan
 struct GalleryTopkArgs {
   const float* q;         // [B][ldq] fp32 query rows, F used per row
   const uint16_t* g;      // [N][ldg] bf16 gallery rows, F used per row, 16-byte aligned
+  const uint8_t* g8;      // or [N][ldg] e4m3 gallery rows, F used per row, 16-byte aligned
+  const float* scale;     // with g8: [N] row scales
   int32_t* out;           // [B][2K]
   void* work;             // split queries + partial candidates: gallery_topk_workspace(B, N, K) bytes, 16-byte aligned
   int B, N, F, K, ldq, ldg;

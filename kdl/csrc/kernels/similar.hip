@@ -28,28 +28,13 @@
 // winner: no state but the previous winner, and a round reads one entry per chunk (a few more
 // for chunks that already won). Separate launches instead of a last-block-done counter, as in
 // embed.hip: no state to reset between graph replays. No atomics; two launches are bit-equal.
-#include <climits>
-
-#include "common.h"
-#include "launch.h"
+// An fp8 gallery (GalleryTopkArgs::g8) takes the same split and merge around the scan of
+// similar_f8.hip; similar.h holds what the two scans share.
+#include "similar.h"
 
 namespace kdl {
 
-constexpr int GAL_WAVES = 4, GAL_TILES = 4, GAL_WROWS = 16 * GAL_TILES;
-constexpr int GAL_LDS = kGalleryChunk + 4;          // fp32 row stride of the score tile
-static_assert(GAL_WAVES * GAL_WROWS == kGalleryChunk, "chunk = rows of one workgroup");
-
-struct GalCand { float v; int i; };                 // 8 bytes of work
 constexpr int GAL_HEADS = 16;                       // list heads a merging lane loads at once
-
-// work = [split queries: 2 * ceil(B / 32) tiles (whole scan passes; queries >= B are zeros) x
-// kGalSteps k-steps x 3 terms x 64 lanes x 16 bytes, sized for kEmbedMaxF because the workspace
-// size does not depend on F][candidates]
-constexpr int kGalSteps = kEmbedMaxF / 32;
-__host__ __device__ static int gallery_tiles(int B) { return 2 * ((B + 31) / 32); }
-__host__ __device__ static size_t gallery_split_bytes(int B) {
-  return (size_t)gallery_tiles(B) * kGalSteps * 3 * 64 * sizeof(u32x4);
-}
 
 // grid (k-steps, query tiles), one wave: lane l splits q[tile * 16 + l % 16][32 * step + 8 * (l / 16) + 0..7]
 template <bool QV>
@@ -148,35 +133,7 @@ __global__ __launch_bounds__(64 * GAL_WAVES) void gallery_scan_kernel(GalleryTop
           (float4){acc[t][u][0], acc[t][u][1], acc[t][u][2], acc[t][u][3]};
   __syncthreads();
 
-  constexpr int R = kGalleryChunk / 64;
-  const int base = chunk * kGalleryChunk;
-  for (int ql = wave; ql < 16 * QT && b0 + ql < a.B; ql += GAL_WAVES) {
-    float v[R];
-    unsigned taken = 0;                       // bit r: row is past N or already picked
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      v[r] = sc[ql][r * 64 + lane];
-      if (base + r * 64 + lane >= a.N) taken |= 1u << r;
-    }
-    float myv = -INFINITY;
-    int myi = INT_MAX;
-    for (int k = 0; k < a.K; ++k) {
-      float bv = -INFINITY;
-      int bi = INT_MAX;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {            // ascending index: '>' keeps the first of equals
-        const bool free_ = !((taken >> r) & 1u);
-        if (free_ && (bi == INT_MAX || v[r] > bv)) { bv = v[r]; bi = base + r * 64 + lane; }
-      }
-      topk_wave_best(bv, bi);                 // every lane now holds the same winner
-      if (bi != INT_MAX && ((bi - base) & 63) == lane) taken |= 1u << ((bi - base) >> 6);
-      if (lane == k) { myv = bv; myi = bi; }
-    }
-    if (lane < a.K) {
-      GalCand* w = (GalCand*)((char*)a.work + gallery_split_bytes(a.B)) + ((long)(b0 + ql) * a.K + lane) * chunks + chunk;
-      *w = GalCand{myv, myi};
-    }
-  }
+  gallery_pick<QT>(sc, a, chunks, chunk, b0, lane, wave);
 }
 
 __global__ __launch_bounds__(64) void gallery_merge_kernel(GalleryTopkArgs a, int chunks) {
@@ -224,7 +181,11 @@ size_t gallery_topk_workspace(int B, int N, int K) {
 }
 
 hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s) {
-  if (!a.q || ((uintptr_t)a.q & 3) || !a.g || ((uintptr_t)a.g & 15) || !a.out || ((uintptr_t)a.out & 3) ||
+  const bool f8 = a.g8 != nullptr;
+  if (f8 ? a.g || ((uintptr_t)a.g8 & 15) || !a.scale || ((uintptr_t)a.scale & 3) || a.F % 16 != 0 || a.ldg % 16 != 0
+         : a.scale != nullptr)
+    return hipErrorInvalidValue;
+  if (!a.q || ((uintptr_t)a.q & 3) || (!f8 && (!a.g || ((uintptr_t)a.g & 15))) || !a.out || ((uintptr_t)a.out & 3) ||
       !a.work || ((uintptr_t)a.work & 15) || a.B < 1 || a.B > 1024 || a.N < 1 || a.N > kGalleryMaxN ||
       a.F < 8 || a.F % 8 != 0 || a.F > kEmbedMaxF || a.ldg % 8 != 0 || a.ldg < a.F || a.ldq < a.F ||
       a.K < 1 || a.K > kTopkMaxK || a.K > a.N)
@@ -234,7 +195,8 @@ hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s) {
   const dim3 sgrid((a.F + 31) / 32, gallery_tiles(a.B));
   if (!((uintptr_t)a.q & 15) && a.ldq % 4 == 0) hipLaunchKernelGGL(gallery_split_kernel<true>, sgrid, dim3(64), 0, s, a);
   else hipLaunchKernelGGL(gallery_split_kernel<false>, sgrid, dim3(64), 0, s, a);
-  if (a.B <= 16) hipLaunchKernelGGL(gallery_scan_kernel<1>, grid, dim3(64 * GAL_WAVES), 0, s, a, chunks);
+  if (f8) gallery_scan_f8(a, chunks, s);
+  else if (a.B <= 16) hipLaunchKernelGGL(gallery_scan_kernel<1>, grid, dim3(64 * GAL_WAVES), 0, s, a, chunks);
   else hipLaunchKernelGGL(gallery_scan_kernel<2>, grid, dim3(64 * GAL_WAVES), 0, s, a, chunks);
   hipLaunchKernelGGL(gallery_merge_kernel, dim3(a.B), dim3(64), 0, s, a, chunks);
   return hipGetLastError();

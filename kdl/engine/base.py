@@ -275,10 +275,13 @@ class Similar:
     tensor [N, ldg] of stored bf16 rows (``kdl.serving.similar.load_gallery``'s values), ldg a
     multiple of 8 and at least the family's F. It is shared: every engine on that device built
     from this object reads the same copy. ``k`` neighbours per image (clipped to N); ``metric``
-    "cosine" normalises the query rows (the stored rows are already unit length), "dot" does not."""
+    "cosine" normalises the query rows (the stored rows are already unit length), "dot" does not.
+    With ``scale``, an fp32 [N] tensor on the same device, the gallery is fp8: uint8 e4m3 codes
+    [N, ldg] (``load_gallery_fp8``'s), ldg and F multiples of 16, scored as scale[j] * sum_i q_i * val(code_ji)."""
     gallery: torch.Tensor
     k: int = 5
     metric: str = "cosine"
+    scale: torch.Tensor | None = None
 
 
 @dataclass(frozen=True)
@@ -611,11 +614,20 @@ class EngineBase:
             raise ValueError(f"similar: metric must be one of {SIMILAR_METRICS}, got {sim.metric!r}")
         if F % 8 or F > lib.EMBED_MAX_F:
             raise ValueError(f"similar: {F} features; the kernel takes a multiple of 8 up to {lib.EMBED_MAX_F}")
-        if (g.dim() != 2 or g.dtype != torch.bfloat16 or not self._on_device(g) or not g.is_contiguous()
-                or g.shape[1] < F or g.shape[1] % 8 or not 1 <= g.shape[0] <= lib.GALLERY_MAX_N):
-            raise ValueError(f"similar: the gallery must be a contiguous bf16 [N, >= {F}] tensor on {self.device} "
-                             f"with 1 <= N <= {lib.GALLERY_MAX_N} and a row stride that is a multiple of 8, got "
+        gdt, mult = (torch.bfloat16, 8) if sim.scale is None else (torch.uint8, 16)
+        if F % mult:
+            raise ValueError(f"similar: {F} features; an fp8 gallery takes a multiple of {mult}")
+        if (g.dim() != 2 or g.dtype != gdt or not self._on_device(g) or not g.is_contiguous()
+                or g.shape[1] < F or g.shape[1] % mult or not 1 <= g.shape[0] <= lib.GALLERY_MAX_N):
+            raise ValueError(f"similar: the gallery must be a contiguous {'bf16' if sim.scale is None else 'uint8 (e4m3)'} "
+                             f"[N, >= {F}] tensor on {self.device} "
+                             f"with 1 <= N <= {lib.GALLERY_MAX_N} and a row stride that is a multiple of {mult}, got "
                              f"{tuple(g.shape)} {g.dtype} on {g.device}")
+        sc = sim.scale
+        if sc is not None and (sc.dim() != 1 or sc.dtype != torch.float32 or not self._on_device(sc)
+                               or not sc.is_contiguous() or sc.shape[0] != g.shape[0]):
+            raise ValueError(f"similar: the scale of an fp8 gallery must be a contiguous fp32 [{g.shape[0]}] tensor on "
+                             f"{self.device}, got {tuple(sc.shape)} {sc.dtype} on {sc.device}")
         if sim.k < 1:
             raise ValueError(f"similar: k must be >= 1, got {sim.k}")
         self.similar_k = min(int(sim.k), g.shape[0])
@@ -646,7 +658,9 @@ class EngineBase:
 
     def _emit_similar(self, prog, step: Step, b: int) -> None:
         g, feat, out = self.similar.gallery, self.feature_slot(self._slot), self._out_rows()
-        prog.add_gallery_topk(step.name, dict(q=_lib.ptr(feat), g=_lib.ptr(g), out=_lib.ptr(out),
+        sc = self.similar.scale
+        gal = dict(g=_lib.ptr(g)) if sc is None else dict(g8=_lib.ptr(g), scale=_lib.ptr(sc))
+        prog.add_gallery_topk(step.name, dict(q=_lib.ptr(feat), out=_lib.ptr(out), **gal,
                                               work=_lib.ptr(self._similar_workspace(self._slot)), B=b,
                                               N=g.shape[0], F=feat.shape[1], K=self.similar_k,
                                               ldq=feat.shape[1], ldg=g.shape[1]))

@@ -112,8 +112,11 @@ class ModelSource:
     embed_normalize: str = "none"
     embed_dim: int = 0
     # gallery search (serving/similar.py): the stored bf16 patterns [N, F] (None = no gallery and no
-    # similar signatures), an id per row, K, the metric, and the device copies (one per device)
+    # similar signatures), an id per row, K, the metric, and the device copies (one per device);
+    # similar_dtype "fp8": the gallery is e4m3 codes and gallery_scale their fp32 row scales [N]
     gallery: np.ndarray | None = None
+    similar_dtype: str = "bf16"
+    gallery_scale: np.ndarray | None = None
     gallery_ids: list = field(default_factory=list)
     similar_k: int = 0
     similar_metric: str = "cosine"
@@ -153,7 +156,7 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      classify_top_k: int | None = None, embedding_normalize: str | None = None,
-                     similar_top_k: int | None = None, gallery: bool = True,
+                     similar_top_k: int | None = None, similar_dtype: str | None = None, gallery: bool = True,
                      overlay_colormap: str | None = None, overlay_alpha: float | None = None,
                      overlay_jpeg_quality: int | None = None, palette_colors: int | None = None,
                      locate_boxes: int | None = None, cutout_gate: int | None = None,
@@ -163,7 +166,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     "preprocess" string of its kdl_model.json / synthetic.json, else nearest. ``classify_top_k``
     (the server's --classify_top_k) overrides the version's classify K (serving/classify.py),
     ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py),
-    ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py);
+    ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py) and
+    ``similar_dtype`` (--similar_dtype) how its gallery is stored;
     ``gallery=False`` leaves the version's gallery files alone (the tool that writes them);
     ``overlay_colormap`` / ``overlay_alpha`` (--overlay_colormap, --overlay_alpha) override the
     version's "overlay" block (serving/overlay.py); ``overlay_jpeg_quality`` (--overlay_jpeg_quality) turns
@@ -189,7 +193,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
-        similar.add_signatures(src, path, similar_top_k)
+        similar.add_signatures(src, path, similar_top_k, similar_dtype)
     explain.add_signatures(src, path)
     rollout.add_signatures(src, path)
     overlay.add_signatures(src, path, overlay_colormap, overlay_alpha)

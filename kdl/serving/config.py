@@ -98,6 +98,9 @@ class ServerConfig:
     # K of the similar signatures (serving/similar.py); None = the model version's own
     # "similar": {"top_k": K}, else 5. 1..32, clipped to the gallery's row count
     similar_top_k: int | None = None
+    # how the gallery of the similar signatures is stored on the device: "bf16" or "fp8" (e4m3 codes
+    # and a scale per row: half the bytes); None = the version's own "similar": {"dtype": ...}, else bf16
+    similar_dtype: str | None = None
     # colour table and strength of the overlay signatures (serving/overlay.py); None = the model
     # version's own "overlay": {"colormap": ..., "alpha": ...}, else jet and 0.5
     overlay_colormap: str | None = None
@@ -254,6 +257,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="gallery items and scores per image of the similar / similar_image / similar_bytes "
                          "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
                          "\"similar\": {\"top_k\": K} (env KDL_SIMILAR_TOP_K, default: the version's, else 5)")
+    ap.add_argument("--similar_dtype", choices=["bf16", "fp8"], default=None,
+                    help="how the gallery of the similar signatures is stored: bf16, or fp8 = e4m3 codes and one "
+                         "scale per row, half the bytes per scan; overrides the model version's "
+                         "\"similar\": {\"dtype\": ...} (env KDL_SIMILAR_DTYPE, default: the version's, else bf16)")
     ap.add_argument("--scatter", choices=["host", "rccl"], default="host",
                     help="rccl: one front-end process scatters each batch over the node's GPUs and gathers "
                          "the logits on RCCL (one process per GPU, --dp_world of them); host: every server "
@@ -293,6 +300,9 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
         bp.allowed_batch_sizes = sorted(int(x) for x in a.allowed_batch_sizes.split(","))
         bp.max_batch_size = bp.allowed_batch_sizes[-1]
     labels = [s for s in env.get("LABELS", "").split(",") if s]
+    similar_dtype = a.similar_dtype or env.get("KDL_SIMILAR_DTYPE") or None
+    if similar_dtype not in (None, "bf16", "fp8"):           # the flag has argparse's choices, the variable this
+        raise ValueError(f"KDL_SIMILAR_DTYPE must be bf16 or fp8, got {similar_dtype!r}")
     return ServerConfig(port=a.port, rest_api_port=a.rest_api_port, model_name=name, model_base_path=base,
                         enable_batching=_truthy(a.enable_batching), batching=bp,
                         file_system_poll_wait_seconds=a.file_system_poll_wait_seconds,
@@ -317,6 +327,7 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         embedding_normalize=a.embedding_normalize or env.get("KDL_EMBEDDING_NORMALIZE") or None,
                         similar_top_k=(a.similar_top_k if a.similar_top_k is not None
                                        else int(env["KDL_SIMILAR_TOP_K"]) if env.get("KDL_SIMILAR_TOP_K") else None),
+                        similar_dtype=similar_dtype,
                         overlay_colormap=a.overlay_colormap or env.get("KDL_OVERLAY_COLORMAP") or None,
                         overlay_alpha=(a.overlay_alpha if a.overlay_alpha is not None
                                        else float(env["KDL_OVERLAY_ALPHA"]) if env.get("KDL_OVERLAY_ALPHA") else None),

@@ -44,7 +44,8 @@ NATIVE_INPUT_KEY = "images"
 # ---------------------------------------------------------------------- GPU engine keywords
 def _similar_kw(sig, src, dev) -> dict:
     from ..engine.base import Similar
-    return dict(similar=Similar(similar.device_gallery(src, dev), sig.top_k, src.similar_metric))
+    return dict(similar=Similar(similar.device_gallery(src, dev), sig.top_k, src.similar_metric,
+                                similar.device_scale(src, dev)))
 
 
 def _map_kw(sig, src, dev) -> dict:
@@ -284,7 +285,7 @@ KINDS = {k.name: k for k in (
          engine=_similar_kw, gpu_words=lambda sig, src: 2 * sig.top_k,
          host_words=lambda sig, src: src.gallery.shape[1], cpu_rows=_feature_rows,
          host_step=lambda sig, src, rows: classify.pack_rows(
-             *similar.similar_rule(rows, src.gallery, sig.top_k, src.similar_metric)),
+             *similar.similar_rule(rows, src.gallery, sig.top_k, src.similar_metric, src.gallery_scale)),
          columns=_ranked(similar.ids_of)),
     Kind("explain", explain.EXPLAIN_SIGNATURES, "kdl_explain_total", **_MAP),
     Kind("attention", rollout.ATTENTION_SIGNATURES, "kdl_attention_total", **_MAP),

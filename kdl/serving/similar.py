@@ -13,11 +13,21 @@ Files in the version directory: ``gallery.npy``, float32 or float16 [N, F] in C 
 else the ids are the decimal row indices. ``python -m kdl.cli build-gallery`` writes both.
 Configuration: ``"similar": {"top_k": 5, "metric": "cosine" | "dot", "gallery": "gallery.npy"}`` in
 ``kdl_model.json`` / ``synthetic.json``; ``--similar_top_k`` overrides K, which is clipped to N.
+``"dtype": "bf16" | "fp8"`` in the same block (``--similar_dtype`` / ``KDL_SIMILAR_DTYPE`` overrides
+it, default bf16) chooses how the rows are stored; the gallery file is the same for both.
 
 The rule. ``load_gallery`` defines the stored values: for cosine each row is divided in float64 by
 max(its L2 norm, 1e-12); the rows are cast to fp32 and rounded to bf16 (nearest even). score[j] =
 sum_i q_i * g_ji with the query as fp32 (for cosine L2-normalised first, ``embed.l2_rule``) and the
-bf16 values as they stand; rows rank by descending score, equal scores by ascending row index."""
+bf16 values as they stand; rows rank by descending score, equal scores by ascending row index.
+
+The fp8 rule. ``load_gallery_fp8`` stores one byte per value and one fp32 scale per row
+(``quantize_fp8``): rows normalised in float64 as above; s_j = fp32(max_i |x_ji| / 448), 1.0 for an
+all-zero row; e_ji the OCP e4m3 code nearest to x_ji / s_j (the quotient taken in float64, cast
+to fp32, clipped to +-448, then torch's round-to-nearest-even ``float8_e4m3fn`` cast, which does
+not saturate by itself), never a NaN code (0x7F, 0xFF). score[j] = s_j * sum_i q_i * val(e_ji),
+query and ranking as above; every e4m3 value is a bf16 value, so the GPU scan
+(kernels/similar_f8.hip) keeps the exact-query arithmetic of the bf16 one at half the bytes."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -34,6 +44,8 @@ DEFAULT_TOP_K = 5
 MAX_TOP_K = 32                     # kTopkMaxK of kernels/launch.h
 GALLERY_MAX_N = 1 << 24            # kGalleryMaxN of kernels/launch.h
 METRICS = ("cosine", "dot")
+DTYPES = ("bf16", "fp8")
+FP8_MAX = 448.0                    # the largest e4m3 value
 DEFAULT_GALLERY = "gallery.npy"
 IDS_FILE = "gallery_ids.txt"
 
@@ -43,12 +55,19 @@ def bf16_to_f64(bits: np.ndarray) -> np.ndarray:
     return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
 
 
-def load_gallery(path: Path, features: int, metric: str = "cosine") -> np.ndarray:
-    """The stored values of the gallery file ``path`` as uint16 bf16 patterns [N, F], C order.
+def fp8_to_f64(codes: np.ndarray) -> np.ndarray:
+    """uint8 e4m3 codes -> the values they stand for, as float64 (NaN for 0x7F / 0xFF)."""
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e - 10.0))
+    v[(c & 0x7F) == 0x7F] = np.nan
+    return np.where(c & 0x80, -v, v)[np.asarray(codes, dtype=np.uint8)]
+
+
+def _read_rows(path: Path, features: int, metric: str) -> np.ndarray:
+    """The rows of the gallery file ``path`` as float64 [N, F], for cosine of unit length.
     ValueError (naming the file) for anything but a finite float32 / float16 [N, features] array
     with 1 <= N <= GALLERY_MAX_N."""
-    import torch
-    path = Path(path)
     if metric not in METRICS:
         raise ValueError(f"similar metric must be one of {METRICS}, got {metric!r}")
     try:
@@ -68,29 +87,76 @@ def load_gallery(path: Path, features: int, metric: str = "cosine") -> np.ndarra
     x = a.astype(np.float64)
     if metric == "cosine":
         x = x / np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-12)
-    x32 = np.ascontiguousarray(x, dtype=np.float32)
+    return x
+
+
+def load_gallery(path: Path, features: int, metric: str = "cosine") -> np.ndarray:
+    """The stored values of the gallery file ``path`` as uint16 bf16 patterns [N, F], C order.
+    ValueError (naming the file) for anything but a finite float32 / float16 [N, features] array
+    with 1 <= N <= GALLERY_MAX_N."""
+    import torch
+    path = Path(path)
+    x32 = np.ascontiguousarray(_read_rows(path, features, metric), dtype=np.float32)
     bits = torch.from_numpy(x32).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
     if not np.isfinite(bf16_to_f64(bits)).all():
         raise ValueError(f"{path}: a value is too large for bf16")
     return np.ascontiguousarray(bits)
 
 
+def quantize_fp8(x: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """float64 rows [N, F] -> (e4m3 codes uint8 [N, F], row scales float32 [N]): the fp8 rule of
+    the module docstring."""
+    import torch
+    x = np.asarray(x, dtype=np.float64)
+    scale = (np.abs(x).max(axis=1) / FP8_MAX).astype(np.float32)
+    scale[scale == 0] = 1.0
+    y = np.clip((x / scale.astype(np.float64)[:, None]).astype(np.float32), -FP8_MAX, FP8_MAX)
+    codes = torch.from_numpy(np.ascontiguousarray(y)).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
+    return np.ascontiguousarray(codes), scale
+
+
+def load_gallery_fp8(path: Path, features: int, metric: str = "cosine") -> tuple[np.ndarray, np.ndarray]:
+    """The fp8 stored values of the gallery file ``path``: (codes uint8 [N, F], scales float32 [N]);
+    the file and its checks are ``load_gallery``'s, and F must be a multiple of 16 (the kernel's)."""
+    path = Path(path)
+    x = _read_rows(path, features, metric)
+    if features % 16:
+        raise ValueError(f"{path}: an fp8 gallery needs a feature count that is a multiple of 16, got {features}")
+    codes, scale = quantize_fp8(x)
+    if not np.isfinite(scale).all():
+        raise ValueError(f"{path}: a value is too large for an fp32 row scale")
+    return codes, scale
+
+
 def similar_rule(features_fp32: np.ndarray, gallery_bf16: np.ndarray, k: int,
-                 metric: str = "cosine") -> tuple[np.ndarray, np.ndarray]:
+                 metric: str = "cosine", scale: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
     """fp32 feature rows [n, F] and the gallery's bf16 patterns [N, F] -> (row indices int32 [n, k],
-    scores fp32 [n, k]): float64 scores, ranked by a stable argsort of their negation."""
+    scores fp32 [n, k]): float64 scores, ranked by a stable argsort of their negation. With
+    ``scale`` (float32 [N]) the gallery is fp8: uint8 e4m3 codes [N, F] and their row scales."""
     q = np.asarray(features_fp32, dtype=np.float32)
     if metric == "cosine":
         from .embed import l2_rule
         q = l2_rule(q)
-    s = q.astype(np.float64) @ bf16_to_f64(gallery_bf16).T
+    if scale is None:
+        s = q.astype(np.float64) @ bf16_to_f64(gallery_bf16).T
+    else:
+        s = (q.astype(np.float64) @ fp8_to_f64(gallery_bf16).T) * np.asarray(scale, dtype=np.float32).astype(np.float64)
     order = np.argsort(-s, axis=1, kind="stable")[:, :k]
     return order.astype(np.int32), np.take_along_axis(s, order, axis=1).astype(np.float32)
 
 
 def resolve(path: Path, features: int, top_k_flag: int | None = None):
     """None for a version without a gallery, else (K, metric, bf16 patterns [N, F], ids [N]) of the
-    version in ``path``; ValueError (naming the file) fails the load."""
+    version in ``path``; ValueError (naming the file) fails the load. (An fp8 version: the first
+    four of ``resolve_stored``.)"""
+    got = resolve_stored(path, features, top_k_flag)
+    return None if got is None else got[:4]
+
+
+def resolve_stored(path: Path, features: int, top_k_flag: int | None = None, dtype_flag: str | None = None):
+    """None for a version without a gallery, else (K, metric, stored values [N, F], ids [N], dtype,
+    scales): bf16 patterns and None, or for "fp8" e4m3 codes and their float32 [N] row scales.
+    ``dtype_flag`` overrides the version's "dtype"; ValueError (naming the file) fails the load."""
     from .outputs import _meta
     path = Path(path)
     meta, name = _meta(path)
@@ -110,7 +176,13 @@ def resolve(path: Path, features: int, top_k_flag: int | None = None):
     metric = spec.get("metric", "cosine")
     if not isinstance(metric, str) or metric not in METRICS:
         raise ValueError(f"{path / name}: similar metric must be one of {METRICS}, got {metric!r}")
-    bits = load_gallery(path / gname, features, metric)
+    dtype = dtype_flag if dtype_flag is not None else spec.get("dtype", "bf16")
+    if not isinstance(dtype, str) or dtype not in DTYPES:
+        raise ValueError(f"{path / name}: similar dtype must be one of {DTYPES}, got {dtype!r}")
+    if dtype == "fp8":
+        bits, scale = load_gallery_fp8(path / gname, features, metric)
+    else:
+        bits, scale = load_gallery(path / gname, features, metric), None
     n = bits.shape[0]
     if (path / IDS_FILE).exists():
         ids = (path / IDS_FILE).read_text().splitlines()
@@ -118,18 +190,18 @@ def resolve(path: Path, features: int, top_k_flag: int | None = None):
             raise ValueError(f"{path / IDS_FILE}: {len(ids)} ids for the {n} rows of {gname}")
     else:
         ids = [str(i) for i in range(n)]
-    return min(k, n), metric, bits, ids
+    return min(k, n), metric, bits, ids, dtype, scale
 
 
-def add_signatures(src, path: Path, top_k_flag: int | None = None) -> None:
+def add_signatures(src, path: Path, top_k_flag: int | None = None, dtype_flag: str | None = None) -> None:
     """Give a loaded ModelSource with a gallery its three similar signatures (beside the others)."""
     from ..engine import registry
     from .outputs import add_trio
     F = src.head.features if src.head is not None else registry.get(src.family).features
-    got = resolve(path, F, top_k_flag)
+    got = resolve_stored(path, F, top_k_flag, dtype_flag)
     if got is None:
         return
-    k, src.similar_metric, src.gallery, src.gallery_ids = got
+    k, src.similar_metric, src.gallery, src.gallery_ids, src.similar_dtype, src.gallery_scale = got
     src.similar_k = k
     outs = (("ids", P.DT_STRING, (-1, k)), ("scores", P.DT_FLOAT, (-1, k)))
     add_trio(src, SIMILAR_SIGNATURES, "ids", (-1, k), outputs=outs, top_k=k, similar=True)
@@ -141,13 +213,30 @@ def ids_of(src, rows: np.ndarray) -> list[list[str]]:
 
 
 def device_gallery(src, device):
-    """The version's gallery as a bf16 tensor on ``device``: one copy per (version, device), shared
-    by every engine there."""
+    """The version's gallery as a bf16 tensor on ``device`` (an fp8 gallery: its uint8 codes): one
+    copy per (version, device), shared by every engine there."""
     import torch
     dev = torch.device(device)
     with src.gallery_lock:
         t = src.gallery_device.get(dev)
         if t is None:
-            t = torch.from_numpy(src.gallery.view(np.int16)).to(dev).view(torch.bfloat16)
+            if src.gallery_scale is not None:
+                t = torch.from_numpy(src.gallery).to(dev)
+            else:
+                t = torch.from_numpy(src.gallery.view(np.int16)).to(dev).view(torch.bfloat16)
             src.gallery_device[dev] = t
+        return t
+
+
+def device_scale(src, device):
+    """The row scales of the version's fp8 gallery as an fp32 tensor on ``device``, one copy per
+    (version, device) like the codes; None for a bf16 gallery."""
+    import torch
+    if src.gallery_scale is None:
+        return None
+    key = (torch.device(device), "scale")
+    with src.gallery_lock:
+        t = src.gallery_device.get(key)
+        if t is None:
+            t = src.gallery_device[key] = torch.from_numpy(src.gallery_scale).to(key[0])
         return t

@@ -1,6 +1,6 @@
 """Gallery search timings on one GPU (profiles/similar.txt).
 
-  python -m tools.similar_bench [--rows 10000,100000,1000000] [--out FILE]
+  python -m tools.similar_bench [--rows 10000,100000,1000000] [--dtype bf16|fp8] [--out FILE]
 
 1. The gallery_topk op alone (kernels/similar.hip) at F = 2048, B = 32, K = 5: microseconds per call
    and gallery bytes / time. "same" re-reads one gallery (a 41 MB or 410 MB one then sits partly or
@@ -9,6 +9,12 @@
 2. The same answer from torch: (q @ g.T).topk(K) with both operands bf16, and with both fp32.
 3. An Xception ``similar`` engine's batch-32 forward (captured graph) against an ``embed="l2"``
    engine's, as interleaved pairs.
+
+``--dtype fp8`` (profiles/similar_fp8.txt) stores the same rows as e4m3 codes with a scale per row
+(kernels/similar_f8.hip): 1 times that gallery and counts how many of the float64 top-K of the
+unquantised rows its ranking keeps, 2 is left out, and 3 pairs a bf16-gallery ``similar`` engine
+with an fp8-gallery one. ``--embed-recall N`` adds the same count on a gallery of N Xception embed
+rows with planted near-duplicates, for an fp8 and a bf16 gallery.
 
 Each time is the median of ``--repeats`` windows of ``--iters`` calls between two device events,
 after warm-up calls of the same shapes."""
@@ -40,13 +46,62 @@ def window(fn, iters: int, repeats: int, warm: int = 5) -> tuple[float, float]:
     return statistics.median(out), min(out)
 
 
-def random_gallery(n: int, seed: int) -> torch.Tensor:
+def unit_slices(n: int, seed: int):
+    """(first row, fp32 unit rows) slices of the random gallery of a seed: no fp32 copy of the whole."""
     g = torch.Generator(device="cuda").manual_seed(seed)
+    for lo in range(0, n, 65536):
+        yield lo, torch.nn.functional.normalize(torch.randn((min(65536, n - lo), F), generator=g, device="cuda"), dim=1)
+
+
+def random_gallery(n: int, seed: int) -> torch.Tensor:
     out = torch.empty((n, F), dtype=torch.bfloat16, device="cuda")
-    for lo in range(0, n, 65536):                       # unit rows, made in slices: no fp32 copy of the whole
-        x = torch.randn((min(65536, n - lo), F), generator=g, device="cuda")
-        out[lo:lo + x.shape[0]] = torch.nn.functional.normalize(x, dim=1).to(torch.bfloat16)
+    for lo, x in unit_slices(n, seed):
+        out[lo:lo + x.shape[0]] = x.to(torch.bfloat16)
     return out
+
+
+def random_gallery_fp8(n: int, seed: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(e4m3 codes uint8 [n, F], fp32 scales [n]) of the same rows: kdl.serving.similar.quantize_fp8's rule."""
+    codes = torch.empty((n, F), dtype=torch.uint8, device="cuda")
+    scale = torch.empty(n, dtype=torch.float32, device="cuda")
+    for lo, x in unit_slices(n, seed):
+        s = (x.double().abs().amax(dim=1) / 448.0).float()
+        s[s == 0] = 1.0
+        y = (x.double() / s.double()[:, None]).float().clamp(-448.0, 448.0)
+        codes[lo:lo + x.shape[0]] = y.to(torch.float8_e4m3fn).view(torch.uint8)
+        scale[lo:lo + x.shape[0]] = s
+    return codes, scale
+
+
+def fp8_rows(n: int, iters: int, repeats: int, say) -> None:
+    from kdl.ops import _lib
+    lib = _lib.lib()
+    nbytes = n * F
+    copies = max(1, -(-(1 << 30) // nbytes))
+    gals = [random_gallery_fp8(n, 17 + c) for c in range(copies)]
+    q = torch.nn.functional.normalize(torch.randn((B, F), generator=torch.Generator().manual_seed(3)), dim=1).cuda()
+    out = torch.zeros((B, 2 * K), dtype=torch.int32, device="cuda")
+    work = torch.zeros(lib.gallery_topk_workspace(B, n, K), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+
+    def call(g):
+        lib.gallery_topk(dict(q=q.data_ptr(), g8=g[0].data_ptr(), scale=g[1].data_ptr(), out=out.data_ptr(),
+                              work=work.data_ptr(), B=B, N=n, F=F, K=K, ldq=F, ldg=F), s)
+    it = max(5, min(iters, (64 << 30) // nbytes))
+    for name, pick in (("same", lambda i: gals[0]), ("rotating", lambda i: gals[i % copies])):
+        if name == "rotating" and copies == 1:
+            continue
+        med, best = window(lambda i: call(pick(i)), it, repeats)
+        say(f"N={n:8d} gallery_topk fp8 {name:8s} ({copies if name == 'rotating' else 1} x {nbytes / 1e6:7.1f} MB): "
+            f"median {med:8.1f} us  min {best:8.1f} us  {nbytes / med / 1e6:6.2f} TB/s of gallery bytes")
+    call(gals[0])
+    torch.cuda.synchronize()
+    mine = out[:, :K].cpu()
+    ref = torch.cat([q.double() @ x.double().T for _, x in unit_slices(n, 17)], dim=1).topk(K).indices.cpu()
+    kept = sum(len(set(mine[b].tolist()) & set(ref[b].tolist())) for b in range(B))
+    say(f"N={n:8d} rows of the float64 top-{K} of the unquantised gallery that the fp8 ranking keeps: {kept}/{B * K}, "
+        f"same row at the same rank {int((mine == ref).sum())}/{B * K}")
+    del gals
 
 
 def op_rows(n: int, iters: int, repeats: int, say) -> None:
@@ -89,15 +144,62 @@ def op_rows(n: int, iters: int, repeats: int, say) -> None:
     del gals, gf
 
 
-def engine_pairs(n: int, pairs: int, say) -> None:
+def embed_recall(n: int, say) -> None:
+    """Recall on a gallery of embed rows: n images of random 8 x 8 colour blocks through an Xception
+    embed="l2" engine, and for each of the B query images four near-duplicates (the image plus uniform
+    noise of +-2, 4, 8, 16 levels) planted among them; the queries themselves are not in the gallery."""
+    from kdl.engine import registry
+    from kdl.ops import _lib
+    lib, info = _lib.lib(), registry.get("xception")
+    eng = info.engine(info.init_params(0), 32, "cuda", embed="l2")
+    g = torch.Generator().manual_seed(11)
+    S = info.input_size
+
+    def blocks(m: int) -> torch.Tensor:
+        small = torch.randint(0, 256, (m, 8, 8, 3), generator=g, dtype=torch.uint8)
+        return small.repeat_interleave(38, 1).repeat_interleave(38, 2)[:, :S, :S].contiguous()
+    qi = blocks(B)
+    dup = [(qi.int() + torch.randint(-a, a + 1, qi.shape, generator=g, dtype=torch.int32)).clamp(0, 255).to(torch.uint8)
+           for a in (2, 4, 8, 16)]
+    imgs = torch.cat(dup + [blocks(n - 4 * B)])
+    rows = torch.cat([eng.forward(imgs[lo:lo + 32].cuda()).clone() for lo in range(0, n, 32)])
+    q = eng.forward(qi.cuda()).clone()
+    ref = (q.double() @ rows.double().T).topk(K).indices.cpu()
+    s = (rows.double().abs().amax(dim=1) / 448.0).float()
+    codes = (rows.double() / s.double()[:, None]).float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    bf = rows.to(torch.bfloat16)
+    out = torch.zeros((B, 2 * K), dtype=torch.int32, device="cuda")
+    work = torch.zeros(lib.gallery_topk_workspace(B, n, K), dtype=torch.uint8, device="cuda")
+    for name, gal in (("fp8", dict(g8=codes.data_ptr(), scale=s.data_ptr())), ("bf16", dict(g=bf.data_ptr()))):
+        lib.gallery_topk(dict(q=q.data_ptr(), out=out.data_ptr(), work=work.data_ptr(), B=B, N=n, F=F, K=K, ldq=F, ldg=F,
+                              **gal), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        mine = out[:, :K].cpu()
+        kept = sum(len(set(mine[b].tolist()) & set(ref[b].tolist())) for b in range(B))
+        dups = sum(len(set(mine[b].tolist()) & {b, B + b, 2 * B + b, 3 * B + b}) for b in range(B))
+        say(f"N={n:8d} embed rows, {name:4s} gallery: rows of the float64 top-{K} kept {kept}/{B * K}, same row at the same "
+            f"rank {int((mine == ref).sum())}/{B * K}, planted near-duplicates among the {K} returned {dups}/{4 * B}")
+    say(f"N={n:8d} embed rows: planted near-duplicates in the float64 top-{K} "
+        f"{sum(len(set(ref[b].tolist()) & {b, B + b, 2 * B + b, 3 * B + b}) for b in range(B))}/{4 * B}")
+
+
+def engine_pairs(n: int, pairs: int, say, dtype: str = "bf16") -> None:
+    """Pairs of an embed="l2" engine and a similar engine; dtype "fp8": of a bf16-gallery similar
+    engine (in the "l2" column) and an fp8-gallery one."""
     from kdl.engine import registry
     from kdl.engine.base import Similar
     from kdl.engine.tuning import tuning_path
     info = registry.get("xception")
     p = info.init_params(0)
     gal = random_gallery(n, 5)
-    engines = {"l2": info.engine(p, 32, "cuda", embed="l2"),
-               "similar": info.engine(p, 32, "cuda", similar=Similar(gal, K, "cosine"))}
+    if dtype == "fp8":
+        codes, scale = random_gallery_fp8(n, 5)
+        engines = {"l2": info.engine(p, 32, "cuda", similar=Similar(gal, K, "cosine")),
+                   "similar": info.engine(p, 32, "cuda", similar=Similar(codes, K, "cosine", scale))}
+    else:
+        engines = {"l2": info.engine(p, 32, "cuda", embed="l2"),
+                   "similar": info.engine(p, 32, "cuda", similar=Similar(gal, K, "cosine"))}
+    first = "similar bf16" if dtype == "fp8" else "embed=l2"
     x = torch.randint(0, 256, (32, info.input_size, info.input_size, 3), dtype=torch.uint8,
                       generator=torch.Generator().manual_seed(1)).cuda()
     tp = tuning_path(info.tuning or "xception", 32)
@@ -121,7 +223,7 @@ def engine_pairs(n: int, pairs: int, say) -> None:
         order = ("l2", "similar") if i % 2 == 0 else ("similar", "l2")
         t = {k: timed(engines[k]) for k in order}
         d = (t["similar"] - t["l2"]) * 1e3
-        say(f"pair {i}: embed=l2 {t['l2']:.4f} ms  similar(N={n}) {t['similar']:.4f} ms  diff {d:+.1f} us "
+        say(f"pair {i}: {first} {t['l2']:.4f} ms  similar{' fp8' if dtype == 'fp8' else ''}(N={n}) {t['similar']:.4f} ms  diff {d:+.1f} us "
             f"({100 * d / 1e3 / t['l2']:+.2f} %)")
     prof = dict(engines["similar"].profile(32))
     say(f"similar engine.profile(32), eager launches, median of 20: embed_rows {prof['embed_rows'] * 1e3:.1f} us, "
@@ -135,6 +237,9 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--engine-rows", type=int, default=100000)
+    ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--embed-recall", type=int, default=0, metavar="N",
+                    help="also count what an fp8 gallery of N Xception embed rows with planted near-duplicates keeps")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -147,11 +252,16 @@ def main(argv=None) -> int:
         if f:
             f.write(line + "\n")
             f.flush()
-    say(f"== gallery_topk alone and torch, F={F} B={B} K={K}")
-    for n in (int(v) for v in a.rows.split(",")):
-        op_rows(n, a.iters, a.repeats, say)
-    say("== xception b32 forward (captured graph, device events), embed=l2 vs similar, interleaved pairs")
-    engine_pairs(a.engine_rows, a.pairs, say)
+    say(f"== gallery_topk alone{' and torch' if a.dtype == 'bf16' else ', fp8 gallery'}, F={F} B={B} K={K}")
+    for n in (int(v) for v in a.rows.split(",") if v):
+        (fp8_rows if a.dtype == "fp8" else op_rows)(n, a.iters, a.repeats, say)
+    if a.embed_recall:
+        say(f"== recall on a gallery of Xception embed rows with planted near-duplicates, B={B} K={K}")
+        embed_recall(a.embed_recall, say)
+    if a.pairs:
+        say("== xception b32 forward (captured graph, device events), "
+            f"{'similar bf16 vs similar fp8' if a.dtype == 'fp8' else 'embed=l2 vs similar'}, interleaved pairs")
+        engine_pairs(a.engine_rows, a.pairs, say, a.dtype)
     return 0
 
 
