@@ -244,6 +244,19 @@ RolloutMapArgs rollout_map_args(const py::dict& d) {
   a.B = I(d, "B"); a.T = I(d, "T"); a.ldr = I(d, "ldr"); a.ldo = I(d, "ldo");
   return a;
 }
+AttnAhatArgs attn_ahat_args(const py::dict& d) {
+  AttnAhatArgs a{};
+  a.qkv = P<const uint16_t>(d, "qkv"); a.out = P<float>(d, "out");
+  a.B = I(d, "B"); a.T = I(d, "T"); a.Tq = I(d, "Tq"); a.H = I(d, "H"); a.dh = I(d, "dh", 64);
+  a.scale = F(d, "scale", 0.125f); a.ldr = I(d, "ldr");
+  return a;
+}
+RolloutChainArgs rollout_chain_args(const py::dict& d) {
+  RolloutChainArgs a{};
+  a.ahat = P<const float* const>(d, "ahat"); a.top = P<const int32_t>(d, "top"); a.out = P<float>(d, "out");
+  a.B = I(d, "B"); a.T = I(d, "T"); a.L = I(d, "L"); a.ldr = I(d, "ldr"); a.ldo = I(d, "ldo");
+  return a;
+}
 HeatOverlayArgs heat_overlay_args(const py::dict& d) {
   HeatOverlayArgs a{};
   a.inp = P<const uint8_t>(d, "inp"); a.out = P<float>(d, "out"); a.tab = P<const uint8_t>(d, "tab");
@@ -438,6 +451,18 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(rollout_map(a, S(s)), "rollout_map");
   });
+  // the rollout heatmap above 256 tokens (kernels/vit_long.hip); rollout_chain's ahat is a DEVICE array of device pointers
+  m.def("attn_ahat", [](py::dict d, uintptr_t s) {
+    const auto a = attn_ahat_args(d);
+    py::gil_scoped_release nogil;
+    chk(attn_ahat(a, S(s)), "attn_ahat");
+  });
+  m.def("rollout_chain", [](py::dict d, uintptr_t s) {
+    const auto a = rollout_chain_args(d);
+    py::gil_scoped_release nogil;
+    chk(rollout_chain(a, S(s)), "rollout_chain");
+  });
+  m.attr("LONG_MAX_T") = int(kLongMaxT);
   // rendered heatmap overlays (kernels/overlay.hip): d = the HeatOverlayArgs fields; h_xb / h_yb are HOST addresses
   m.def("heat_overlay", [](py::dict d, uintptr_t s) {
     const auto a = heat_overlay_args(d);
@@ -842,6 +867,12 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_rollout_map", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_ROLLOUT_MAP; op.name = name; op.rm = rollout_map_args(d); p.add(op);
+      })
+      .def("add_attn_ahat", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_ATTN_AHAT; op.name = name; op.ah = attn_ahat_args(d); p.add(op);
+      })
+      .def("add_rollout_chain", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_ROLLOUT_CHAIN; op.name = name; op.rc = rollout_chain_args(d); p.add(op);
       })
       .def("add_heat_overlay", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_HEAT_OVERLAY; op.name = name; op.ho = heat_overlay_args(d); p.add(op);

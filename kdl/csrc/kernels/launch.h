@@ -494,6 +494,39 @@ struct RolloutMapArgs {
 };
 hipError_t rollout_map(const RolloutMapArgs& a, hipStream_t s);
 
+// The rollout heatmap above 256 tokens (kernels/vit_long.hip; ViT-B/16 at 384 x 384 has 577): two entry
+// points of their own beside attn_rollout / rollout_map, whose limits stay as they are.
+constexpr int kLongMaxT = 1024;
+// A^ = (mean_h softmax(Q_h K_h^T * scale) + I) / 2 of one layer (attn_rollout's first half), on the
+// packed qkv [B*T][3*H*dh] bf16: out is fp32 [B][T][ldr], of which the rows 0 .. Tq-1 and the columns
+// 0 .. T-1 of the images 0 .. B-1 are written and nothing else. Sums run in a fixed order without
+// atomics: launches are bit-identical and row 0 of a Tq = 1 launch equals row 0 of a Tq = T launch.
+// dh != 64, T outside 1..kLongMaxT, H < 1, B < 1, Tq outside 1..T, ldr < T, ldr % 4 != 0 and a null or
+// not 16-byte aligned qkv / out are hipErrorInvalidValue, and nothing is launched.
+struct AttnAhatArgs {
+  const uint16_t* qkv;
+  float* out;
+  int B, T, Tq, H, dh;    // dh = 64
+  float scale;            // 1/sqrt(dh)
+  int ldr;                // row stride of out in floats
+};
+hipError_t attn_ahat(const AttnAhatArgs& a, hipStream_t s);
+
+// The rollout heatmap row of each image from the layers' A^ (attn_ahat), one launch behind the last
+// layer: v = row 0 of A^_L, v = v A^_l for l = L-1 .. 1 (fp32 fmaf chains over ascending rows in 16 fixed
+// parts, added in order: launches are bit-identical), then out[b] = [top[b], v[1 .. T-1] / their
+// largest value] as rollout_map writes it. ahat is a DEVICE array of L device pointers, ahat[l] = A^ of
+// layer l + 1, each fp32 [B][T][ldr] and 16-byte aligned; of ahat[L-1] only row 0 is read.
+// T outside 2..kLongMaxT, L < 1, B < 1, ldr < T, ldr % 4 != 0, ldo < T + 1 and a null or unaligned
+// ahat / top / out are hipErrorInvalidValue, and nothing is launched.
+struct RolloutChainArgs {
+  const float* const* ahat;
+  const int32_t* top;     // [B][2]
+  float* out;             // [B][ldo]
+  int B, T, L, ldr, ldo;
+};
+hipError_t rollout_chain(const RolloutChainArgs& a, hipStream_t s);
+
 // Rendered heatmap overlays (kernels/overlay.hip): behind class_map / rollout_map, one launch paints
 // each image's h x w map over the S x S x 3 uint8 picture the model saw, in integers throughout
 // (kdl/serving/overlay.py overlay_rule is the definition):

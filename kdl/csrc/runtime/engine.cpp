@@ -42,6 +42,8 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_LOCATE: return locate(op.loc, s);
     case OP_CUTOUT: return cutout(op.cut, s);
     case OP_PNG_ENCODE: return png_encode(op.pe, s);
+    case OP_ATTN_AHAT: return attn_ahat(op.ah, s);
+    case OP_ROLLOUT_CHAIN: return rollout_chain(op.rc, s);
   }
   return hipErrorInvalidValue;
 }

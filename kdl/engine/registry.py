@@ -146,15 +146,38 @@ def _vit_b16_fp8():
                      rollout_oracle=V.vit_rollout, map_size=(V.INPUT_SIZE // V.PATCH, V.INPUT_SIZE // V.PATCH))
 
 
+def _vit_b16_384(fp8: bool = False):
+    """torchvision's ``IMAGENET1K_SWAG_E2E_V1`` shape: 384 x 384, 577 tokens, a (1, 577, 768) position
+    embedding; the lowering of ``vit_b16`` on more rows, with the long-sequence attention and rollout
+    kernels (kernels/vit_long.hip). No tuning table yet: the GEMM tiles are the defaults."""
+    from ..models import vit as V
+    from .vit import ViTEngine
+    S = 384
+    return ModelInfo("vit_b16_384_fp8" if fp8 else "vit_b16_384", S, 1000, V.count_params(size=S),
+                     "ViT-B/16 384x384 (torchvision layout, 86,859,496 params, 577 tokens)"
+                     + (", e4m3 linears" if fp8 else ""),
+                     lambda seed=0: V.init_params(seed=seed, size=S),
+                     lambda p, max_batch, device, **kw: ViTEngine(p, max_batch=max_batch, device=device, fp8=fp8,
+                                                                  size=S, **kw),
+                     lambda p, x: V.vit_forward(p, x, size=S),
+                     dtype="fp8-e4m3 linears / bf16 rest" if fp8 else "bf16",
+                     stage_cut="encoder.layers.encoder_layer_5.mlp.3",
+                     features=V.DIM, feature_oracle=lambda p, x: V.vit_features(p, x, size=S),
+                     rollout_oracle=lambda p, x: V.vit_rollout(p, x, size=S), map_size=(S // V.PATCH, S // V.PATCH))
+
+
 _FACTORIES = {"xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),
-              "vit_b16": _vit_b16, "vit_b16_fp8": _vit_b16_fp8, "efficientnet_b7": _efficientnet_b7}
+              "vit_b16": _vit_b16, "vit_b16_fp8": _vit_b16_fp8, "efficientnet_b7": _efficientnet_b7,
+              "vit_b16_384": _vit_b16_384, "vit_b16_384_fp8": lambda: _vit_b16_384(True)}
 
 
 # (family, --dtype) -> engine variant; "auto" keeps the family's own default
 _VARIANTS = {("resnet50", "bf16"): "resnet50_bf16", ("resnet50_bf16", "fp16"): "resnet50",
-             ("vit_b16", "fp8"): "vit_b16_fp8", ("vit_b16_fp8", "bf16"): "vit_b16"}
+             ("vit_b16", "fp8"): "vit_b16_fp8", ("vit_b16_fp8", "bf16"): "vit_b16",
+             ("vit_b16_384", "fp8"): "vit_b16_384_fp8", ("vit_b16_384_fp8", "bf16"): "vit_b16_384"}
 _DTYPES = {"xception": {"bf16"}, "resnet50": {"fp16"}, "resnet50_bf16": {"bf16"}, "vit_b16": {"bf16"},
-           "vit_b16_fp8": {"fp8"}, "efficientnet_b7": {"bf16"}}
+           "vit_b16_fp8": {"fp8"}, "efficientnet_b7": {"bf16"}, "vit_b16_384": {"bf16"},
+           "vit_b16_384_fp8": {"fp8"}}
 
 
 def variant(family: str, dtype: str = "auto") -> str:

@@ -94,7 +94,7 @@ def plan_stages(steps, split_after, scratch=()) -> StagePlan:
     readers: dict = {}                       # writer step -> max reader stage
     for i, st in enumerate(steps):
         r = {}
-        for nm in (st.src, st.res):
+        for nm in (st.src, st.res, *st.extra.get("reads", ())):     # extra["reads"]: what a step reads beyond src / res
             if nm and nm not in ("input", "logits"):
                 w = last_write.get(nm, -1)
                 r[nm] = w
@@ -107,7 +107,7 @@ def plan_stages(steps, split_after, scratch=()) -> StagePlan:
             last_write[st.dst] = i
     touched: dict = {}                       # stages that read or write each name
     for i, st in enumerate(steps):
-        for nm in (st.src, st.res, st.dst):
+        for nm in (st.src, st.res, st.dst, *st.extra.get("reads", ())):
             if nm:
                 touched.setdefault(nm, set()).add(stage[i])
 

@@ -32,6 +32,12 @@ gemm_f8.hip (OCP e4m3 x e4m3, block-scaled MFMA 16x16x128); ln_1 / ln_2 /
 attention / the GELU GEMM write e4m3 directly with static per-tensor scales
 calibrated on the fp32 oracle (amax x 1.25 / 448); weights per output channel.
 The residual stream, QKV, softmax and the patch embedding / head stay bf16/fp32.
+
+size=384 (577 tokens; any multiple of 16 up to 1024 tokens): the same lowering on more rows; attention
+picks its query-tiled kernel above 256 tokens. There rollout=True keeps every
+layer's A^ = (mean_h softmax + I)/2 in a buffer of its own (attn_ahat, AH0 .. AH11; the last layer row 0
+only) and one "rollout_chain" step behind "top1" applies them to row 0 from the left: T^2 work per layer
+where the layer-by-layer product is T^3. Up to 256 tokens the steps are the ones above, unchanged.
 """
 from __future__ import annotations
 
@@ -54,7 +60,7 @@ class ViTEngine(EngineBase):
                  calib: torch.Tensor | None = None, calib_margin: float = 1.25,
                  topk: int = 0, embed: str = "", similar=None, explain: bool = False, rollout: bool = False,
                  overlay=None, overlay_jpeg=None, palette=None, locate=None, cutout=None,
-                 cutout_png=None):
+                 cutout_png=None, size: int = V.INPUT_SIZE):
         if explain:      # before anything touches the device: the class token has no spatial map
             raise ValueError("ViT-B/16 has no spatial feature map in front of its head: no explain outputs "
                              "(its heatmaps are attention rollout: rollout=True)")
@@ -65,13 +71,16 @@ class ViTEngine(EngineBase):
         if fp8:
             self.model_name = "vit_b16_fp8"
             if calib is None:   # synthetic calibration batch (serving would use real images)
-                calib = torch.randint(0, 256, (2, V.INPUT_SIZE, V.INPUT_SIZE, 3),
+                calib = torch.randint(0, 256, (2, size, size, 3),
                                       generator=torch.Generator().manual_seed(1234), dtype=torch.uint8)
-            self.amax = V.activation_amax(params, calib)
+            self.amax = V.activation_amax(params, calib, size)
             self.calib_margin = calib_margin
-        self.size = V.INPUT_SIZE
-        self.T = V.TOKENS
+        self.size = size
+        self.T = V.tokens(size)
         self.np = self.T - 1
+        self.long = self.T > 256              # rollout by attn_ahat / rollout_chain (kernels/vit_long.hip)
+        if size != V.INPUT_SIZE:
+            self.model_name = f"vit_b16_{size}" + ("_fp8" if fp8 else "")
         self.ldr = (self.T + 3) // 4 * 4      # rollout only: row stride of the fp32 state R [max_batch, T, ldr]
         self._r_last = None                   # rollout only: the buffer the last layer's rollout step writes
         self.classes = params["heads.head.bias"].numel()
@@ -138,9 +147,13 @@ class ViTEngine(EngineBase):
         that crosses a stage cut comes out double-buffered by batch parity."""
         if not self.rollout:
             return
-        dst = f"R{i & 1}"
-        step = Step("rollout", f"{L}.rollout", src="QKV", res=self._r_last, dst=dst,
-                    extra=dict(Tq=1 if i == V.DEPTH - 1 else self.T))      # only row 0 of the last R is used
+        if self.long:     # its own buffer per layer: rollout_chain reads all of them behind the head
+            dst = f"AH{i}"
+            step = Step("ahat", f"{L}.ahat", src="QKV", dst=dst, extra=dict(Tq=1 if i == V.DEPTH - 1 else self.T))
+        else:
+            dst = f"R{i & 1}"
+            step = Step("rollout", f"{L}.rollout", src="QKV", res=self._r_last, dst=dst,
+                        extra=dict(Tq=1 if i == V.DEPTH - 1 else self.T))      # only row 0 of the last R is used
         # the fp8 layer is already complete: the step goes in behind its qkv step, in front of attention
         at = next((k for k in range(len(self.steps) - 1, -1, -1) if self.steps[k].name == f"{L}.qkv"), None)
         self.steps.insert(at + 1, step)
@@ -182,7 +195,7 @@ class ViTEngine(EngineBase):
             self.bufs.update({"Xn8": u8(B * T, D), "A8": u8(B * T, D), "Hd8": u8(B * T, V.MLP)})
             self.ld.update({"Xn8": D, "A8": D, "Hd8": V.MLP})
         if self.rollout:
-            for nm in ("R0", "R1"):
+            for nm in [f"AH{i}" for i in range(V.DEPTH)] if self.long else ("R0", "R1"):
                 self.bufs[nm] = torch.zeros((B, T, self.ldr), dtype=torch.float32, device=dev)
                 self.ld[nm] = self.ldr
         self.logits = torch.zeros((B, self.classes), dtype=torch.float32, device=dev)
@@ -198,13 +211,18 @@ class ViTEngine(EngineBase):
         lib = _lib.lib()
         if self.classes > lib.TOPK_MAX_NC:
             raise ValueError(f"rollout: {self.classes} classes exceed the top-1 kernel's {lib.TOPK_MAX_NC}")
-        if self.T > lib.ROLLOUT_MAX_T:
-            raise ValueError(f"rollout: {self.T} tokens exceed the kernel's {lib.ROLLOUT_MAX_T}")
+        if self.T > (lib.LONG_MAX_T if self.long else lib.ROLLOUT_MAX_T):
+            raise ValueError(f"rollout: {self.T} tokens exceed the kernels' {lib.LONG_MAX_T}")
         self.logit_slots = [self.logits]
         self.top1_slots = [torch.zeros((self.max_batch, 2), dtype=torch.float32, device=self.device)]
         self.logits = torch.zeros((self.max_batch, 2 + self.np), dtype=torch.float32, device=self.device)
         self.steps.append(Step("top1", "top1", src="logits"))
-        self.steps.append(Step("rollout_map", "rollout_map", src=self._r_last))
+        if self.long:     # src: the last layer's A^; extra["reads"]: the others (stages.plan_stages versions them too)
+            self.steps.append(Step("rollout_chain", "rollout_chain", src=self._r_last,
+                                   extra=dict(reads=[f"AH{i}" for i in range(V.DEPTH - 1)])))
+            self._chain_tables = []       # device pointer tables of the emitted rollout_chain launches
+        else:
+            self.steps.append(Step("rollout_map", "rollout_map", src=self._r_last))
         return self.size // V.PATCH, self.size // V.PATCH
 
     def _ptr(self, name: str) -> int:
@@ -232,8 +250,8 @@ class ViTEngine(EngineBase):
             return
         lay: ConvGemmLayer = step.layer
         if step.extra.get("kind") == "patch":
-            g = Geometry(b, V.INPUT_SIZE // V.PATCH, V.INPUT_SIZE // V.PATCH,
-                         V.INPUT_SIZE // V.PATCH, V.INPUT_SIZE // V.PATCH)
+            g = Geometry(b, self.size // V.PATCH, self.size // V.PATCH,
+                         self.size // V.PATCH, self.size // V.PATCH)
             opad = 2
         else:
             rows = b * self.T
@@ -281,6 +299,20 @@ class ViTEngine(EngineBase):
                                                   r_out=self._ptr(step.dst), B=b, T=self.T, Tq=step.extra["Tq"],
                                                   H=V.HEADS, dh=D // V.HEADS, scale=(D // V.HEADS) ** -0.5,
                                                   ldr=self.ldr))
+        elif step.kind == "ahat":
+            prog.add_attn_ahat(step.name, dict(qkv=self._ptr(step.src), out=self._ptr(step.dst), B=b, T=self.T,
+                                               Tq=step.extra["Tq"], H=V.HEADS, dh=D // V.HEADS,
+                                               scale=(D // V.HEADS) ** -0.5, ldr=self.ldr))
+        elif step.kind == "rollout_chain":
+            # the A^ buffers as this program sees them (a stage pipeline renames them by batch parity)
+            table = torch.tensor([self._ptr(nm) for nm in (*step.extra["reads"], step.src)], dtype=torch.int64,
+                                 device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+            self._chain_tables.append(table)
+            out = self._out_rows()
+            prog.add_rollout_chain(step.name, dict(ahat=_lib.ptr(table), top=_lib.ptr(self.top1_slot(self._slot)),
+                                                   out=_lib.ptr(out), B=b, T=self.T, L=V.DEPTH, ldr=self.ldr,
+                                                   ldo=out.shape[1]))
         elif step.kind == "rollout_map":
             out = self._out_rows()
             prog.add_rollout_map(step.name, dict(r=self._ptr(step.src), top=_lib.ptr(self.top1_slot(self._slot)),
@@ -293,4 +325,4 @@ class ViTEngine(EngineBase):
             raise ValueError(step.kind)
 
     def flops_per_image(self) -> float:
-        return 2.0 * V.macs_per_image()
+        return 2.0 * V.macs_per_image(self.size)

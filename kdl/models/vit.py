@@ -32,13 +32,21 @@ STD = (0.229, 0.224, 0.225)
 TOTAL_PARAMS = 86_567_656                     # torchvision vit_b_16
 
 
+def tokens(size: int = INPUT_SIZE) -> int:
+    """Class token + (size / 16)^2 patches: 197 at 224, 577 at 384 (``IMAGENET1K_SWAG_E2E_V1``). Every
+    function below takes ``size``; the default is the 224 model, whose results it leaves as they were."""
+    if size < PATCH or size % PATCH:
+        raise ValueError(f"ViT-B/16 input size {size} is not a positive multiple of {PATCH}")
+    return (size // PATCH) ** 2 + 1
+
+
 def _layer(i: int) -> str:
     return f"encoder.layers.encoder_layer_{i}"
 
 
-def param_shapes(num_classes: int = NUM_CLASSES) -> dict[str, tuple]:
+def param_shapes(num_classes: int = NUM_CLASSES, size: int = INPUT_SIZE) -> dict[str, tuple]:
     s = {"class_token": (1, 1, DIM), "conv_proj.weight": (DIM, 3, PATCH, PATCH), "conv_proj.bias": (DIM,),
-         "encoder.pos_embedding": (1, TOKENS, DIM)}
+         "encoder.pos_embedding": (1, tokens(size), DIM)}
     for i in range(DEPTH):
         L = _layer(i)
         s.update({f"{L}.ln_1.weight": (DIM,), f"{L}.ln_1.bias": (DIM,),
@@ -54,16 +62,16 @@ def param_shapes(num_classes: int = NUM_CLASSES) -> dict[str, tuple]:
     return s
 
 
-def count_params(num_classes: int = NUM_CLASSES) -> int:
-    return sum(math.prod(v) for v in param_shapes(num_classes).values())
+def count_params(num_classes: int = NUM_CLASSES, size: int = INPUT_SIZE) -> int:
+    return sum(math.prod(v) for v in param_shapes(num_classes, size).values())
 
 
-def init_params(seed: int = 0, num_classes: int = NUM_CLASSES) -> dict[str, torch.Tensor]:
+def init_params(seed: int = 0, num_classes: int = NUM_CLASSES, size: int = INPUT_SIZE) -> dict[str, torch.Tensor]:
     """Random init of the exact architecture (truncated-normal-like scales as in
     torchvision; LN gains 1, biases small so the residual stream keeps a sane scale)."""
     g = torch.Generator().manual_seed(seed)
     p = {}
-    for k, shp in param_shapes(num_classes).items():
+    for k, shp in param_shapes(num_classes, size).items():
         if k.endswith("ln_1.weight") or k.endswith("ln_2.weight") or k == "encoder.ln.weight":
             t = torch.ones(shp)
         elif k.endswith(".bias") and ("ln_" in k or k == "encoder.ln.bias"):
@@ -85,8 +93,11 @@ def preprocess(x_u8_nhwc: torch.Tensor) -> torch.Tensor:
     return (x - torch.tensor(MEAN, device=x.device).view(1, 3, 1, 1)) / torch.tensor(STD, device=x.device).view(1, 3, 1, 1)
 
 
-def embed(p, x_nchw):
+def embed(p, x_nchw, size: int = INPUT_SIZE):
     B = x_nchw.shape[0]
+    if tuple(x_nchw.shape[2:]) != (size, size) or p["encoder.pos_embedding"].shape[1] != tokens(size):
+        raise ValueError(f"ViT-B/16 at {size}: input {tuple(x_nchw.shape)}, position embedding "
+                         f"{tuple(p['encoder.pos_embedding'].shape)}")
     t = F.conv2d(x_nchw, p["conv_proj.weight"], p["conv_proj.bias"], stride=PATCH)   # [B, D, 14, 14]
     t = t.flatten(2).transpose(1, 2)                                                 # [B, 196, D]
     cls = p["class_token"].expand(B, -1, -1)
@@ -111,27 +122,27 @@ def encoder_layer(p, i, x):
 
 
 @torch.no_grad()
-def vit_features(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
-    """fp32 oracle: uint8 NHWC [B,224,224,3] -> the normalised class token [B,768] in front of heads.head."""
-    x = embed(p, preprocess(x_u8_nhwc))
+def vit_features(p, x_u8_nhwc: torch.Tensor, size: int = INPUT_SIZE) -> torch.Tensor:
+    """fp32 oracle: uint8 NHWC [B,size,size,3] -> the normalised class token [B,768] in front of heads.head."""
+    x = embed(p, preprocess(x_u8_nhwc), size)
     for i in range(DEPTH):
         x = encoder_layer(p, i, x)
     return F.layer_norm(x[:, 0], (DIM,), p["encoder.ln.weight"], p["encoder.ln.bias"], LN_EPS)
 
 
 @torch.no_grad()
-def vit_forward(p, x_u8_nhwc: torch.Tensor) -> torch.Tensor:
-    """fp32 oracle: uint8 NHWC [B,224,224,3] -> logits [B,1000]."""
-    return vit_features(p, x_u8_nhwc) @ p["heads.head.weight"].t() + p["heads.head.bias"]
+def vit_forward(p, x_u8_nhwc: torch.Tensor, size: int = INPUT_SIZE) -> torch.Tensor:
+    """fp32 oracle: uint8 NHWC [B,size,size,3] -> logits [B,1000]."""
+    return vit_features(p, x_u8_nhwc, size) @ p["heads.head.weight"].t() + p["heads.head.bias"]
 
 
 @torch.no_grad()
-def vit_rollout(p, x_u8_nhwc: torch.Tensor) -> tuple:
-    """fp32 oracle of the attention-rollout heatmap (Abnar & Zuidema 2020): uint8 NHWC [B,224,224,3] ->
-    (class int32 [B], softmax score fp32 [B], heat fp32 [B,14,14]). Per layer P_h = softmax(Q_h K_h^T /
+def vit_rollout(p, x_u8_nhwc: torch.Tensor, size: int = INPUT_SIZE) -> tuple:
+    """fp32 oracle of the attention-rollout heatmap (Abnar & Zuidema 2020): uint8 NHWC [B,size,size,3] ->
+    (class int32 [B], softmax score fp32 [B], heat fp32 [B,size/16,size/16]: 14 x 14 at 224). Per layer P_h = softmax(Q_h K_h^T /
     sqrt(dh)), A^ = (mean_h P_h + I) / 2 (rows sum to 1), R_1 = A^_1, R_l = A^_l R_(l-1); the map is row 0
     of R_12 without the class token's own column, divided by its largest value."""
-    x = embed(p, preprocess(x_u8_nhwc))
+    x = embed(p, preprocess(x_u8_nhwc), size)
     B, N, D = x.shape
     eye = torch.eye(N, dtype=x.dtype, device=x.device)
     r = None
@@ -148,17 +159,17 @@ def vit_rollout(p, x_u8_nhwc: torch.Tensor) -> tuple:
     cls = logits.argmax(dim=1)
     score = torch.softmax(logits, dim=1).gather(1, cls[:, None])[:, 0]
     heat = r[:, 0, 1:]
-    heat = (heat / heat.amax(dim=1, keepdim=True)).reshape(B, INPUT_SIZE // PATCH, INPUT_SIZE // PATCH)
+    heat = (heat / heat.amax(dim=1, keepdim=True)).reshape(B, size // PATCH, size // PATCH)
     return cls.to(torch.int32), score.float(), heat.float()
 
 
 @torch.no_grad()
-def activation_amax(p, x_u8_nhwc: torch.Tensor) -> list[dict[str, float]]:
+def activation_amax(p, x_u8_nhwc: torch.Tensor, size: int = INPUT_SIZE) -> list[dict[str, float]]:
     """Calibration for the fp8 engine: per encoder layer, the max |value| of the four
     tensors that feed fp8 GEMMs (ln_1 out -> QKV, attention out -> out_proj,
     ln_2 out -> mlp.0, GELU out -> mlp.3)."""
     out = []
-    x = embed(p, preprocess(x_u8_nhwc))
+    x = embed(p, preprocess(x_u8_nhwc), size)
     for i in range(DEPTH):
         L = _layer(i)
         h1 = F.layer_norm(x, (DIM,), p[f"{L}.ln_1.weight"], p[f"{L}.ln_1.bias"], LN_EPS)
@@ -175,7 +186,7 @@ def activation_amax(p, x_u8_nhwc: torch.Tensor) -> list[dict[str, float]]:
     return out
 
 
-def macs_per_image() -> int:
-    n = TOKENS
+def macs_per_image(size: int = INPUT_SIZE) -> int:
+    n = tokens(size)
     per_layer = n * DIM * 3 * DIM + 2 * n * n * DIM + n * DIM * DIM + 2 * n * DIM * MLP
     return (n - 1) * DIM * 3 * PATCH * PATCH + DEPTH * per_layer + DIM * NUM_CLASSES
