@@ -8,11 +8,13 @@
   make-synthetic <repo>/<version> [--seed] [--model xception|resnet50|vit_b16|efficientnet_b7]
                                              random-init weights of the exact architecture (Xception:
                                              a SavedModel; other families: torchvision-layout safetensors)
-  build-gallery <version_dir> <images_dir> [--device cpu|gpu]
+  build-gallery <version_dir> <images_dir> [--device cpu|gpu] [--ivf_lists L]
                                              the gallery of the similar signatures (serving/similar.py): every
                                              image file of <images_dir>, in sorted order, through the
                                              version's embed_bytes path with raw rows -> gallery.npy (fp32
-                                             [N, F]) + gallery_ids.txt (the file names) in <version_dir>
+                                             [N, F]) + gallery_ids.txt (the file names) in <version_dir>;
+                                             --ivf_lists L also writes the index files gallery_centroids.npy
+                                             and gallery_lists.npy (k-means into L lists, on the CPU)
   serve [server flags...]                    same as python -m kdl.serving
 """
 from __future__ import annotations
@@ -42,6 +44,7 @@ def main(argv=None) -> int:
     g.add_argument("images_dir")
     g.add_argument("--device", choices=["cpu", "gpu"], default="cpu")
     g.add_argument("--batch", type=int, default=8, help="images per forward")
+    g.add_argument("--ivf_lists", type=int, default=0, help="also write an inverted-file index of this many lists")
     sv = sub.add_parser("serve")
     sv.add_argument("rest", nargs=argparse.REMAINDER)
     a = ap.parse_args(argv)
@@ -87,19 +90,19 @@ def main(argv=None) -> int:
         write_savedmodel(a.dst, to_keras_variables(X.init_params(seed=a.seed), residual_offset=a.residual_offset))
         print(f"wrote synthetic SavedModel to {a.dst}")
     elif a.cmd == "build-gallery":
-        return build_gallery(Path(a.version_dir), Path(a.images_dir), a.device, a.batch)
+        return build_gallery(Path(a.version_dir), Path(a.images_dir), a.device, a.batch, a.ivf_lists)
     elif a.cmd == "serve":
         from .serving.server import main as serve_main
         return serve_main(a.rest)
     return 0
 
 
-def build_gallery(version_dir: Path, images_dir: Path, device: str = "cpu", batch: int = 8) -> int:
+def build_gallery(version_dir: Path, images_dir: Path, device: str = "cpu", batch: int = 8, ivf_lists: int = 0) -> int:
     import numpy as np
 
     from .serving.backend import Servable, load_version_dir, pick_devices
     from .serving.config import BatchingParams, ServerConfig
-    from .serving.similar import DEFAULT_GALLERY, IDS_FILE
+    from .serving.similar import CENTROIDS_FILE, DEFAULT_GALLERY, IDS_FILE, LISTS_FILE, build_ivf
     names = sorted(p.name for p in images_dir.iterdir() if p.is_file())
     if not names:
         print(f"no image files in {images_dir}", file=sys.stderr)
@@ -122,6 +125,12 @@ def build_gallery(version_dir: Path, images_dir: Path, device: str = "cpu", batc
     np.save(version_dir / DEFAULT_GALLERY, gal, allow_pickle=False)
     (version_dir / IDS_FILE).write_text("".join(n + "\n" for n in names))
     print(f"wrote {version_dir / DEFAULT_GALLERY} {list(gal.shape)} and {version_dir / IDS_FILE}")
+    if ivf_lists:
+        centroids, lists = build_ivf(gal, ivf_lists)
+        np.save(version_dir / CENTROIDS_FILE, centroids, allow_pickle=False)
+        np.save(version_dir / LISTS_FILE, lists, allow_pickle=False)
+        print(f"wrote {version_dir / CENTROIDS_FILE} {list(centroids.shape)} and {version_dir / LISTS_FILE}: "
+              'set "similar": {"index": "ivf"} in the version json to search through the index')
     return 0
 
 

@@ -222,6 +222,13 @@ GalleryTopkArgs gallery_topk_args(const py::dict& d) {
   a.B = I(d, "B"); a.N = I(d, "N"); a.F = I(d, "F"); a.K = I(d, "K"); a.ldq = I(d, "ldq"); a.ldg = I(d, "ldg");
   return a;
 }
+GalleryIvfArgs gallery_ivf_args(const py::dict& d) {
+  GalleryIvfArgs a{};
+  static_cast<GalleryTopkArgs&>(a) = gallery_topk_args(d);
+  a.probe = P<const int32_t>(d, "probe"); a.table = P<const int32_t>(d, "table");
+  a.L = I(d, "L"); a.P = I(d, "P"); a.C = I(d, "C"); a.ldp = I(d, "ldp");
+  return a;
+}
 ClassMapArgs class_map_args(const py::dict& d) {
   ClassMapArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.top = P<const int32_t>(d, "top"); a.w = P<const uint16_t>(d, "w");
@@ -436,6 +443,12 @@ PYBIND11_MODULE(_C, m) {
     chk(gallery_topk(a, S(s)), "gallery_topk");
   });
   m.def("gallery_topk_workspace", [](int B, int N, int K) { return gallery_topk_workspace(B, N, K); });
+  m.def("gallery_ivf_topk", [](py::dict d, uintptr_t s) {
+    const auto a = gallery_ivf_args(d);
+    py::gil_scoped_release nogil;
+    chk(gallery_ivf_topk(a, S(s)), "gallery_ivf_topk");
+  });
+  m.def("gallery_ivf_workspace", [](int B, int K, int L, int C) { return gallery_ivf_workspace(B, K, L, C); });
   m.def("class_map", [](py::dict d, uintptr_t s) {
     const auto a = class_map_args(d);
     py::gil_scoped_release nogil;
@@ -894,6 +907,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_gallery_topk", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GALLERY_TOPK; op.name = name; op.gt = gallery_topk_args(d); p.add(op);
+      })
+      .def("add_gallery_ivf_topk", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_GALLERY_IVF_TOPK; op.name = name; op.gi = gallery_ivf_args(d); p.add(op);
       })
       .def("add_gap", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GAP; op.name = name; op.gp = gap_args(d); p.add(op);

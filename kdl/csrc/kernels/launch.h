@@ -416,6 +416,43 @@ struct GalleryTopkArgs {
 size_t gallery_topk_workspace(int B, int N, int K);
 hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s);
 
+// Gallery search over an inverted-file index (kernels/similar_ivf.hip): the N stored bf16 rows are
+// grouped into L lists, a list being a run of consecutive rows, and each query is scored only
+// against the rows of the P lists named in its `probe` row. Per query the K best of those
+// candidates by gallery_topk's rule (score descending, row index ascending), in gallery_topk's
+// output layout; a query whose probed lists hold fewer than K rows gets index -1 and score -inf in
+// the missing places. Scores are the dense scan's, bit for bit: the same three bf16 terms per
+// query value, the same k order for every row, so the same bound
+// |score - exact| <= (F + 16) * 2^-23 * sum_i |q_i| * |g_ji| holds, equal rows give bit-equal
+// scores and replays are bit-identical.
+// `table` is the static chunk table, C entries of three int32 {list, first row, row count}, built
+// once on the host from the list offsets: every list is cut into chunks of at most kGalleryChunk
+// rows, C = sum_l ceil(len_l / kGalleryChunk), entries in ascending row order. The grid follows
+// the table, not the probes, so the op is captured into a graph with no host work per replay.
+// `probe` is [B][ldp] int32; the first P words of a row are the probed list ids (ids outside
+// 0..L-1 are ignored, repeated ids count once): the first P words of a gallery_topk output row
+// over the L centroids with K = P, ldp = 2P.
+// Four launches: the queries are split into their bf16 terms (per query, not per tile); a mask
+// launch writes for every (list, 32-query pass) the 32-bit set of the pass's queries that probe
+// the list, whole on every call; the scan runs one workgroup per table entry and pass: with an
+// empty mask it reads no gallery bytes and writes only a (-inf, no row) head per query, else it
+// packs the probing queries into one 16-query MFMA tile (two when more than 16 probe) and scans
+// its rows once for all of them; the merge is gallery_topk's, over C chunks.
+// A batch that probes overlapping lists reads each list once per 32 queries. Nothing is loaded past
+// a list's last row, row N - 1 or column F - 1; pad columns of q and g are not read; a table entry
+// outside [0, N) or with a list outside 0..L-1 is scanned for no query.
+// The conditions of GalleryTopkArgs for a bf16 gallery hold (g8 and scale null), and 1 <= L <=
+// kGalleryMaxN, 1 <= P <= min(L, kTopkMaxK), ldp >= P, 1 <= C <= kGalleryMaxN / kGalleryChunk + L,
+// probe and table 4-byte aligned and not null, work gallery_ivf_workspace(B, K, L, C) bytes;
+// anything else is hipErrorInvalidValue and nothing is launched.
+struct GalleryIvfArgs : GalleryTopkArgs {
+  const int32_t* probe;   // [B][ldp] probed list ids, P used per row
+  const int32_t* table;   // [C][3] {list, first row, row count <= kGalleryChunk}
+  int L, P, C, ldp;
+};
+size_t gallery_ivf_workspace(int B, int K, int L, int C);
+hipError_t gallery_ivf_topk(const GalleryIvfArgs& a, hipStream_t s);
+
 // Grad-CAM heatmaps (kernels/explain.hip): for each image the map of its predicted class,
 //   raw_p = (1/HW) sum_c d_c x[b][p][c],   d_c = dlogit_k / d(mean_p x[b][p][c]),   k = top[b][0],
 // with d in closed form for the two head kinds (no backward pass):

@@ -23,20 +23,47 @@ __host__ __device__ static inline size_t gallery_split_bytes(int B) {
   return (size_t)gallery_tiles(B) * kGalSteps * 3 * 64 * sizeof(u32x4);
 }
 
-// The K best of the chunk's rows for each of the pass's queries, from its score tile sc[query][row]
-// in LDS (complete: the caller has passed a barrier): wave w takes the queries w, w + 4, ...
-template <int QT>
-__device__ __forceinline__ void gallery_pick(const float (*sc)[GAL_LDS], const GalleryTopkArgs& a, int chunks,
-                                             int chunk, int b0, int lane, int wave) {
+// The three bf16 terms (hi, the rounded remainder, the rounded remainder of that) of the 8 query
+// values q[b][k .. k + 7], zeros for a query >= B or a column >= F (F % 8 == 0: the 8 are in or out)
+template <bool QV>
+__device__ __forceinline__ void gallery_split_terms(const GalleryTopkArgs& a, int b, int k, u32x4& hi, u32x4& mid,
+                                                    u32x4& lo) {
+  float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (b < a.B && k < a.F) {
+    const float* p = a.q + (long)b * a.ldq + k;
+    if (QV) {
+      const float4 v0 = *(const float4*)p, v1 = *(const float4*)(p + 4);
+      x[0] = v0.x; x[1] = v0.y; x[2] = v0.z; x[3] = v0.w; x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = p[j];
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const float x0 = x[2 * d], x1 = x[2 * d + 1];
+    hi[d] = pack_bf16(x0, x1);
+    const float r0 = x0 - bf_lo(hi[d]), r1 = x1 - bf_hi(hi[d]);       // exact
+    mid[d] = pack_bf16(r0, r1);
+    lo[d] = pack_bf16(r0 - bf_lo(mid[d]), r1 - bf_hi(mid[d]));        // exact, then <= 8 bits left
+  }
+}
+
+// The K best of the rows [base, end) of a chunk (at most kGalleryChunk of them) for each of `slots`
+// score rows of its tile sc[slot][row - base] in LDS (complete: the caller has passed a barrier);
+// slot ql belongs to query query_of(ql). Wave w takes the slots w, w + 4, ...
+template <class Q>
+__device__ __forceinline__ void gallery_pick_rows(const float (*sc)[GAL_LDS], const GalleryTopkArgs& a, int chunks,
+                                                  int chunk, int base, int end, int slots, int lane, int wave,
+                                                  Q query_of) {
   constexpr int R = kGalleryChunk / 64;
-  const int base = chunk * kGalleryChunk;
-  for (int ql = wave; ql < 16 * QT && b0 + ql < a.B; ql += GAL_WAVES) {
+  for (int ql = wave; ql < slots; ql += GAL_WAVES) {
     float v[R];
-    unsigned taken = 0;                       // bit r: row is past N or already picked
+    unsigned taken = 0;                       // bit r: row is past the end or already picked
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       v[r] = sc[ql][r * 64 + lane];
-      if (base + r * 64 + lane >= a.N) taken |= 1u << r;
+      if (base + r * 64 + lane >= end) taken |= 1u << r;
     }
     float myv = -INFINITY;
     int myi = INT_MAX;
@@ -53,13 +80,24 @@ __device__ __forceinline__ void gallery_pick(const float (*sc)[GAL_LDS], const G
       if (lane == k) { myv = bv; myi = bi; }
     }
     if (lane < a.K) {
-      GalCand* w = (GalCand*)((char*)a.work + gallery_split_bytes(a.B)) + ((long)(b0 + ql) * a.K + lane) * chunks + chunk;
+      GalCand* w = (GalCand*)((char*)a.work + gallery_split_bytes(a.B)) + ((long)query_of(ql) * a.K + lane) * chunks + chunk;
       *w = GalCand{myv, myi};
     }
   }
 }
 
+// The dense scans' pick: chunk c holds the rows from c * kGalleryChunk on, slot ql is query b0 + ql
+template <int QT>
+__device__ __forceinline__ void gallery_pick(const float (*sc)[GAL_LDS], const GalleryTopkArgs& a, int chunks,
+                                             int chunk, int b0, int lane, int wave) {
+  gallery_pick_rows(sc, a, chunks, chunk, chunk * kGalleryChunk, a.N, min(16 * QT, a.B - b0), lane, wave,
+                    [b0](int ql) { return b0 + ql; });
+}
+
 // the scan of an fp8 gallery (similar_f8.hip), between gallery_topk's split and merge launches
 void gallery_scan_f8(const GalleryTopkArgs& a, int chunks, hipStream_t s);
+// gallery_topk's last launch (similar.hip), one wave per query over `chunks` candidate lists;
+// `missing`: a place that no candidate fills is written as index -1 (the dense op always has K)
+void gallery_merge(const GalleryTopkArgs& a, int chunks, bool missing, hipStream_t s);
 
 }  // namespace kdl

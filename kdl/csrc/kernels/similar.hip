@@ -41,26 +41,8 @@ template <bool QV>
 __global__ __launch_bounds__(64) void gallery_split_kernel(GalleryTopkArgs a) {
   const int lane = threadIdx.x, l15 = lane & 15, kg = lane >> 4;
   const int b = blockIdx.y * 16 + l15, k = blockIdx.x * 32 + 8 * kg;
-  float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (b < a.B && k < a.F) {                          // F % 8 == 0: a lane's 8 columns are in or out
-    const float* p = a.q + (long)b * a.ldq + k;
-    if (QV) {
-      const float4 v0 = *(const float4*)p, v1 = *(const float4*)(p + 4);
-      x[0] = v0.x; x[1] = v0.y; x[2] = v0.z; x[3] = v0.w; x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = p[j];
-    }
-  }
   u32x4 hi, mid, lo;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const float x0 = x[2 * d], x1 = x[2 * d + 1];
-    hi[d] = pack_bf16(x0, x1);
-    const float r0 = x0 - bf_lo(hi[d]), r1 = x1 - bf_hi(hi[d]);       // exact
-    mid[d] = pack_bf16(r0, r1);
-    lo[d] = pack_bf16(r0 - bf_lo(mid[d]), r1 - bf_hi(mid[d]));        // exact, then <= 8 bits left
-  }
+  gallery_split_terms<QV>(a, b, k, hi, mid, lo);
   u32x4* w = (u32x4*)a.work + ((long)blockIdx.y * kGalSteps + blockIdx.x) * 3 * 64 + lane;
   w[0] = hi; w[64] = mid; w[128] = lo;
 }
@@ -136,6 +118,8 @@ __global__ __launch_bounds__(64 * GAL_WAVES) void gallery_scan_kernel(GalleryTop
   gallery_pick<QT>(sc, a, chunks, chunk, b0, lane, wave);
 }
 
+// MISSING: a place that no candidate fills (gallery_ivf_topk: fewer than K rows probed) is index -1
+template <bool MISSING>
 __global__ __launch_bounds__(64) void gallery_merge_kernel(GalleryTopkArgs a, int chunks) {
   const int lane = threadIdx.x, b = blockIdx.x;
   const GalCand* w = (const GalCand*)((const char*)a.work + gallery_split_bytes(a.B)) + (long)b * a.K * chunks;   // [K][chunks]
@@ -168,9 +152,14 @@ __global__ __launch_bounds__(64) void gallery_merge_kernel(GalleryTopkArgs a, in
   }
   if (lane < a.K) {
     int32_t* o = a.out + (long)b * 2 * a.K;
-    o[lane] = myi;
+    o[lane] = MISSING && myi == INT_MAX ? -1 : myi;
     reinterpret_cast<float*>(o)[a.K + lane] = myv;
   }
+}
+
+void gallery_merge(const GalleryTopkArgs& a, int chunks, bool missing, hipStream_t s) {
+  if (missing) hipLaunchKernelGGL(gallery_merge_kernel<true>, dim3(a.B), dim3(64), 0, s, a, chunks);
+  else hipLaunchKernelGGL(gallery_merge_kernel<false>, dim3(a.B), dim3(64), 0, s, a, chunks);
 }
 
 static int gallery_chunks(int N) { return (N + kGalleryChunk - 1) / kGalleryChunk; }
@@ -198,7 +187,7 @@ hipError_t gallery_topk(const GalleryTopkArgs& a, hipStream_t s) {
   if (f8) gallery_scan_f8(a, chunks, s);
   else if (a.B <= 16) hipLaunchKernelGGL(gallery_scan_kernel<1>, grid, dim3(64 * GAL_WAVES), 0, s, a, chunks);
   else hipLaunchKernelGGL(gallery_scan_kernel<2>, grid, dim3(64 * GAL_WAVES), 0, s, a, chunks);
-  hipLaunchKernelGGL(gallery_merge_kernel, dim3(a.B), dim3(64), 0, s, a, chunks);
+  gallery_merge(a, chunks, false, s);
   return hipGetLastError();
 }
 

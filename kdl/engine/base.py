@@ -15,6 +15,7 @@ import json
 from dataclasses import dataclass, field
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from ..ops import _lib
@@ -270,6 +271,20 @@ SIMILAR_METRICS = ("cosine", "dot")
 
 
 @dataclass
+class Ivf:
+    """An inverted-file index over a ``Similar`` gallery whose rows are stored list by list
+    (``kdl.serving.similar.load_ivf``): ``centroids`` the device tensor [L, ldc] of bf16 centroid rows,
+    laid out like the gallery; ``offsets`` int32 [L + 1] (any device), list l being the rows
+    offsets[l] .. offsets[l + 1] - 1; ``chunk_table`` the device tensor int32 [C, 3] that
+    ``kdl.serving.similar.chunk_table(offsets)`` gives; ``nprobe`` lists scanned per image,
+    1 <= nprobe <= min(L, 32). Shared per device like the gallery."""
+    centroids: torch.Tensor
+    chunk_table: torch.Tensor
+    offsets: torch.Tensor
+    nprobe: int = 8
+
+
+@dataclass
 class Similar:
     """Gallery search outputs of an engine (``EngineBase(similar=...)``). ``gallery`` is the device
     tensor [N, ldg] of stored bf16 rows (``kdl.serving.similar.load_gallery``'s values), ldg a
@@ -277,11 +292,15 @@ class Similar:
     from this object reads the same copy. ``k`` neighbours per image (clipped to N); ``metric``
     "cosine" normalises the query rows (the stored rows are already unit length), "dot" does not.
     With ``scale``, an fp32 [N] tensor on the same device, the gallery is fp8: uint8 e4m3 codes
-    [N, ldg] (``load_gallery_fp8``'s), ldg and F multiples of 16, scored as scale[j] * sum_i q_i * val(code_ji)."""
+    [N, ldg] (``load_gallery_fp8``'s), ldg and F multiples of 16, scored as scale[j] * sum_i q_i * val(code_ji).
+    With ``ivf`` (bf16 galleries only) each image is scored against the rows of its ``nprobe`` nearest
+    lists instead of all rows (``kdl.serving.similar.ivf_rule``); places that those lists cannot fill
+    are index -1 with score -inf."""
     gallery: torch.Tensor
     k: int = 5
     metric: str = "cosine"
     scale: torch.Tensor | None = None
+    ivf: Ivf | None = None
 
 
 @dataclass(frozen=True)
@@ -430,6 +449,7 @@ class EngineBase:
         self.similar: Similar | None = similar
         self.feature_slots: list[torch.Tensor] = []   # similar only: per-slot fp32 features [max_batch, F]
         self._similar_work: list[torch.Tensor] = []   # similar only: per-slot gallery_topk workspace
+        self._probe_slots: list[tuple] = []           # similar with an index: per-slot (probe rows, coarse workspace)
         # Grad-CAM outputs: False = the output is the fp32 logits; True = two more steps write the
         # predicted class, its score and the class's heatmap over the last feature map (_enable_explain)
         self.explain = bool(explain)
@@ -633,12 +653,40 @@ class EngineBase:
         self.similar_k = min(int(sim.k), g.shape[0])
         if self.similar_k > lib.TOPK_MAX_K:
             raise ValueError(f"similar: k must be <= {lib.TOPK_MAX_K}, got {self.similar_k}")
+        if sim.ivf is not None:
+            self._check_ivf(sim, F)
         self.logit_slots = [self.logits]
         self.feature_slots = [torch.zeros((self.max_batch, F), dtype=torch.float32, device=self.device)]
         self.logits = torch.zeros((self.max_batch, 2 * self.similar_k), dtype=torch.float32, device=self.device)
         self._embed_step = Step("embed", "embed_rows", src=src)
         self.steps.append(self._embed_step)
         self.steps.append(Step("similar", "similar", src="features"))
+
+    def _check_ivf(self, sim: Similar, F: int) -> None:
+        """ValueError unless ``sim.ivf`` describes ``sim.gallery``: the chunk table is compared, once,
+        with the one its offsets give, so the scan never sees a row range of the host's making."""
+        from ..serving.similar import chunk_table
+        lib, ivf, g = _lib.lib(), sim.ivf, sim.gallery
+        if sim.scale is not None:
+            raise ValueError("similar: an fp8 gallery cannot have an index")
+        c, off, tab = ivf.centroids, ivf.offsets, ivf.chunk_table
+        if (c.dim() != 2 or c.dtype != torch.bfloat16 or not self._on_device(c) or not c.is_contiguous()
+                or c.shape[1] < F or c.shape[1] % 8 or not 1 <= c.shape[0] <= lib.GALLERY_MAX_N):
+            raise ValueError(f"similar: the centroids of an index must be a contiguous bf16 [L, >= {F}] tensor on "
+                             f"{self.device} with a row stride that is a multiple of 8, got {tuple(c.shape)} {c.dtype} "
+                             f"on {c.device}")
+        L = c.shape[0]
+        o = off.detach().cpu().numpy() if off.dtype == torch.int32 and off.shape == (L + 1,) else None
+        if o is None or o[0] != 0 or o[-1] != g.shape[0] or (np.diff(o) < 0).any():
+            raise ValueError(f"similar: the offsets of an index must be int32 [{L + 1}], ascending from 0 to the "
+                             f"gallery's {g.shape[0]} rows")
+        want = chunk_table(o)
+        if (tab.dtype != torch.int32 or not self._on_device(tab) or not tab.is_contiguous()
+                or tuple(tab.shape) != want.shape or not np.array_equal(tab.cpu().numpy(), want)):
+            raise ValueError("similar: the chunk table of an index must be the int32 [C, 3] tensor on "
+                             f"{self.device} that kdl.serving.similar.chunk_table(offsets) gives")
+        if not isinstance(ivf.nprobe, int) or not 1 <= ivf.nprobe <= min(L, lib.TOPK_MAX_K):
+            raise ValueError(f"similar: nprobe must be in 1..{min(L, lib.TOPK_MAX_K)}, got {ivf.nprobe!r}")
 
     def _on_device(self, t: torch.Tensor) -> bool:
         d = self.device
@@ -651,14 +699,40 @@ class EngineBase:
         return self.feature_slots[slot]
 
     def _similar_workspace(self, slot: int) -> torch.Tensor:
+        lib, ivf = _lib.lib(), self.similar.ivf
         while len(self._similar_work) <= slot:
-            n = _lib.lib().gallery_topk_workspace(self.max_batch, self.similar.gallery.shape[0], self.similar_k)
+            if ivf is None:
+                n = lib.gallery_topk_workspace(self.max_batch, self.similar.gallery.shape[0], self.similar_k)
+            else:
+                n = lib.gallery_ivf_workspace(self.max_batch, self.similar_k, ivf.centroids.shape[0],
+                                              ivf.chunk_table.shape[0])
             self._similar_work.append(torch.zeros(n, dtype=torch.uint8, device=self.device))
         return self._similar_work[slot]
 
+    def _probe_slot(self, slot: int) -> tuple:
+        """Per slot of an indexed engine: the coarse stage's output rows [max_batch, 2 * nprobe] int32
+        (the probed lists, then their scores) and its gallery_topk workspace."""
+        ivf = self.similar.ivf
+        while len(self._probe_slots) <= slot:
+            n = _lib.lib().gallery_topk_workspace(self.max_batch, ivf.centroids.shape[0], ivf.nprobe)
+            self._probe_slots.append((torch.zeros((self.max_batch, 2 * ivf.nprobe), dtype=torch.int32, device=self.device),
+                                      torch.zeros(n, dtype=torch.uint8, device=self.device)))
+        return self._probe_slots[slot]
+
     def _emit_similar(self, prog, step: Step, b: int) -> None:
         g, feat, out = self.similar.gallery, self.feature_slot(self._slot), self._out_rows()
-        sc = self.similar.scale
+        sc, ivf = self.similar.scale, self.similar.ivf
+        if ivf is not None:        # the nprobe nearest centroids of each image, then the rows of those lists
+            c, (probe, cwork) = ivf.centroids, self._probe_slot(self._slot)
+            prog.add_gallery_topk(step.name + "_probe", dict(
+                q=_lib.ptr(feat), g=_lib.ptr(c), out=_lib.ptr(probe), work=_lib.ptr(cwork), B=b, N=c.shape[0],
+                F=feat.shape[1], K=ivf.nprobe, ldq=feat.shape[1], ldg=c.shape[1]))
+            prog.add_gallery_ivf_topk(step.name, dict(
+                q=_lib.ptr(feat), g=_lib.ptr(g), out=_lib.ptr(out), work=_lib.ptr(self._similar_workspace(self._slot)),
+                B=b, N=g.shape[0], F=feat.shape[1], K=self.similar_k, ldq=feat.shape[1], ldg=g.shape[1],
+                probe=_lib.ptr(probe), table=_lib.ptr(ivf.chunk_table), L=c.shape[0], P=ivf.nprobe,
+                C=ivf.chunk_table.shape[0], ldp=probe.shape[1]))
+            return
         gal = dict(g=_lib.ptr(g)) if sc is None else dict(g8=_lib.ptr(g), scale=_lib.ptr(sc))
         prog.add_gallery_topk(step.name, dict(q=_lib.ptr(feat), out=_lib.ptr(out), **gal,
                                               work=_lib.ptr(self._similar_workspace(self._slot)), B=b,

@@ -117,6 +117,9 @@ class ModelSource:
     gallery: np.ndarray | None = None
     similar_dtype: str = "bf16"
     gallery_scale: np.ndarray | None = None
+    # the version's inverted-file index (serving/similar.py IvfIndex; None = every row is scanned);
+    # with one, gallery and gallery_ids are in its stored order
+    gallery_ivf: object = None
     gallery_ids: list = field(default_factory=list)
     similar_k: int = 0
     similar_metric: str = "cosine"
@@ -157,6 +160,7 @@ def _family_source(family: str, params: dict | None, seed: int, origin: str) -> 
 def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
                      classify_top_k: int | None = None, embedding_normalize: str | None = None,
                      similar_top_k: int | None = None, similar_dtype: str | None = None, gallery: bool = True,
+                     similar_nprobe: int | None = None,
                      overlay_colormap: str | None = None, overlay_alpha: float | None = None,
                      overlay_jpeg_quality: int | None = None, palette_colors: int | None = None,
                      locate_boxes: int | None = None, cutout_gate: int | None = None,
@@ -167,7 +171,8 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     (the server's --classify_top_k) overrides the version's classify K (serving/classify.py),
     ``embedding_normalize`` (--embedding_normalize) its embedding normalisation (serving/embed.py),
     ``similar_top_k`` (--similar_top_k) the K of its gallery search (serving/similar.py) and
-    ``similar_dtype`` (--similar_dtype) how its gallery is stored;
+    ``similar_dtype`` (--similar_dtype) how its gallery is stored, ``similar_nprobe`` (--similar_nprobe) how
+    many lists of its index a query probes;
     ``gallery=False`` leaves the version's gallery files alone (the tool that writes them);
     ``overlay_colormap`` / ``overlay_alpha`` (--overlay_colormap, --overlay_alpha) override the
     version's "overlay" block (serving/overlay.py); ``overlay_jpeg_quality`` (--overlay_jpeg_quality) turns
@@ -193,7 +198,7 @@ def load_version_dir(path: Path, synthetic: bool = False, preprocess: str = "",
     classify.add_signatures(src, path, classify_top_k)
     embed.add_signatures(src, path, embedding_normalize)
     if gallery:
-        similar.add_signatures(src, path, similar_top_k, similar_dtype)
+        similar.add_signatures(src, path, similar_top_k, similar_dtype, similar_nprobe)
     explain.add_signatures(src, path)
     rollout.add_signatures(src, path)
     overlay.add_signatures(src, path, overlay_colormap, overlay_alpha)

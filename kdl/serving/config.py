@@ -101,6 +101,9 @@ class ServerConfig:
     # how the gallery of the similar signatures is stored on the device: "bf16" or "fp8" (e4m3 codes
     # and a scale per row: half the bytes); None = the version's own "similar": {"dtype": ...}, else bf16
     similar_dtype: str | None = None
+    # lists a query probes in a version's gallery index (serving/similar.py); None = the version's own
+    # "similar": {"nprobe": ...}, else 8. 1..min(lists, 32); ignored by a version without an index
+    similar_nprobe: int | None = None
     # colour table and strength of the overlay signatures (serving/overlay.py); None = the model
     # version's own "overlay": {"colormap": ..., "alpha": ...}, else jet and 0.5
     overlay_colormap: str | None = None
@@ -257,6 +260,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="gallery items and scores per image of the similar / similar_image / similar_bytes "
                          "signatures (1..32, clipped to the gallery's row count); overrides the model version's "
                          "\"similar\": {\"top_k\": K} (env KDL_SIMILAR_TOP_K, default: the version's, else 5)")
+    ap.add_argument("--similar_nprobe", type=int, default=None,
+                    help="lists of a version's gallery index (\"similar\": {\"index\": \"ivf\"}) that each image "
+                         "probes, 1..min(lists, 32); overrides the version's \"similar\": {\"nprobe\": ...} "
+                         "(env KDL_SIMILAR_NPROBE, default: the version's, else 8)")
     ap.add_argument("--similar_dtype", choices=["bf16", "fp8"], default=None,
                     help="how the gallery of the similar signatures is stored: bf16, or fp8 = e4m3 codes and one "
                          "scale per row, half the bytes per scan; overrides the model version's "
@@ -328,6 +335,8 @@ def config_from_args(argv=None, env=None) -> ServerConfig:
                         similar_top_k=(a.similar_top_k if a.similar_top_k is not None
                                        else int(env["KDL_SIMILAR_TOP_K"]) if env.get("KDL_SIMILAR_TOP_K") else None),
                         similar_dtype=similar_dtype,
+                        similar_nprobe=(a.similar_nprobe if a.similar_nprobe is not None
+                                        else int(env["KDL_SIMILAR_NPROBE"]) if env.get("KDL_SIMILAR_NPROBE") else None),
                         overlay_colormap=a.overlay_colormap or env.get("KDL_OVERLAY_COLORMAP") or None,
                         overlay_alpha=(a.overlay_alpha if a.overlay_alpha is not None
                                        else float(env["KDL_OVERLAY_ALPHA"]) if env.get("KDL_OVERLAY_ALPHA") else None),

@@ -39,7 +39,8 @@ def latest_version_source(cfg: ServerConfig):
         raise FileNotFoundError(f"no versions under {base} (use --synthetic_model for random weights)")
     return load_version_dir(base / str(versions[-1]), synthetic=cfg.synthetic, preprocess=cfg.preprocess,
                             classify_top_k=cfg.classify_top_k, embedding_normalize=cfg.embedding_normalize,
-                            similar_top_k=cfg.similar_top_k, similar_dtype=cfg.similar_dtype, overlay_colormap=cfg.overlay_colormap,
+                            similar_top_k=cfg.similar_top_k, similar_dtype=cfg.similar_dtype, similar_nprobe=cfg.similar_nprobe,
+                            overlay_colormap=cfg.overlay_colormap,
                             overlay_alpha=cfg.overlay_alpha, overlay_jpeg_quality=cfg.overlay_jpeg_quality,
                             palette_colors=cfg.palette_colors, locate_boxes=cfg.locate_boxes,
                             cutout_gate=cfg.cutout_gate, cutout_png=cfg.cutout_png)
@@ -82,6 +83,7 @@ class ModelManager:
                                    classify_top_k=self.cfg.classify_top_k,
                                    embedding_normalize=self.cfg.embedding_normalize,
                                    similar_top_k=self.cfg.similar_top_k, similar_dtype=self.cfg.similar_dtype,
+                                   similar_nprobe=self.cfg.similar_nprobe,
                                    overlay_colormap=self.cfg.overlay_colormap, overlay_alpha=self.cfg.overlay_alpha,
                                    overlay_jpeg_quality=self.cfg.overlay_jpeg_quality,
                                    palette_colors=self.cfg.palette_colors,

@@ -45,7 +45,7 @@ NATIVE_INPUT_KEY = "images"
 def _similar_kw(sig, src, dev) -> dict:
     from ..engine.base import Similar
     return dict(similar=Similar(similar.device_gallery(src, dev), sig.top_k, src.similar_metric,
-                                similar.device_scale(src, dev)))
+                                similar.device_scale(src, dev), similar.device_ivf(src, dev)))
 
 
 def _map_kw(sig, src, dev) -> dict:
@@ -284,8 +284,7 @@ KINDS = {k.name: k for k in (
     Kind("similar", similar.SIMILAR_SIGNATURES, "kdl_similar_total",
          engine=_similar_kw, gpu_words=lambda sig, src: 2 * sig.top_k,
          host_words=lambda sig, src: src.gallery.shape[1], cpu_rows=_feature_rows,
-         host_step=lambda sig, src, rows: classify.pack_rows(
-             *similar.similar_rule(rows, src.gallery, sig.top_k, src.similar_metric, src.gallery_scale)),
+         host_step=lambda sig, src, rows: classify.pack_rows(*similar.rule_rows(src, rows, sig.top_k)),
          columns=_ranked(similar.ids_of)),
     Kind("explain", explain.EXPLAIN_SIGNATURES, "kdl_explain_total", **_MAP),
     Kind("attention", rollout.ATTENTION_SIGNATURES, "kdl_attention_total", **_MAP),

@@ -16,6 +16,14 @@ unquantised rows its ranking keeps, 2 is left out, and 3 pairs a bf16-gallery ``
 with an fp8-gallery one. ``--embed-recall N`` adds the same count on a gallery of N Xception embed
 rows with planted near-duplicates, for an fp8 and a bf16 gallery.
 
+``--ivf L,nprobe`` (profiles/similar_ivf.txt) times the indexed search instead (kernels/similar_ivf.hip:
+the coarse gallery_topk over L centroids, then gallery_ivf_topk over the rows of nprobe lists) against
+the dense bf16 op on the same stored rows as interleaved pairs, on clustered rows (unit centres plus
+noise) and on unit-norm random rows, the worst case for any index; it prints the share of chunks and
+rows a call reads and the recall of the float64 dense top-K at nprobe 1, 4, 8, 16, 32, and 3 pairs a
+dense ``similar`` engine with an indexed one. The index is two rounds of spherical k-means on the
+device, in this tool only: the product builds its index on the CPU (``build-gallery --ivf_lists``).
+
 Each time is the median of ``--repeats`` windows of ``--iters`` calls between two device events,
 after warm-up calls of the same shapes."""
 from __future__ import annotations
@@ -144,6 +152,103 @@ def op_rows(n: int, iters: int, repeats: int, say) -> None:
     del gals, gf
 
 
+def ivf_gallery(n: int, lists: int, kind: str, seed: int):
+    """(stored bf16 rows [n, F] list by list, bf16 centroids [lists, F], offsets int32 numpy [lists + 1], B queries):
+    "random" unit rows and queries, or "clustered": a unit centre per list plus noise of the same length
+    in all, queries made the same way. Lists come from two rounds of spherical k-means from the first rows."""
+    import numpy as np
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    unit = torch.nn.functional.normalize
+    centres = unit(torch.randn((lists, F), generator=g, device="cuda"), dim=1)
+
+    def rows(m: int) -> torch.Tensor:
+        x = torch.randn((m, F), generator=g, device="cuda")
+        if kind == "clustered":
+            x = centres[torch.randint(0, lists, (m,), generator=g, device="cuda")] + x / F ** 0.5
+        return unit(x, dim=1)
+    gal = torch.cat([rows(min(65536, n - lo)).to(torch.bfloat16) for lo in range(0, n, 65536)])
+    c = gal[:lists].clone()
+    assign = lambda: torch.cat([(gal[lo:lo + 65536] @ c.T).argmax(dim=1) for lo in range(0, n, 65536)])
+    for _ in range(2):
+        a = assign()
+        sums = torch.zeros((lists, F), device="cuda")
+        for lo in range(0, n, 65536):
+            sums.index_add_(0, a[lo:lo + 65536], gal[lo:lo + 65536].float())
+        c = torch.where(sums.norm(dim=1, keepdim=True) > 0, unit(sums, dim=1), c.float()).to(torch.bfloat16)
+    a = assign()
+    order = torch.argsort(a, stable=True)
+    offsets = np.concatenate([[0], np.cumsum(torch.bincount(a, minlength=lists).cpu().numpy())]).astype(np.int32)
+    return gal[order].contiguous(), c.contiguous(), offsets, rows(B).float().contiguous()
+
+
+def ivf_rows(n: int, lists: int, nprobe: int, kind: str, iters: int, repeats: int, pairs: int, say) -> None:
+    import numpy as np
+
+    from kdl.ops import _lib
+    from kdl.serving.similar import chunk_table
+    lib = _lib.lib()
+    gal, cen, offsets, q = ivf_gallery(n, lists, kind, 17)
+    table = torch.from_numpy(chunk_table(offsets)).cuda()
+    C = table.shape[0]
+    lens = np.diff(offsets)
+    say(f"N={n:8d} L={lists} {kind}: {C} chunks (dense: {-(-n // 256)}), list length min {lens.min()} median "
+        f"{int(np.median(lens))} max {lens.max()}, empty lists {int((lens == 0).sum())}")
+    out = torch.zeros((B, 2 * K), dtype=torch.int32, device="cuda")
+    dwork = torch.zeros(lib.gallery_topk_workspace(B, n, K), dtype=torch.uint8, device="cuda")
+    cwork = torch.zeros(lib.gallery_topk_workspace(B, lists, 32), dtype=torch.uint8, device="cuda")
+    iwork = torch.zeros(lib.gallery_ivf_workspace(B, K, lists, C), dtype=torch.uint8, device="cuda")
+    probe = torch.zeros((B, 64), dtype=torch.int32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    base = dict(q=q.data_ptr(), B=B, F=F, ldq=F, ldg=F)
+
+    def dense(i=0):
+        lib.gallery_topk(dict(base, g=gal.data_ptr(), out=out.data_ptr(), work=dwork.data_ptr(), N=n, K=K), s)
+
+    def coarse(p):
+        lib.gallery_topk(dict(base, g=cen.data_ptr(), out=probe.data_ptr(), work=cwork.data_ptr(), N=lists, K=p), s)
+
+    def scan(p):
+        lib.gallery_ivf_topk(dict(base, g=gal.data_ptr(), out=out.data_ptr(), work=iwork.data_ptr(), N=n, K=K,
+                                  probe=probe.data_ptr(), table=table.data_ptr(), L=lists, P=p, C=C, ldp=2 * p), s)
+
+    def indexed(i=0, p=nprobe):
+        coarse(p)
+        scan(p)
+    it = max(5, min(iters, (64 << 30) // (n * F * 2)))
+    ratios = []
+    for i in range(pairs):
+        order = (dense, indexed) if i % 2 == 0 else (indexed, dense)
+        t = {fn: window(fn, it, repeats)[0] for fn in order}
+        ratios.append(t[dense] / t[indexed])
+        say(f"N={n:8d} L={lists} nprobe={nprobe} {kind} pair {i}: dense gallery_topk {t[dense]:8.1f} us  "
+            f"coarse + gallery_ivf_topk {t[indexed]:8.1f} us  dense / indexed {ratios[-1]:.2f}")
+    tc, ts = window(lambda i: coarse(nprobe), it, repeats)[0], window(lambda i: scan(nprobe), it, repeats)[0]
+    say(f"N={n:8d} L={lists} nprobe={nprobe} {kind}: median dense / indexed {statistics.median(ratios):.2f}; alone: "
+        f"coarse gallery_topk {tc:.1f} us, gallery_ivf_topk {ts:.1f} us")
+    ref = torch.cat([q.double() @ gal[lo:lo + 65536].double().T for lo in range(0, n, 65536)], dim=1).topk(K).indices.cpu()
+    tab = table.cpu().numpy()
+    for p in (1, 4, 8, 16, 32):
+        if p > lists:
+            continue
+        indexed(0, p)
+        torch.cuda.synchronize()
+        mine = out[:, :K].cpu()
+        hit = np.zeros(lists, bool)
+        hit[probe.flatten()[:B * 2 * p].view(B, 2 * p)[:, :p].cpu().numpy().ravel()] = True      # rows of 2p words
+        kept = sum(len(set(mine[b].tolist()) & set(ref[b].tolist())) for b in range(B))
+        say(f"N={n:8d} L={lists} {kind} nprobe={p:2d}: recall of the float64 dense top-{K} {kept}/{B * K}; chunks read "
+            f"{int(hit[tab[:, 0]].sum())}/{C} ({100 * hit[tab[:, 0]].mean():.2f} %), rows read {int(lens[hit].sum())}/{n} "
+            f"({100 * lens[hit].sum() / n:.2f} %)")
+
+
+def ivf_engine_pairs(n: int, lists: int, nprobe: int, pairs: int, say) -> None:
+    from kdl.engine.base import Ivf, Similar
+    from kdl.serving.similar import chunk_table
+    gal, cen, offsets, _ = ivf_gallery(n, lists, "clustered", 5)
+    ivf = Ivf(cen, torch.from_numpy(chunk_table(offsets)).cuda(), torch.from_numpy(offsets), nprobe)
+    engine_pairs(n, pairs, say, sims={"dense": Similar(gal, K, "cosine"), "ivf": Similar(gal, K, "cosine", None, ivf)})
+
+
 def embed_recall(n: int, say) -> None:
     """Recall on a gallery of embed rows: n images of random 8 x 8 colour blocks through an Xception
     embed="l2" engine, and for each of the B query images four near-duplicates (the image plus uniform
@@ -183,23 +288,27 @@ def embed_recall(n: int, say) -> None:
         f"{sum(len(set(ref[b].tolist()) & {b, B + b, 2 * B + b, 3 * B + b}) for b in range(B))}/{4 * B}")
 
 
-def engine_pairs(n: int, pairs: int, say, dtype: str = "bf16") -> None:
+def engine_pairs(n: int, pairs: int, say, dtype: str = "bf16", sims: dict | None = None) -> None:
     """Pairs of an embed="l2" engine and a similar engine; dtype "fp8": of a bf16-gallery similar
-    engine (in the "l2" column) and an fp8-gallery one."""
+    engine (in the "l2" column) and an fp8-gallery one; ``sims`` {"dense": Similar, "ivf": Similar}: of
+    those two similar engines."""
     from kdl.engine import registry
     from kdl.engine.base import Similar
     from kdl.engine.tuning import tuning_path
     info = registry.get("xception")
     p = info.init_params(0)
-    gal = random_gallery(n, 5)
-    if dtype == "fp8":
+    gal = None if sims else random_gallery(n, 5)
+    if sims:
+        engines = {"l2": info.engine(p, 32, "cuda", similar=sims["dense"]),
+                   "similar": info.engine(p, 32, "cuda", similar=sims["ivf"])}
+    elif dtype == "fp8":
         codes, scale = random_gallery_fp8(n, 5)
         engines = {"l2": info.engine(p, 32, "cuda", similar=Similar(gal, K, "cosine")),
                    "similar": info.engine(p, 32, "cuda", similar=Similar(codes, K, "cosine", scale))}
     else:
         engines = {"l2": info.engine(p, 32, "cuda", embed="l2"),
                    "similar": info.engine(p, 32, "cuda", similar=Similar(gal, K, "cosine"))}
-    first = "similar bf16" if dtype == "fp8" else "embed=l2"
+    first = "similar dense" if sims else "similar bf16" if dtype == "fp8" else "embed=l2"
     x = torch.randint(0, 256, (32, info.input_size, info.input_size, 3), dtype=torch.uint8,
                       generator=torch.Generator().manual_seed(1)).cuda()
     tp = tuning_path(info.tuning or "xception", 32)
@@ -223,7 +332,7 @@ def engine_pairs(n: int, pairs: int, say, dtype: str = "bf16") -> None:
         order = ("l2", "similar") if i % 2 == 0 else ("similar", "l2")
         t = {k: timed(engines[k]) for k in order}
         d = (t["similar"] - t["l2"]) * 1e3
-        say(f"pair {i}: {first} {t['l2']:.4f} ms  similar{' fp8' if dtype == 'fp8' else ''}(N={n}) {t['similar']:.4f} ms  diff {d:+.1f} us "
+        say(f"pair {i}: {first} {t['l2']:.4f} ms  similar{' ivf' if sims else ' fp8' if dtype == 'fp8' else ''}(N={n}) {t['similar']:.4f} ms  diff {d:+.1f} us "
             f"({100 * d / 1e3 / t['l2']:+.2f} %)")
     prof = dict(engines["similar"].profile(32))
     say(f"similar engine.profile(32), eager launches, median of 20: embed_rows {prof['embed_rows'] * 1e3:.1f} us, "
@@ -240,6 +349,7 @@ def main(argv=None) -> int:
     ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--embed-recall", type=int, default=0, metavar="N",
                     help="also count what an fp8 gallery of N Xception embed rows with planted near-duplicates keeps")
+    ap.add_argument("--ivf", default="", metavar="L,NPROBE", help="time the indexed search of L lists, NPROBE probed")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -252,6 +362,16 @@ def main(argv=None) -> int:
         if f:
             f.write(line + "\n")
             f.flush()
+    if a.ivf:
+        lists, nprobe = (int(v) for v in a.ivf.split(","))
+        say(f"== dense gallery_topk vs coarse gallery_topk + gallery_ivf_topk, L={lists} nprobe={nprobe}, F={F} B={B} K={K}")
+        for n in (int(v) for v in a.rows.split(",") if v):
+            for kind in ("clustered", "random"):
+                ivf_rows(n, lists, nprobe, kind, a.iters, a.repeats, max(a.pairs, 1), say)
+        if a.pairs and a.engine_rows:
+            say("== xception b32 forward (captured graph, device events), dense similar vs indexed similar, interleaved pairs")
+            ivf_engine_pairs(a.engine_rows, lists, nprobe, a.pairs, say)
+        return 0
     say(f"== gallery_topk alone{' and torch' if a.dtype == 'bf16' else ', fp8 gallery'}, F={F} B={B} K={K}")
     for n in (int(v) for v in a.rows.split(",") if v):
         (fp8_rows if a.dtype == "fp8" else op_rows)(n, a.iters, a.repeats, say)
