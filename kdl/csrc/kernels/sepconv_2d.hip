@@ -755,13 +755,15 @@ __global__ __launch_bounds__(64 * (WGM * WGN + 1)) void sepconv_2dw_kernel(ConvG
             v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
           }
           u32x2 o = {pack_bf16(v0, v1), pack_bf16(v2, v3)};
-          if (a.res && ok) {                    // residual (bf16-rounded output + residual, as epi_store)
+          if (a.res && ok && n < a.nstore) {    // residual (bf16-rounded output + residual, as epi_store);
+                                                // never read past the stored channels of a res row
             const u32x2 rv = *(const u32x2*)(a.res + ((long)(bimg * H + h) * W + w) * a.ldr + n);
 #pragma unroll
-            for (int d = 0; d < 2; ++d) {
-              o[d] = pack_bf16(bf_lo(o[d]) + bf_lo(rv[d]), bf_hi(o[d]) + bf_hi(rv[d]));
-              if (a.relu_out == 2) o[d] = relu_bf16x2(o[d]);
-            }
+            for (int d = 0; d < 2; ++d) o[d] = pack_bf16(bf_lo(o[d]) + bf_lo(rv[d]), bf_hi(o[d]) + bf_hi(rv[d]));
+          }
+          if (a.relu_out == 2) {                // ReLU after the add, with or without a residual (epi_store)
+#pragma unroll
+            for (int d = 0; d < 2; ++d) o[d] = relu_bf16x2(o[d]);
           }
           if (ok && n < a.nstore) *(u32x2*)(yrow + n) = o;
           acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
