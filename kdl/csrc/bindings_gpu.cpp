@@ -183,6 +183,16 @@ FcMfmaArgs fcm_args(const py::dict& d) {
   a.dt = I(d, "dt");
   return a;
 }
+GroupedConvArgs grouped_conv_args(const py::dict& d) {
+  GroupedConvArgs a{};
+  a.x = P<const uint16_t>(d, "x"); a.wp = P<const uint16_t>(d, "wp"); a.bias = P<const float>(d, "bias");
+  a.y = P<uint16_t>(d, "y");
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.OH = I(d, "OH"); a.OW = I(d, "OW");
+  a.C = I(d, "C"); a.G = I(d, "G"); a.cg = I(d, "cg"); a.stride = I(d, "stride", 1);
+  a.ldx = I(d, "ldx"); a.ldy = I(d, "ldy"); a.relu = I(d, "relu"); a.dt = I(d, "dt");
+  a.rows = I(d, "rows");
+  return a;
+}
 PoolAddArgs pool_args(const py::dict& d) {
   PoolAddArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.res = P<const uint16_t>(d, "res"); a.y = P<uint16_t>(d, "y");
@@ -623,6 +633,11 @@ PYBIND11_MODULE(_C, m) {
     if (gemm_f8_config(cfg, &bm, &bn, &th) != 0) throw std::out_of_range("bad gemm_f8 config");
     return py::make_tuple(bm, bn, th);
   });
+  m.def("grouped_conv", [](py::dict d, uintptr_t s) {
+    const auto a = grouped_conv_args(d);
+    py::gil_scoped_release nogil;
+    chk(grouped_conv(a, S(s)), "grouped_conv");
+  });
   m.def("fc_mfma", [](py::dict d, uintptr_t s) {
     const auto a = fcm_args(d);
     py::gil_scoped_release nogil;
@@ -943,6 +958,9 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_gemm_f8", [](Program& p, const std::string& name, int cfg, py::dict d) {
         Op op; op.kind = OP_GEMM_F8; op.name = name; op.cfg = cfg; op.f8 = f8_args(d); p.add(op);
+      })
+      .def("add_grouped_conv", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_GROUPED_CONV; op.name = name; op.gc = grouped_conv_args(d); p.add(op);
       })
       .def("add_fc_mfma", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_FC_MFMA; op.name = name; op.fcm = fcm_args(d); p.add(op);

@@ -213,6 +213,35 @@ struct FcMfmaArgs {
 };
 hipError_t fc_mfma(const FcMfmaArgs& a, hipStream_t s);
 
+// Grouped 3x3 convolution + bias (+ReLU), G groups of cg channels (grouped_conv.hip): ResNeXt's conv2.
+//   y[b][oy][ox][g*cg + o] = act(bias[g*cg + o] + sum over ky, kx, c < cg of
+//       x[b][oy*stride + ky][ox*stride + kx][g*cg + c] * w[g*cg + o][(ky*3 + kx)*cg + c])
+// x is the zero-bordered buffer a 1x1 conv writes with opad = 1: (H + 2) x (W + 2) pixels per image,
+// so no tap is bounds-checked and the result is the 'same'-padded conv of the H x W interior. y is
+// the un-padded OH x OW map, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1; channels past C
+// of a wider row (ldy > C) are not written. fp32 accumulation, one rounding to the output type.
+// The launcher returns hipErrorInvalidValue and launches nothing unless: cg is 4, 8, 16 or 32;
+// C == G * cg and C % 16 == 0; stride is 1 or 2; OH / OW are as above; ldx, ldy >= C and multiples
+// of 8; every pointer is non-null and 16-byte aligned; 1 <= B <= 65535; and the row ring fits:
+// (3 + stride) * (W + 2) * (2 * SC + 16) <= 64 KiB and stride * (W + 2) <= 128, SC = 64 / 32 / 16
+// channels per workgroup (the widest that divides C): W <= 111 at stride 1, 62 at stride 2.
+struct GroupedConvArgs {
+  const uint16_t* x;      // [B][H + 2][W + 2][ldx], border pixels zero
+  const uint16_t* wp;     // packed [C / 16][KS][64][8] (pack_grouped_fragments, ops/pack.py): per
+                          // 16-channel slab the block-diagonal 16 x 32 tile of each k-step; KS = 5
+                          // (cg <= 16: two taps x 16 channels) or 9 (cg = 32: one tap x 32 channels)
+  const float* bias;      // [C]
+  uint16_t* y;            // [B][OH][OW][ldy]
+  int B, H, W, OH, OW;
+  int C, G, cg;
+  int stride;
+  int ldx, ldy;
+  int relu;               // 0 none, 1 ReLU
+  int dt;                 // element type of x, wp and y: 0 bf16, 1 fp16
+  int rows;               // output rows per workgroup band (0 = chosen by the launcher)
+};
+hipError_t grouped_conv(const GroupedConvArgs& a, hipStream_t s);
+
 // ViT patch embedding input: uint8 NHWC image -> A [B*np][3*P*P] bf16, k = c*P*P + ky*P + kx,
 // normalised on load (per-channel scale/shift).
 struct PatchifyArgs {

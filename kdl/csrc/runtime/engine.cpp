@@ -45,6 +45,7 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_ATTN_AHAT: return attn_ahat(op.ah, s);
     case OP_ROLLOUT_CHAIN: return rollout_chain(op.rc, s);
     case OP_GALLERY_IVF_TOPK: return gallery_ivf_topk(op.gi, s);
+    case OP_GROUPED_CONV: return grouped_conv(op.gc, s);
   }
   return hipErrorInvalidValue;
 }

@@ -104,6 +104,28 @@ def _resnet50(dtype: str = "fp16"):
                      map_size=(7, 7))
 
 
+def _resnext50_32x4d(dtype: str = "fp16"):
+    """torchvision's ``resnext50_32x4d``: ResNet-50's graph with 32-group 3x3 convs on bottleneck widths
+    128 / 256 / 512 / 1024 (kernels/grouped_conv.hip). No tuning table yet: the 1x1 convs run on the
+    default tiles, and the stage cut is ResNet-50's, unmeasured here."""
+    from ..models import resnet as R
+    from .resnet import ResNetEngine
+    arch = R.RESNEXT50_32X4D
+    return ModelInfo("resnext50_32x4d" if dtype == "fp16" else "resnext50_32x4d_bf16", R.INPUT_SIZE, 1000,
+                     R.RESNEXT50_32X4D_PARAMS,
+                     f"ResNeXt-50 32x4d 224x224 (torchvision layout, 25,028,904 params), {dtype}",
+                     lambda seed=0: R.init_params(seed=seed, **arch),
+                     lambda p, max_batch, device, **kw: ResNetEngine(p, max_batch=max_batch, device=device,
+                                                                     dtype=dtype, **arch, **kw),
+                     lambda p, x: R.resnet_forward(p, x, **arch), dtype=dtype,
+                     stage_cut="layer2.1.conv3,layer3.3.conv3", features=2048,
+                     feature_oracle=lambda p, x: _no_grad_mean(lambda q, t: R.features(q, t, **arch), p,
+                                                               R.preprocess(x)),
+                     cam_oracle=lambda p, x: _cam(lambda q, t: R.features(q, t, **arch),
+                                                  _linear_head("fc.weight", "fc.bias"), p, R.preprocess(x)),
+                     map_size=(7, 7))
+
+
 def _vit_b16():
     from ..models import vit as V
     from .vit import ViTEngine
@@ -168,16 +190,18 @@ def _vit_b16_384(fp8: bool = False):
 
 _FACTORIES = {"xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),
               "vit_b16": _vit_b16, "vit_b16_fp8": _vit_b16_fp8, "efficientnet_b7": _efficientnet_b7,
-              "vit_b16_384": _vit_b16_384, "vit_b16_384_fp8": lambda: _vit_b16_384(True)}
+              "vit_b16_384": _vit_b16_384, "vit_b16_384_fp8": lambda: _vit_b16_384(True),
+              "resnext50_32x4d": _resnext50_32x4d, "resnext50_32x4d_bf16": lambda: _resnext50_32x4d("bf16")}
 
 
 # (family, --dtype) -> engine variant; "auto" keeps the family's own default
 _VARIANTS = {("resnet50", "bf16"): "resnet50_bf16", ("resnet50_bf16", "fp16"): "resnet50",
              ("vit_b16", "fp8"): "vit_b16_fp8", ("vit_b16_fp8", "bf16"): "vit_b16",
-             ("vit_b16_384", "fp8"): "vit_b16_384_fp8", ("vit_b16_384_fp8", "bf16"): "vit_b16_384"}
+             ("vit_b16_384", "fp8"): "vit_b16_384_fp8", ("vit_b16_384_fp8", "bf16"): "vit_b16_384",
+             ("resnext50_32x4d", "bf16"): "resnext50_32x4d_bf16", ("resnext50_32x4d_bf16", "fp16"): "resnext50_32x4d"}
 _DTYPES = {"xception": {"bf16"}, "resnet50": {"fp16"}, "resnet50_bf16": {"bf16"}, "vit_b16": {"bf16"},
            "vit_b16_fp8": {"fp8"}, "efficientnet_b7": {"bf16"}, "vit_b16_384": {"bf16"},
-           "vit_b16_384_fp8": {"fp8"}}
+           "vit_b16_384_fp8": {"fp8"}, "resnext50_32x4d": {"fp16"}, "resnext50_32x4d_bf16": {"bf16"}}
 
 
 def variant(family: str, dtype: str = "auto") -> str:

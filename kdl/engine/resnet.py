@@ -12,6 +12,12 @@ Lowering (one launch per box, all captured into one hipGraph per batch bucket):
       conv_gemm MODE_PW   conv3 1x1 + BN, + shortcut, ReLU after the add (relu_out=2)
     gap + fc    global average pool (bf16 features), Dense 2048 -> 1000 on MFMA
 
+ResNeXt-50 32x4d (``groups=32, base_width=4``) is the same lowering on bottleneck widths
+128 / 256 / 512 / 1024 with conv2 as one ``grouped_conv`` launch (kernels/grouped_conv.hip:
+32 groups of 4 / 8 / 16 / 32 channels). ``KDL_GROUPED_CONV=0`` lowers conv2 instead as
+conv_gemm MODE_CONV over the block-diagonal dense expansion of the same folded weights (32 times
+the MACs and weight bytes): for A/B runs and bisection only.
+
 = 2 + 16*3 + 4 + 2 = 56 launches. Buffers: block outputs ping-pong between two
 slabs and each stage owns its padded / mid / shortcut scratch (a few hundred MB
 at batch 32, well inside one MI355X's 288 GB and mostly MALL-resident).
@@ -26,7 +32,7 @@ import torch
 from ..models import resnet as R
 from ..ops import _lib
 from ..ops.conv import MODE_CONV, MODE_PW, ConvGemmLayer, Geometry
-from ..ops.pack import pack_fragments, rowrun_weights
+from ..ops.pack import grouped_dense_weights, pack_fragments, pack_grouped_fragments, rowrun_weights
 from .base import EngineBase, Step
 
 
@@ -41,16 +47,40 @@ def _fold(p: dict, conv: str, bn: str):
     return w_nk, b - m * s
 
 
+class GroupedConvLayer:
+    """A grouped 3x3 conv + BN + ReLU (``grouped_conv``): folded weights [C][9*cg] packed per
+    16-channel slab, fp32 bias [C]."""
+
+    def __init__(self, name: str, w_nk: torch.Tensor, bias: torch.Tensor, *, groups: int, stride: int,
+                 device, dtype: torch.dtype):
+        self.name, self.stride, self.G = name, stride, groups
+        self.C, self.cg = w_nk.shape[0], w_nk.shape[1] // 9
+        assert self.C == groups * self.cg, (name, w_nk.shape, groups)
+        self.dt = int(dtype == torch.float16)
+        self.wp = pack_grouped_fragments(w_nk, self.cg, dtype).to(device).contiguous()
+        self.bias = bias.float().to(device).contiguous()
+
+    def args(self, x: int, y: int, b: int, H: int, W: int, OH: int, OW: int) -> dict:
+        """``H``, ``W``: the interior of the zero-bordered input."""
+        return dict(x=x, wp=_lib.ptr(self.wp), bias=_lib.ptr(self.bias), y=y, B=b, H=H, W=W, OH=OH, OW=OW,
+                    C=self.C, G=self.G, cg=self.cg, stride=self.stride, ldx=self.C, ldy=self.C, relu=1,
+                    dt=self.dt)
+
+
 class ResNetEngine(EngineBase):
     model_name = "resnet50"
+    arch = (1, 64)        # (groups, base_width); the instance's own after __init__
+    grouped = False       # conv2 on grouped_conv (groups > 1 unless KDL_GROUPED_CONV=0)
 
     def __init__(self, params: dict, max_batch: int = 32, device: str | torch.device = "cuda",
                  in_kind: str = "u8", buckets=None, tune_file: str | Path | None = None,
                  dtype: str = "fp16", topk: int = 0, embed: str = "", similar=None, explain: bool = False,
                  overlay=None, overlay_jpeg=None, palette=None, locate=None, cutout=None,
-                 cutout_png=None):
+                 cutout_png=None, groups: int = 1, base_width: int = 64):
         """``dtype``: "fp16" (BASELINE.json's "ResNet-50 224x224 fp16" config: IEEE half
-        activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16"."""
+        activations and weights on v_mfma_f32_16x16x32_f16, fp32 accumulation) or "bf16".
+        ``groups``, ``base_width``: the architecture (models/resnet.py): (1, 64) ResNet-50,
+        (32, 4) ResNeXt-50 32x4d."""
         super().__init__(device, max_batch, buckets, topk, embed, similar, explain, overlay=overlay,
                          overlay_jpeg=overlay_jpeg, palette=palette, locate=locate, cutout=cutout,
                          cutout_png=cutout_png)
@@ -59,6 +89,10 @@ class ResNetEngine(EngineBase):
         self.in_kind = in_kind
         self.dtype = torch.float16 if dtype == "fp16" else torch.bfloat16
         self.dt = int(dtype == "fp16")
+        self.arch = (groups, base_width)
+        if groups > 1:
+            self.model_name = f"resnext50_{groups}x{base_width}d"
+        self.grouped = groups > 1 and os.environ.get("KDL_GROUPED_CONV", "1") != "0"
         self.size = R.INPUT_SIZE
         self.classes = params["fc.bias"].numel()
         self.shapes: dict[str, tuple[int, int, int, int]] = {}   # buffer -> (H, W, C, border)
@@ -92,7 +126,7 @@ class ResNetEngine(EngineBase):
                                extra=dict(C=64)))
         H, cur, ping = ph, "pool", 0
         self.shapes["pool"] = (H, H, 64, 0)
-        for blk in R.blocks():
+        for blk in R.blocks(*self.arch):
             wdt, cout = blk.width, blk.cout
             oh = (H + 2 - 3) // blk.stride + 1
             tpad, tmid = f"pad{H}_{wdt}", f"mid{oh}_{wdt}"
@@ -106,9 +140,16 @@ class ResNetEngine(EngineBase):
                                relu_out=1, device=dev, dtype=self.dtype, ksplit=sk if H <= 14 else ())
             self.steps.append(Step("conv", l1.name, l1, cur, tpad, geom=(H, H, H, H), extra=dict(opad=1)))
             w2, b2 = _fold(p, f"{blk.prefix}.conv2.weight", f"{blk.prefix}.bn2")
-            l2 = ConvGemmLayer(f"{blk.prefix}.conv2", MODE_CONV, w2, b2, cin_pad=wdt, n=wdt,
-                               stride=blk.stride, relu_out=1, device=dev, dtype=self.dtype, ksplit=sk)
-            self.steps.append(Step("conv", l2.name, l2, tpad, tmid, geom=(H + 2, H + 2, oh, oh)))
+            if self.grouped:
+                l2 = GroupedConvLayer(f"{blk.prefix}.conv2", w2, b2, groups=blk.groups, stride=blk.stride,
+                                      device=dev, dtype=self.dtype)
+                self.steps.append(Step("gconv", l2.name, l2, tpad, tmid, geom=(H, H, oh, oh)))
+            else:
+                if blk.groups > 1:      # the dense lowering of the grouped conv
+                    w2 = grouped_dense_weights(w2, wdt // blk.groups)
+                l2 = ConvGemmLayer(f"{blk.prefix}.conv2", MODE_CONV, w2, b2, cin_pad=wdt, n=wdt,
+                                   stride=blk.stride, relu_out=1, device=dev, dtype=self.dtype, ksplit=sk)
+                self.steps.append(Step("conv", l2.name, l2, tpad, tmid, geom=(H + 2, H + 2, oh, oh)))
             if blk.downsample:
                 sc = f"sc{oh}_{cout}"
                 self.shapes[sc] = (oh, oh, cout, 0)
@@ -136,7 +177,7 @@ class ResNetEngine(EngineBase):
         # K-rotated LDS-DMA GEMMs (each M tile starts its K loop at its own step): measured
         # +3.1 % img/s, p50 -2.4 % on ResNet-50 fp16 (profiles/krot_ab.txt)
         for st in self.steps:
-            if getattr(st, "layer", None) is not None:
+            if st.kind == "conv":
                 st.layer.krot = 1
 
     def _alloc(self) -> None:
@@ -211,6 +252,9 @@ class ResNetEngine(EngineBase):
                                               algo=1))   # pixel-per-thread: row-streaming measured -0.3 %
         elif step.kind == "conv":
             self._emit_conv(prog, step, b)
+        elif step.kind == "gconv":
+            prog.add_grouped_conv(step.name, step.layer.args(self._ptr(step.src), self._ptr(step.dst), b,
+                                                             H, W, OH, OW))
         elif step.kind == "gap":
             prog.add_gap(step.name, dict(x=self._ptr(step.src), y=None, yb=self._ptr("feat"), B=b, HW=H * W,
                                          ldx=self._ld(step.src), F=step.extra["F"], dt=self.dt))
@@ -223,5 +267,5 @@ class ResNetEngine(EngineBase):
             raise ValueError(step.kind)
 
     def flops_per_image(self) -> float:
-        return 2.0 * R.macs_per_image()
+        return 2.0 * R.macs_per_image(*self.arch)
 

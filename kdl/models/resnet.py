@@ -29,6 +29,10 @@ STD = (0.229, 0.224, 0.225)
 TOTAL_PARAMS = 25_557_032          # torchvision resnet50, trainable parameters
 STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))   # (width, blocks, stride)
 EXPANSION = 4
+# ResNeXt-50 32x4d (Xie et al. 2017; torchvision resnext50_32x4d): the same graph with
+# groups = 32, base_width = 4: bottleneck width planes * 2 and a 32-group 3x3 conv2
+RESNEXT50_32X4D = dict(groups=32, base_width=4)
+RESNEXT50_32X4D_PARAMS = 25_028_904    # torchvision resnext50_32x4d, trainable parameters
 
 
 @dataclass(frozen=True)
@@ -38,18 +42,22 @@ class Bottleneck:
     width: int
     stride: int
     downsample: bool
+    planes: int = 0  # the stage's nominal width (0: = width, ResNet-50); cout = planes * 4
+    groups: int = 1  # groups of conv2
 
     @property
     def cout(self) -> int:
-        return self.width * EXPANSION
+        return (self.planes or self.width) * EXPANSION
 
 
-def blocks() -> list[Bottleneck]:
+def blocks(groups: int = 1, base_width: int = 64) -> list[Bottleneck]:
+    """torchvision's Bottleneck: width = planes * base_width / 64 * groups."""
     out, cin = [], 64
     for si, (w, n, s) in enumerate(STAGES, start=1):
         for bi in range(n):
             stride = s if bi == 0 else 1
-            out.append(Bottleneck(f"layer{si}.{bi}", cin, w, stride, bi == 0))
+            out.append(Bottleneck(f"layer{si}.{bi}", cin, w * base_width // 64 * groups, stride, bi == 0, w,
+                                  groups))
             cin = w * EXPANSION
     return out
 
@@ -59,12 +67,12 @@ def _bn_shapes(name: str, c: int) -> dict:
             f"{name}.running_var": (c,)}
 
 
-def param_shapes(num_classes: int = NUM_CLASSES) -> dict[str, tuple]:
+def param_shapes(num_classes: int = NUM_CLASSES, groups: int = 1, base_width: int = 64) -> dict[str, tuple]:
     s = {"conv1.weight": (64, 3, 7, 7), **_bn_shapes("bn1", 64)}
-    for b in blocks():
+    for b in blocks(groups, base_width):
         s[f"{b.prefix}.conv1.weight"] = (b.width, b.cin, 1, 1)
         s.update(_bn_shapes(f"{b.prefix}.bn1", b.width))
-        s[f"{b.prefix}.conv2.weight"] = (b.width, b.width, 3, 3)
+        s[f"{b.prefix}.conv2.weight"] = (b.width, b.width // b.groups, 3, 3)
         s.update(_bn_shapes(f"{b.prefix}.bn2", b.width))
         s[f"{b.prefix}.conv3.weight"] = (b.cout, b.width, 1, 1)
         s.update(_bn_shapes(f"{b.prefix}.bn3", b.cout))
@@ -76,9 +84,9 @@ def param_shapes(num_classes: int = NUM_CLASSES) -> dict[str, tuple]:
     return s
 
 
-def count_params(num_classes: int = NUM_CLASSES) -> int:
+def count_params(num_classes: int = NUM_CLASSES, groups: int = 1, base_width: int = 64) -> int:
     n = 0
-    for k, shp in param_shapes(num_classes).items():
+    for k, shp in param_shapes(num_classes, groups, base_width).items():
         if k.endswith("running_mean") or k.endswith("running_var"):
             continue
         p = 1
@@ -89,12 +97,12 @@ def count_params(num_classes: int = NUM_CLASSES) -> int:
 
 
 def init_params(seed: int = 0, num_classes: int = NUM_CLASSES, calibrate: bool = True,
-                calib_batch: int = 2) -> dict[str, torch.Tensor]:
+                calib_batch: int = 2, groups: int = 1, base_width: int = 64) -> dict[str, torch.Tensor]:
     """Random-init weights of the exact architecture; BN statistics calibrated on a
     random batch so activations keep a trained-like scale (see xception.init_params)."""
     g = torch.Generator().manual_seed(seed)
     p = {}
-    for k, shp in param_shapes(num_classes).items():
+    for k, shp in param_shapes(num_classes, groups, base_width).items():
         if k.endswith(".running_mean"):
             t = torch.zeros(shp)
         elif k.endswith(".running_var"):
@@ -113,7 +121,7 @@ def init_params(seed: int = 0, num_classes: int = NUM_CLASSES, calibrate: bool =
         p[k] = t.float()
     if calibrate:
         x = torch.randint(0, 256, (calib_batch, INPUT_SIZE, INPUT_SIZE, 3), generator=g, dtype=torch.uint8)
-        resnet_forward(p, x, calibrate_bn=True)
+        resnet_forward(p, x, calibrate_bn=True, groups=groups, base_width=base_width)
     return p
 
 
@@ -134,14 +142,14 @@ def _bn(x, p, name, calibrate):
 
 
 @torch.no_grad()
-def features(p, x_nchw, calibrate_bn: bool = False) -> torch.Tensor:
+def features(p, x_nchw, calibrate_bn: bool = False, groups: int = 1, base_width: int = 64) -> torch.Tensor:
     x = F.conv2d(x_nchw, p["conv1.weight"], stride=2, padding=3)
     x = torch.relu(_bn(x, p, "bn1", calibrate_bn))
     x = F.max_pool2d(x, 3, 2, 1)
-    for b in blocks():
+    for b in blocks(groups, base_width):
         y = torch.relu(_bn(F.conv2d(x, p[f"{b.prefix}.conv1.weight"]), p, f"{b.prefix}.bn1", calibrate_bn))
-        y = torch.relu(_bn(F.conv2d(y, p[f"{b.prefix}.conv2.weight"], stride=b.stride, padding=1), p,
-                           f"{b.prefix}.bn2", calibrate_bn))
+        y = torch.relu(_bn(F.conv2d(y, p[f"{b.prefix}.conv2.weight"], stride=b.stride, padding=1,
+                                    groups=b.groups), p, f"{b.prefix}.bn2", calibrate_bn))
         y = _bn(F.conv2d(y, p[f"{b.prefix}.conv3.weight"]), p, f"{b.prefix}.bn3", calibrate_bn)
         if b.downsample:
             sc = _bn(F.conv2d(x, p[f"{b.prefix}.downsample.0.weight"], stride=b.stride), p,
@@ -153,20 +161,21 @@ def features(p, x_nchw, calibrate_bn: bool = False) -> torch.Tensor:
 
 
 @torch.no_grad()
-def resnet_forward(p, x_u8_nhwc: torch.Tensor, calibrate_bn: bool = False) -> torch.Tensor:
+def resnet_forward(p, x_u8_nhwc: torch.Tensor, calibrate_bn: bool = False, groups: int = 1,
+                   base_width: int = 64) -> torch.Tensor:
     """fp32 oracle: uint8 NHWC [B,224,224,3] -> logits [B,1000]."""
-    f = features(p, preprocess(x_u8_nhwc), calibrate_bn)
+    f = features(p, preprocess(x_u8_nhwc), calibrate_bn, groups, base_width)
     return f.mean(dim=(2, 3)) @ p["fc.weight"].t() + p["fc.bias"]
 
 
-def macs_per_image() -> int:
+def macs_per_image(groups: int = 1, base_width: int = 64) -> int:
     """Multiply-accumulates of one 224x224 forward (convs + fc)."""
     total = 112 * 112 * 64 * 3 * 49
     h = 56
-    for b in blocks():
+    for b in blocks(groups, base_width):
         oh = h // b.stride
         total += h * h * b.width * b.cin
-        total += oh * oh * b.width * b.width * 9
+        total += oh * oh * b.width * (b.width // b.groups) * 9
         total += oh * oh * b.cout * b.width
         if b.downsample:
             total += oh * oh * b.cout * b.cin

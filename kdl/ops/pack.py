@@ -44,6 +44,43 @@ def unpack_fragments(packed: torch.Tensor, n: int, k: int) -> torch.Tensor:
     return t.view(nf * 16, kt * 32)[:n, :k]
 
 
+def grouped_slab_weights(w_nk: torch.Tensor, cg: int) -> torch.Tensor:
+    """Grouped 3x3 weights W[C][9*cg] (k = tap*cg + c, row o in group o // cg) -> the per-slab
+    dense tiles [C][KS*32] that grouped_conv.hip multiplies: row o's k-step t holds, for
+    cg <= 16 (KS = 5), taps 2t and 2t + 1 over the 16 input channels of o's own 16-channel slab
+    (k = 32t + 16*(tap & 1) + slab channel; zero outside o's group and for the tenth tap), and
+    for cg = 32 (KS = 9) tap t over the group's 32 channels."""
+    C, k = w_nk.shape
+    assert cg in (4, 8, 16, 32) and k == 9 * cg and C % max(cg, 16) == 0, (w_nk.shape, cg)
+    w = w_nk.reshape(C, 9, cg)
+    if cg == 32:
+        return w.reshape(C, 9 * 32)
+    out = torch.zeros(C, 10, 16, dtype=w_nk.dtype)
+    first = (torch.arange(C) % 16) // cg * cg          # o's group starts here inside its slab
+    for c in range(cg):
+        out[torch.arange(C), :9, first + c] = w[:, :, c]
+    return out.reshape(C, 5 * 32)
+
+
+def pack_grouped_fragments(w_nk: torch.Tensor, cg: int, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Grouped 3x3 weights W[C][9*cg] -> ``dtype`` [C/16][KS][64][8] in MFMA fragment order
+    (GroupedConvArgs.wp): ``pack_fragments`` of the slab tiles, one 16-row fragment per slab."""
+    t = grouped_slab_weights(w_nk, cg)
+    return pack_fragments(t, t.shape[0] // 16, t.shape[1] // 32, dtype)
+
+
+def grouped_dense_weights(w_nk: torch.Tensor, cg: int) -> torch.Tensor:
+    """Grouped 3x3 weights W[C][9*cg] -> the block-diagonal dense W[C][9*C] (k = tap*C + c) of the
+    same convolution: the MODE_CONV lowering, G times the MACs and weight bytes."""
+    C = w_nk.shape[0]
+    w = w_nk.reshape(C, 9, cg)
+    out = torch.zeros(C, 9, C, dtype=w_nk.dtype)
+    first = torch.arange(C) // cg * cg
+    for c in range(cg):
+        out[torch.arange(C), :, first + c] = w[:, :, c]
+    return out.reshape(C, 9 * C)
+
+
 def pad_vec(v: torch.Tensor, n: int) -> torch.Tensor:
     out = torch.zeros(n, dtype=torch.float32)
     out[: v.numel()] = v.float()
