@@ -5,7 +5,7 @@
                                              the conv kernels, kernels bf16: kdl.ingest.fold;
                                              --keep-bn: the Keras fp32 variables as they are)
                                              + kdl_model.json (head, signatures)
-  make-synthetic <repo>/<version> [--seed] [--model xception|resnet50|resnext50_32x4d|vit_b16|efficientnet_b7]
+  make-synthetic <repo>/<version> [--seed] [--model xception|resnet50|resnext50_32x4d|convnext_tiny|vit_b16|efficientnet_b7]
                                              random-init weights of the exact architecture (Xception:
                                              a SavedModel; other families: torchvision-layout safetensors)
   build-gallery <version_dir> <images_dir> [--device cpu|gpu] [--ivf_lists L]

@@ -193,6 +193,23 @@ GroupedConvArgs grouped_conv_args(const py::dict& d) {
   a.rows = I(d, "rows");
   return a;
 }
+DwLnArgs dwln_args(const py::dict& d) {
+  DwLnArgs a{};
+  a.x = P<const uint16_t>(d, "x"); a.w = P<const float>(d, "w"); a.bias = P<const float>(d, "bias");
+  a.gamma = P<const float>(d, "gamma"); a.beta = P<const float>(d, "beta"); a.y = P<uint16_t>(d, "y");
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.C = I(d, "C");
+  a.ldx = I(d, "ldx"); a.ldy = I(d, "ldy"); a.eps = F(d, "eps", 1e-6f);
+  a.rows = I(d, "rows"); a.tw = I(d, "tw");
+  return a;
+}
+LnS2dArgs ln_s2d_args(const py::dict& d) {
+  LnS2dArgs a{};
+  a.x = P<const uint16_t>(d, "x"); a.gamma = P<const float>(d, "gamma"); a.beta = P<const float>(d, "beta");
+  a.y = P<uint16_t>(d, "y");
+  a.B = I(d, "B"); a.H = I(d, "H"); a.W = I(d, "W"); a.C = I(d, "C");
+  a.ldx = I(d, "ldx"); a.ldy = I(d, "ldy"); a.eps = F(d, "eps", 1e-6f);
+  return a;
+}
 PoolAddArgs pool_args(const py::dict& d) {
   PoolAddArgs a{};
   a.x = P<const uint16_t>(d, "x"); a.res = P<const uint16_t>(d, "res"); a.y = P<uint16_t>(d, "y");
@@ -638,6 +655,21 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     chk(grouped_conv(a, S(s)), "grouped_conv");
   });
+  m.def("dwconv7_ln", [](py::dict d, uintptr_t s) {
+    const auto a = dwln_args(d);
+    py::gil_scoped_release nogil;
+    chk(dwconv7_ln(a, S(s)), "dwconv7_ln");
+  });
+  m.def("dwconv7_ln_plan", [](py::dict d) {     // (band height, strip width) the launcher picks
+    int rows = 0, tw = 0;
+    chk(dwconv7_ln_plan(dwln_args(d), &rows, &tw), "dwconv7_ln_plan");
+    return py::make_tuple(rows, tw);
+  });
+  m.def("ln_s2d", [](py::dict d, uintptr_t s) {
+    const auto a = ln_s2d_args(d);
+    py::gil_scoped_release nogil;
+    chk(ln_s2d(a, S(s)), "ln_s2d");
+  });
   m.def("fc_mfma", [](py::dict d, uintptr_t s) {
     const auto a = fcm_args(d);
     py::gil_scoped_release nogil;
@@ -961,6 +993,12 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("add_grouped_conv", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_GROUPED_CONV; op.name = name; op.gc = grouped_conv_args(d); p.add(op);
+      })
+      .def("add_dwconv7_ln", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_DWCONV7_LN; op.name = name; op.dl = dwln_args(d); p.add(op);
+      })
+      .def("add_ln_s2d", [](Program& p, const std::string& name, py::dict d) {
+        Op op; op.kind = OP_LN_S2D; op.name = name; op.ls = ln_s2d_args(d); p.add(op);
       })
       .def("add_fc_mfma", [](Program& p, const std::string& name, py::dict d) {
         Op op; op.kind = OP_FC_MFMA; op.name = name; op.fcm = fcm_args(d); p.add(op);

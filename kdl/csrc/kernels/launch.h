@@ -242,8 +242,57 @@ struct GroupedConvArgs {
 };
 hipError_t grouped_conv(const GroupedConvArgs& a, hipStream_t s);
 
+// Depthwise 7x7 ('same' zero padding 3, stride 1) + bias, then LayerNorm over the channels of every
+// pixel (dwconv_ln.hip): the head of a ConvNeXt block in one launch.
+//   d[c] = bias[c] + sum over ky, kx < 7 of x[b][oy + ky - 3][ox + kx - 3][c] * w[ky*7 + kx][c]
+//   y[b][oy][ox][c] = gamma[c] * (d[c] - mean_c d) / sqrt(var_c d + eps) + beta[c]
+// d never reaches memory. Accumulation (an fmaf chain from the bias in tap order) and the statistics
+// are fp32; the variance is the mean of the squared deviations from the mean (two passes over the
+// LDS-held d); one rounding, to bf16, at the store. No atomics and a fixed summation order: replays
+// are bit-identical. Channels C..ldy of y are not written; nothing is read outside the B images.
+// The launcher returns hipErrorInvalidValue and launches nothing unless: C % 8 == 0 and
+// 32 <= C <= 1024; ldx, ldy >= C and multiples of 8; every pointer is non-null, x and y 16-byte and
+// the fp32 vectors 4-byte aligned; 1 <= B <= 65535; H, W >= 1; eps > 0; rows, tw >= 0; and the tile
+// fits: nring * LW * (2 C + 16) + 4 C * (LW - 6) <= 160 KiB and LW * C / 8 <= 1536, with R the band
+// height, TW the strip width, nring = min(8, H, R + 6) ring rows and LW = TW rounded up to a multiple
+// of 4 or 7 (whichever is less) + 6 ring columns.
+struct DwLnArgs {
+  const uint16_t* x;      // [B][H][W][ldx] bf16
+  const float* w;         // [49][C]
+  const float* bias;      // [C]
+  const float* gamma;     // [C]
+  const float* beta;      // [C]
+  uint16_t* y;            // [B][H][W][ldy] bf16
+  int B, H, W, C;
+  int ldx, ldy;
+  float eps;
+  int rows;               // output rows per workgroup band (0 = chosen by the launcher)
+  int tw;                 // output columns per workgroup strip (0 = chosen by the launcher)
+};
+hipError_t dwconv7_ln(const DwLnArgs& a, hipStream_t s);
+// The (band height, strip width) dwconv7_ln() launches with: it launches from this plan itself.
+hipError_t dwconv7_ln_plan(const DwLnArgs& a, int* rows, int* tw);
+
+// LayerNorm over the channels of every pixel, written space-to-depth for a 2x2 / stride-2 conv
+// (dwconv_ln.hip): ConvNeXt's downsample input, so that conv is one pointwise GEMM with K = 4 C.
+//   y[(b*H/2 + oy/2)*W/2 + ox/2][((oy & 1)*2 + (ox & 1))*C + c] = LN_c(x[b][oy][ox][:])[c]
+// with LN as above (fp32, two-pass variance, one rounding). Columns 4C..ldy are not written.
+// hipErrorInvalidValue and no launch unless: C % 8 == 0 and 32 <= C <= 1024; H and W even and >= 2;
+// ldx >= C, ldy >= 4 C, both multiples of 8; pointers non-null and aligned as above; B >= 1; eps > 0.
+struct LnS2dArgs {
+  const uint16_t* x;      // [B][H][W][ldx] bf16
+  const float* gamma;     // [C]
+  const float* beta;      // [C]
+  uint16_t* y;            // [B * H/2 * W/2][ldy] bf16
+  int B, H, W, C;
+  int ldx, ldy;
+  float eps;
+};
+hipError_t ln_s2d(const LnS2dArgs& a, hipStream_t s);
+
 // ViT patch embedding input: uint8 NHWC image -> A [B*np][3*P*P] bf16, k = c*P*P + ky*P + kx,
-// normalised on load (per-channel scale/shift).
+// normalised on load (per-channel scale/shift). P is a multiple of 8, or 4 (ConvNeXt's stem:
+// K = 48, eight consecutive k being two patch rows of one channel).
 struct PatchifyArgs {
   const uint8_t* x;
   uint16_t* y;

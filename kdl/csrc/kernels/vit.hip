@@ -24,14 +24,22 @@ __global__ __launch_bounds__(256) void patchify_kernel(PatchifyArgs a) {
   const float sc = c == 0 ? a.scale[0] : c == 1 ? a.scale[1] : a.scale[2];
   const float sh = c == 0 ? a.shift[0] : c == 1 ? a.shift[1] : a.shift[2];
   u32x4 o;
+  if (a.P == 4) {     // eight k = patch rows ky, ky + 1 of the channel, four columns each
+    const uint8_t* s1 = src + (long)a.W * 3;
+    o[0] = pack_bf16((float)src[0] * sc + sh, (float)src[3] * sc + sh);
+    o[1] = pack_bf16((float)src[6] * sc + sh, (float)src[9] * sc + sh);
+    o[2] = pack_bf16((float)s1[0] * sc + sh, (float)s1[3] * sc + sh);
+    o[3] = pack_bf16((float)s1[6] * sc + sh, (float)s1[9] * sc + sh);
+  } else {
 #pragma unroll
-  for (int d = 0; d < 4; ++d)
-    o[d] = pack_bf16((float)src[(2 * d) * 3] * sc + sh, (float)src[(2 * d + 1) * 3] * sc + sh);
+    for (int d = 0; d < 4; ++d)
+      o[d] = pack_bf16((float)src[(2 * d) * 3] * sc + sh, (float)src[(2 * d + 1) * 3] * sc + sh);
+  }
   *(u32x4*)(a.y + row * a.ldy + k0) = o;
 }
 
 hipError_t patchify(const PatchifyArgs& a, hipStream_t s) {
-  if (a.P % 8 != 0 || a.H % a.P != 0 || a.W % a.P != 0) return hipErrorInvalidValue;
+  if ((a.P % 8 != 0 && a.P != 4) || a.P < 4 || a.H % a.P != 0 || a.W % a.P != 0) return hipErrorInvalidValue;
   const long total = (long)a.B * (a.H / a.P) * (a.W / a.P) * (3 * a.P * a.P / 8);
   hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();

@@ -46,6 +46,8 @@ hipError_t run_op(const Op& op, hipStream_t s) {
     case OP_ROLLOUT_CHAIN: return rollout_chain(op.rc, s);
     case OP_GALLERY_IVF_TOPK: return gallery_ivf_topk(op.gi, s);
     case OP_GROUPED_CONV: return grouped_conv(op.gc, s);
+    case OP_DWCONV7_LN: return dwconv7_ln(op.dl, s);
+    case OP_LN_S2D: return ln_s2d(op.ls, s);
   }
   return hipErrorInvalidValue;
 }

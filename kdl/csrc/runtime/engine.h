@@ -20,7 +20,7 @@ enum OpKind { OP_CONV_GEMM = 0, OP_STEM = 1, OP_POOL_ADD = 2, OP_HEAD = 3, OP_RE
               OP_DWK = 14, OP_SE = 15, OP_CHSCALE = 16, OP_GEMM_F8 = 17,
               OP_ENTRY_BLOCK = 21, OP_STEM_CONV = 22, OP_SOFTMAX_TOPK = 23, OP_EMBED_ROWS = 24, OP_GALLERY_TOPK = 25, OP_CLASS_MAP = 26,
               OP_ATTN_ROLLOUT = 27, OP_ROLLOUT_MAP = 28, OP_HEAT_OVERLAY = 29, OP_JPEG_ENCODE = 30, OP_PALETTE = 31, OP_LOCATE = 32, OP_CUTOUT = 33, OP_PNG_ENCODE = 34,
-              OP_ATTN_AHAT = 35, OP_ROLLOUT_CHAIN = 36, OP_GALLERY_IVF_TOPK = 37, OP_GROUPED_CONV = 38 };   // 18: retired (round 6: the SE weight scale, replaced by the project
+              OP_ATTN_AHAT = 35, OP_ROLLOUT_CHAIN = 36, OP_GALLERY_IVF_TOPK = 37, OP_GROUPED_CONV = 38, OP_DWCONV7_LN = 39, OP_LN_S2D = 40 };   // 18: retired (round 6: the SE weight scale, replaced by the project
                                        // GEMM's A-operand scales); 19: retired (the round-3 chained
                                        // middle-flow launch); 20: retired (round 5: the vendor GEMM node
                                        // left the product, tools/probes/blaslt)
@@ -64,6 +64,8 @@ struct Op {
   RolloutChainArgs rc{};
   GalleryIvfArgs gi{};
   GroupedConvArgs gc{};
+  DwLnArgs dl{};
+  LnS2dArgs ls{};
   void* mem_ptr = nullptr;
   size_t mem_bytes = 0;
 };

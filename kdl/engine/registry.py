@@ -188,7 +188,24 @@ def _vit_b16_384(fp8: bool = False):
                      rollout_oracle=lambda p, x: V.vit_rollout(p, x, size=S), map_size=(S // V.PATCH, S // V.PATCH))
 
 
-_FACTORIES = {"xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),
+def _convnext_tiny():
+    """torchvision's ``convnext_tiny``. Its classifier normalises the pooled features (LayerNorm2d between
+    the pool and the Linear), so neither closed-form head of ``class_map`` applies: ``cam_oracle`` and
+    ``rollout_oracle`` are None and the heatmap signatures answer as for any family without a map method.
+    No tuning table yet (default GEMM tiles); the stage cut, behind the third of stage 3's nine blocks,
+    is unmeasured."""
+    from ..models import convnext as CX
+    from .convnext import ConvNeXtEngine
+    return ModelInfo("convnext_tiny", CX.INPUT_SIZE, 1000, CX.TOTAL_PARAMS,
+                     "ConvNeXt-Tiny 224x224 (torchvision layout, 28,589,128 params)",
+                     lambda seed=0: CX.init_params(seed=seed),
+                     lambda p, max_batch, device, **kw: ConvNeXtEngine(p, max_batch=max_batch, device=device, **kw),
+                     CX.convnext_forward, stage_cut="features.5.2.block.5", features=CX.DIMS[-1],
+                     feature_oracle=lambda p, x: _no_grad_mean(CX.features, p, CX.preprocess(x)),
+                     cam_oracle=None, rollout_oracle=None, map_size=())
+
+
+_FACTORIES = {"convnext_tiny": _convnext_tiny, "xception": _xception, "resnet50": _resnet50, "resnet50_bf16": lambda: _resnet50("bf16"),
               "vit_b16": _vit_b16, "vit_b16_fp8": _vit_b16_fp8, "efficientnet_b7": _efficientnet_b7,
               "vit_b16_384": _vit_b16_384, "vit_b16_384_fp8": lambda: _vit_b16_384(True),
               "resnext50_32x4d": _resnext50_32x4d, "resnext50_32x4d_bf16": lambda: _resnext50_32x4d("bf16")}
@@ -201,7 +218,8 @@ _VARIANTS = {("resnet50", "bf16"): "resnet50_bf16", ("resnet50_bf16", "fp16"): "
              ("resnext50_32x4d", "bf16"): "resnext50_32x4d_bf16", ("resnext50_32x4d_bf16", "fp16"): "resnext50_32x4d"}
 _DTYPES = {"xception": {"bf16"}, "resnet50": {"fp16"}, "resnet50_bf16": {"bf16"}, "vit_b16": {"bf16"},
            "vit_b16_fp8": {"fp8"}, "efficientnet_b7": {"bf16"}, "vit_b16_384": {"bf16"},
-           "vit_b16_384_fp8": {"fp8"}, "resnext50_32x4d": {"fp16"}, "resnext50_32x4d_bf16": {"bf16"}}
+           "vit_b16_384_fp8": {"fp8"}, "resnext50_32x4d": {"fp16"}, "resnext50_32x4d_bf16": {"bf16"},
+           "convnext_tiny": {"bf16"}}
 
 
 def variant(family: str, dtype: str = "auto") -> str:

@@ -81,6 +81,22 @@ def grouped_dense_weights(w_nk: torch.Tensor, cg: int) -> torch.Tensor:
     return out.reshape(C, 9 * C)
 
 
+def fold_layer_scale(w: torch.Tensor, b: torch.Tensor, scale: torch.Tensor):
+    """ConvNeXt's ``layer_scale`` [C, 1, 1] folded into the block's last linear W [C][4C], b [C]:
+    scale * (W h + b) = (scale W) h + scale b, in float64 (the GEMM's epilogue then adds the
+    block input as its residual)."""
+    s = scale.double().reshape(-1)
+    return w.double() * s[:, None], b.double() * s
+
+
+def s2d_weights(w_oihw: torch.Tensor) -> torch.Tensor:
+    """A 2x2 / stride-2 conv weight [O][C][2][2] -> W[O][4C] with k = (ky*2 + kx)*C + c: the column
+    order ``ln_s2d`` writes, so the conv is one pointwise GEMM over its space-to-depth rows."""
+    o, c, kh, kw = w_oihw.shape
+    assert (kh, kw) == (2, 2), w_oihw.shape
+    return w_oihw.double().permute(0, 2, 3, 1).reshape(o, 4 * c)
+
+
 def pad_vec(v: torch.Tensor, n: int) -> torch.Tensor:
     out = torch.zeros(n, dtype=torch.float32)
     out[: v.numel()] = v.float()
